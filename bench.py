@@ -7,11 +7,13 @@ S exposure sub-samples -> camera delta -> projection -> tile binning + per-tile 
 exposure blend -> loss = <blended, Wimg> + <acc, Wacc> -> gradients to every leaf (means, quats, scales,
 opacities, colours, motion coefficients, bases, times, camera deltas, viewmat).  Inputs are resident in HBM
 before the timed region.  value = Gaussians / t_frame (whole job); `instances_per_s` = N*S / t_frame.
-The line also carries `roofline` (+ `roofline_hbm`, `roofline_streaming`) for the dominant kernel of WHATEVER `--config` was run - live
-launch durations from HIP events, counters from the hash-stamped files under profiles/ - the measured ceilings of the box, `cpu_baseline`
-(default config only), and `sustained`: the same step function run for `--sustain` seconds (default 6) right after the timed region,
-reported beside `value`, never as it.  Eager steps verify their intersection-list sizes at most CHECK_LAG steps late and all of them
-before the clock stops (`config.size_check`).
+A plain run sets up, runs the --warmup steps (+ the graph capture, if any, and the --pre-roll steps), times --steps steps, writes
+the last timed step's outputs if --dump-outputs DIR is given, and prints the line.
+With `--full` the line also carries `roofline` (+ `roofline_hbm`, `roofline_streaming`) for the dominant kernel of WHATEVER `--config` was
+run - live launch durations from HIP events, counters from the hash-stamped files under profiles/ - the measured ceilings of the box,
+`n_isect_per_step`, `cpu_baseline` (default config only), and `sustained`: the same step function run for `--sustain` seconds (default 6)
+right after the timed region, reported beside `value`, never as it.  Eager steps verify their intersection-list sizes at most CHECK_LAG
+steps late and all of them before the clock stops (`config.size_check`).
 
 Configs (`--config`): cfg1 / cfg2 (headline, default) / cfg3 / cfg5 = BASELINE.json's, `refdefault[720]` = the
 reference's own training shape (40 k dynamic + 100 k static Gaussians, 20 bases, 11 sub-samples, 17 channels:
@@ -24,7 +26,7 @@ the max / min policy channels; HIP kernels d4gs_blend_shard_* around the collect
 all-reduce of the winning sub-sample, leaf gradients are all-reduced; the whole step, collectives included, is replayed
 from ONE HIP graph (`--no-graph`: eager).  Total work is fixed -> "scaling": "strong", value = N / t, and the N = 1
 value equals the single-GPU line.  The view-sharded (data-parallel) throughput - every rank renders its own full frame, "weak" scaling,
-value = world * N / t - is measured right after the timed region and reported as the secondary object
+value = world * N / t - is measured right after the timed region (with `--full`) and reported as the secondary object
 `views_weak_scaling`, and from N = 4 the (N/2) views x 2-way exposure mesh as `views_x_exposure_mesh` (value = views * N / t, weak).
 `--shard views` / `--shard mesh --mesh VxE` make one of them the primary line instead.
 """
@@ -75,8 +77,17 @@ def flops_per_pair(bwd: bool, n_ch: int) -> float:
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps (ms_per_step = their wall time / --steps)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: HIP-event kernel timings and the roofline objects, the measured ceilings "
+                         "(unless --no-peaks), the sustained phase (--sustain), the exact intersection count of the benched scene "
+                         "(n_isect_per_step), the CPU baseline (unless --no-cpu-baseline) and, at N > 1, the secondary shardings; "
+                         "without it the run only warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed - the render outputs (renders, alphas, blended, "
+                         "acc; single-process path) and every leaf gradient - as DIR/<name>.npy (float32), at most 64 MB in all: above that "
+                         "every large array keeps the same fixed, seeded sample of its elements (flattened)")
     ap.add_argument("--pre-roll", type=int, default=30,
                     help="untimed steps between the warm-up steps (+ the graph capture, if any) and the timed region (reported in config.pre_roll_steps): the first ~10 steps of a process run "
                          "3-7 %% slow (list-size guesses, row mode and lazy-sort decisions settle within 3; the device then needs ~15 ms of "
@@ -140,6 +151,28 @@ def parse():
 
 def to_dev(sc, dev):
     return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in sc.items()}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_WHOLE_ELEMS = 4096  # arrays up to this size are always written whole
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> host tensor) as path/<name>.npy.  Above DUMP_LIMIT_BYTES in all, every array of more than
+    DUMP_WHOLE_ELEMS elements is replaced by the same fraction of its flattened elements, at indices drawn by a fixed seed (sorted,
+    duplicates dropped) - so two builds given the same arguments write the same sample."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: (v if v.dtype in (torch.float32, torch.float64) else v.float()).contiguous().numpy() for k, v in arrays.items()}
+    small = sum(a.nbytes for a in arrs.values() if a.size <= DUMP_WHOLE_ELEMS)
+    large = sum(a.nbytes for a in arrs.values() if a.size > DUMP_WHOLE_ELEMS)
+    keep = 1.0 if small + large <= DUMP_LIMIT_BYTES else (DUMP_LIMIT_BYTES - small) / large
+    for i, (k, a) in enumerate(sorted(arrs.items())):
+        if keep < 1.0 and a.size > DUMP_WHOLE_ELEMS:
+            idx = np.unique(np.random.default_rng(1000 + i).integers(0, a.size, int(a.size * keep)))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 LEAVES = ("means", "quats", "scales", "opacities", "colors", "motion_coefs", "rots", "transls", "times", "RTs", "viewmat")
@@ -494,7 +527,7 @@ def main():
         raise SystemExit(f"exposure sharding needs its width <= S ({primary_mesh[1]} > {S})")
     bg = torch.ones(channels, device=dev)
     lib = None if dry else L.lib()
-    prof_ok = not args.no_profile and not dry
+    prof_ok = args.full and not args.no_profile and not dry
     _groups = {}
 
     def exposure_group(V, E):
@@ -566,10 +599,10 @@ def main():
             return None
 
 
-    def measure(mode, mesh, steps, warmup, profile, use_graph):
+    def measure(mode, mesh, steps, warmup, profile, use_graph, keep_outputs=False):
         """One measurement of `mode` (mesh = (V, E)): warm-up, optional HIP-graph capture, pre-roll, the timed region.
         -> dict(dt = seconds for `steps` steps (max over ranks), kern / kern_all / n_break = live kernel timings, st = last state,
-                graph_note, step_stats)"""
+                graph_note, step_stats, outputs = host copies of what the last timed step computed (keep_outputs) or None)"""
         graph_note, step_stats = {}, {}
         if use_graph:
             profile = False  # HIP events cannot bracket kernels inside a replayed graph
@@ -618,6 +651,8 @@ def main():
                 loss = torch.dot(res["blended"].reshape(-1), wimg.reshape(-1)) + torch.dot(res["acc"].reshape(-1), wacc.reshape(-1))
                 loss.backward()
                 last["st"] = res["state"]
+                if keep_outputs:
+                    last["res"] = res
             else:
                 last["st"] = sharder.step(leaves, d["K"], W, H, bg, wimg, wacc)
             if mode_flag["deferred"] and not dry:
@@ -663,6 +698,8 @@ def main():
                                       lazy_sort=True if args.lazy_sort else None)
                 loss = torch.dot(res["blended"].reshape(-1), wimg.reshape(-1)) + torch.dot(res["acc"].reshape(-1), wacc.reshape(-1))
                 loss.backward()
+                if keep_outputs:
+                    last["res"] = res  # (inside the capture: the graph's own output tensors, which every replay rewrites)
                 return res["state"]
 
             if not dry:
@@ -756,13 +793,18 @@ def main():
         step_stats["host_ms_max_at"] = host_gaps.index(max(host_gaps))
         step_stats["slowest"] = [(i, round(1e3 * g, 4)) for g, i in sorted(((g, i) for i, g in enumerate(host_gaps)), reverse=True)[:5]]
         step_stats["last_sync_ms"] = 1e3 * (t0 + dt - marks[-1])
+        outputs = None
+        if keep_outputs:  # (the clock has stopped: host copies of the LAST timed step's results, before anything below runs another step)
+            outputs = {k: last["res"][k].detach().cpu() for k in ("renders", "alphas", "blended", "acc")
+                       if "res" in last and torch.is_tensor(last["res"].get(k))}
+            outputs.update({"grad_" + k: v.grad.detach().cpu() for k, v in leaves.items() if v.grad is not None})
         kern, kern_all, n_break = {}, {}, 0
         if profile:
             kern = collect()  # the dominant kernels, measured live over the timed region
         # sustained cross-check (N = 1, untimed for `value`): the SAME step function for --sustain seconds.  K = 20 steps are 25 ms of
         # device time - too short for an outside monitor to see the GPU busy at all (the driver's 5-s samples read 0.0) and
         # short enough to be a clock burst; the rate over several seconds is reported beside it.
-        if args.sustain > 0 and not dry and world == 1 and not args.share > 1:
+        if args.full and args.sustain > 0 and not dry and world == 1 and not args.share > 1:
             n_s, t_s = 0, time.perf_counter()
             while time.perf_counter() - t_s < args.sustain:
                 for _ in range(100):
@@ -783,7 +825,7 @@ def main():
                 kern = {k: v for k, v in kern_all.items() if k.startswith("k_raster_bwd")}
                 graph_note["roofline_timing"] = (f"the timed region replays a HIP graph, whose kernels HIP events cannot bracket: the roofline "
                                                  f"kernel's duration is its average over {n_break} untimed eager steps run right after it")
-        if not dry:  # one untimed STAGED step with host-checked sizes: its state carries the exact counts and the
+        if args.full and not dry:  # one untimed STAGED step with host-checked sizes: its state carries the exact counts and the
             mode_flag["deferred"] = False  # per-stage buffers (tile offsets, last ids) of the byte / pair accounting below
             mode_flag["fused"] = False
             if sharder is not None:
@@ -798,7 +840,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         return dict(dt=dt, kern=kern, kern_all=kern_all, n_break=n_break, st=last["st"], graph_note=graph_note, step_stats=step_stats,
-                    graph_used=bool(use_graph and "fallback" not in graph_note))
+                    graph_used=bool(use_graph and "fallback" not in graph_note), outputs=outputs)
 
     def parallelism_of(mode, mesh):
         V, E = mesh
@@ -866,7 +908,8 @@ def main():
             return out
         n_isect = st.n_isect
         S_loc = st.cfg.S
-        out["n_isect_per_step"] = n_isect if world == 1 else None
+        if args.full:  # (exact only after measure()'s host-checked staged step; a deferred state holds the list capacity)
+            out["n_isect_per_step"] = n_isect if world == 1 else None
         out["config"]["pre_roll_steps"] = args.pre_roll
         if "sustained" in step_stats:
             sus = step_stats.pop("sustained")
@@ -874,6 +917,8 @@ def main():
             out["sustained"] = sus
         out["host_step_times"] = dict(step_stats, note="per-step host time between the returns of consecutive steps inside the timed region (diagnostic)")
         # (after every timed region: ~30 ms of full-rate FMA issue right in front of one cost it 0.2 % - 1.4052 against 1.4024 ms, four runs each)
+        if not args.full:
+            return out
         peaks = measured_peaks() if not args.no_peaks else None
         out["peaks_measured"] = peaks
         if kern:
@@ -1006,23 +1051,26 @@ def main():
         return out
 
     # ---- the measurements.  N = 1: one (eager by default).  N > 1: the EAGER primary step first - its line is kept - then, under the
-    # watchdog, the HIP-graph version of it and the secondary shardings; one JSON line whatever happens after the first measurement.
+    # watchdog, the HIP-graph version of it and (--full) the secondary shardings; one JSON line whatever happens after the first measurement.
     first_graph = want_graph and not eager_first
     wd = Watchdog(rank, args.graph_timeout) if world > 1 else None
     if wd:  # nothing to print if THIS hangs (communicator bring-up, the first collective): leave with exit code 3 instead of waiting
         wd.kick("eager primary step (communicator bring-up, first collectives)", scale=3.0)  # for RCCL's 600 s watchdog / the driver's clock
         if dry and os.environ.get("D4GS_BENCH_INJECT_HANG") == "eager" and rank == world - 1:
             time.sleep(1e6)  # tests/test_parallel_gloo.py: a rank that never joins the first collective
-    res = measure(primary_mode, primary_mesh, args.steps, args.warmup, prof_ok and not first_graph, first_graph)
+    keep = bool(args.dump_outputs) and rank == 0
+    res = measure(primary_mode, primary_mesh, args.steps, args.warmup, prof_ok and not first_graph, first_graph, keep)
     out = line_of(res, primary_mode, primary_mesh)
+    outputs = res["outputs"]
     if world > 1:
         graph_ok = False
         if eager_first:
             out["config"]["launch"] = "eager step (the HIP-graph attempt had not finished)"
             wd.kick("HIP-graph capture + replays of the primary step (RCCL collectives inside)", out)
-            resg = measure(primary_mode, primary_mesh, args.steps, args.warmup, False, True)
+            resg = measure(primary_mode, primary_mesh, args.steps, args.warmup, False, True, keep)
             graph_ok = resg["graph_used"]
             if graph_ok:
+                outputs = resg["outputs"]
                 t = resg["dt"] / args.steps
                 out["eager"] = {"value": out["value"], "ms_per_step": out["ms_per_step"], "host_step_times": out.pop("host_step_times", None),
                                 "note": "the same step issued eagerly (~40 launches + the collectives per step from Python), measured first"}
@@ -1035,29 +1083,32 @@ def main():
                                                       "(events cannot bracket kernels of a replayed graph); same kernels, same launch geometry")
             else:
                 out["config"]["launch"] = "eager step: " + (resg["graph_note"].get("fallback") or "the captured step was not used")
-        cands = [("exposure", (1, world), "exposure_strong_scaling")]
-        if world >= 4 and world % 2 == 0:
-            cands.append(("mesh", (world // 2, 2), "views_x_exposure_mesh"))
-        cands.append(("views", (world, 1), "views_weak_scaling"))
-        secondaries = [(m, ms, key) for m, ms, key in cands if (m, ms) != (primary_mode, primary_mesh) and ms[1] <= S]
-        for m, ms, key in secondaries:
-            wd.kick(f"secondary measurement {key}", out)
-            out[key] = brief(measure(m, ms, args.steps, args.warmup, False, graph_ok), m, ms)
-            if key == "exposure_strong_scaling":
-                out[key]["note"] = "BASELINE cfg4 in the strict sense: ONE frame, its sub-samples over all ranks; value = N / t"
-            elif key == "views_x_exposure_mesh":
-                out[key]["note"] = (f"{ms[0]} camera views (data parallel) x {ms[1]}-way exposure sharding of each view's frame - the decomposition of the "
-                                    "reference's own step (several renders behind one backward); NOT BASELINE cfg4: value = views * N / t, weak scaling")
-            else:
-                out[key]["note"] = "every rank renders its own full frame (one camera view per GPU), flat gradient all-reduce; value = world * N / t"
+        if args.full:
+            cands = [("exposure", (1, world), "exposure_strong_scaling")]
+            if world >= 4 and world % 2 == 0:
+                cands.append(("mesh", (world // 2, 2), "views_x_exposure_mesh"))
+            cands.append(("views", (world, 1), "views_weak_scaling"))
+            secondaries = [(m, ms, key) for m, ms, key in cands if (m, ms) != (primary_mode, primary_mesh) and ms[1] <= S]
+            for m, ms, key in secondaries:
+                wd.kick(f"secondary measurement {key}", out)
+                out[key] = brief(measure(m, ms, args.steps, args.warmup, False, graph_ok), m, ms)
+                if key == "exposure_strong_scaling":
+                    out[key]["note"] = "BASELINE cfg4 in the strict sense: ONE frame, its sub-samples over all ranks; value = N / t"
+                elif key == "views_x_exposure_mesh":
+                    out[key]["note"] = (f"{ms[0]} camera views (data parallel) x {ms[1]}-way exposure sharding of each view's frame - the decomposition of the "
+                                        "reference's own step (several renders behind one backward); NOT BASELINE cfg4: value = views * N / t, weak scaling")
+                else:
+                    out[key]["note"] = "every rank renders its own full frame (one camera view per GPU), flat gradient all-reduce; value = world * N / t"
         wd.done()
     if rank == 0:
-        if not dry and not args.no_cpu_baseline and world == 1:
+        if args.full and not dry and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(name, channels, full=args.cpu_baseline_full)
             except Exception as e:  # the checker must never take the bench line down
                 out["cpu_baseline"] = {"value": None, "unit": "Gaussians/s", "cores": 1, "kind": "port",
                                        "sample": f"failed: {e!r}"}
+        if keep:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
     sys.stdout.flush()
     if use_dist:

@@ -5,7 +5,7 @@ D4GS_LIB_PATH=$AB python -m pytest tests/test_gpu_rasterization.py tests/test_gp
 for c in "--config refdefault" "--config cfg2 --channels 16" "--config refdefault --scale-mul 4" "--config refdefault720"; do
  for n in base w4; do
   lib=""; [ $n = w4 ] && lib=$AB
-  D4GS_LIB_PATH=$lib python bench.py $c --no-cpu-baseline 2>/dev/null | python -c "
+  D4GS_LIB_PATH=$lib python bench.py --full $c --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels_ms_per_step']
 print('[$c] $n', '%.3f ms' % d['ms_per_step'], {n: round(1e3*t) for n,t in list(k.items())[:4]})"

@@ -23,7 +23,7 @@ if [ "$1" = build ]; then
 fi
 for n in 0 1 2 3 4; do
   lib=""; [ $n != 0 ] && lib="$PWD/scripts/ablate/libd4gs_abl$n.so"
-  D4GS_LIB_PATH=$lib python bench.py --no-cpu-baseline --steps 20 ${BENCH_ARGS} | python -c "
+  D4GS_LIB_PATH=$lib python bench.py --full --no-cpu-baseline --steps 20 ${BENCH_ARGS} | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels_ms_per_step']
 print('ABL=$n', 'bwd_q %.1f us' % (1e3*k.get('k_raster_bwd_q',0)), 'frame %.3f ms' % d['ms_per_step'])"

@@ -27,20 +27,20 @@ for c in cfg2 refdefault cfg3 cfg5; do
   PMC_MORE=1 scripts/run.sh pmc $tag $c
   python scripts/pmc_to_json.py ${tag}_$c $rnd $c   # (on the box: the bench lines below quote the counters of THIS library; redone from gpurun_out/ at home)
   scripts/run.sh prof $tag $c
-  python bench.py --config $c --no-cpu-baseline 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_$c.json
+  scripts/run.sh bench ${tag}_$c --full --config $c --no-cpu-baseline
   date
 done
-python bench.py --steps 30 --warmup 5 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_cfg2.json
+scripts/run.sh bench ${tag}_cfg2 --full --steps 30 --warmup 5
 python bench.py --gpus 1 --steps 20 --warmup 5 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_cfg2_driver_flags.json
 python bench.py 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_cfg2_default_flags.json
-python bench.py --graph --steps 30 --warmup 5 --no-cpu-baseline 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_graph_cfg2.json
-python bench.py --force-dist --graph --steps 30 --warmup 5 --no-cpu-baseline 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_graph_rccl_world1_cfg2.json
-python bench.py --sync-size-check --steps 30 --warmup 5 --no-cpu-baseline 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_cfg2_sync_size_check.json
+scripts/run.sh bench ${tag}_graph_cfg2 --full --graph --steps 30 --warmup 5 --no-cpu-baseline
+scripts/run.sh bench ${tag}_graph_rccl_world1_cfg2 --full --force-dist --graph --steps 30 --warmup 5 --no-cpu-baseline
+scripts/run.sh bench ${tag}_cfg2_sync_size_check --full --sync-size-check --steps 30 --warmup 5 --no-cpu-baseline
 date
 for sh in 2 4 8; do scripts/run.sh prof $tag share$sh --config cfg2 --share $sh; done
 scripts/run.sh prof $tag ch16 --config cfg2 --channels 16
 python scripts/shard_floor.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${tag}_shard_floor.txt
-TOPK=10 scripts/run.sh frames ${tag}_other "--config cfg3" "--config cfg5" "--config refdefault" "--config cfg2 --channels 16" "--config cfg2 --scale-mul 4" "--config refdefault720 --steps 10" "--config cfg1"
+TOPK=10 scripts/run.sh frames ${tag}_other "--full --config cfg3" "--full --config cfg5" "--full --config refdefault" "--full --config cfg2 --channels 16" "--full --config cfg2 --scale-mul 4" "--full --config refdefault720 --steps 10" "--full --config cfg1"
 mv gpurun_out/${tag}_other_frames.txt gpurun_out/${tag}_other_workloads.txt
 date
 ls gpurun_out | grep $tag | wc -l

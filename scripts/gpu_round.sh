@@ -6,7 +6,7 @@ set -x
 mkdir -p gpurun_out
 python -m pytest tests -x -q -m gpu "$@" 2>&1 | tail -15 | tee gpurun_out/${tag}_pytest_gpu.txt
 python __graft_entry__.py smoke 2>&1 | tail -2 | tee gpurun_out/${tag}_smoke.txt
-python bench.py --steps 30 --warmup 5 2>gpurun_out/${tag}_bench.err | tail -1 | tee gpurun_out/${tag}_bench.json
+scripts/run.sh bench $tag --full --steps 30 --warmup 5
 export TMPDIR=/tmp
 R=$PWD
 for cfg in cfg2 cfg5 refdefault; do

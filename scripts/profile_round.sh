@@ -7,7 +7,7 @@ tag=${1:-r02p}
 R=$PWD
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-python bench.py --steps 30 --warmup 5 2>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_cfg2.json
+scripts/run.sh bench ${tag}_cfg2 --full --steps 30 --warmup 5
 for cfg in cfg2 cfg3 cfg5 refdefault; do
   steps=10; [ $cfg = cfg5 ] && steps=5
   (cd /tmp && rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${tag}_prof_$cfg -o r -- python $R/bench.py --config $cfg --steps $steps --warmup 3 --no-cpu-baseline --no-profile --no-peaks > $R/gpurun_out/${tag}_bench_under_rocprof_$cfg.json 2>>$R/gpurun_out/${tag}_prof.err)
@@ -25,8 +25,8 @@ for sh in 4 8; do
   rm -rf gpurun_out/${tag}_prof_share$sh
 done
 python scripts/shard_floor.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${tag}_shard_floor.txt
-python bench.py --graph --steps 30 --warmup 5 --no-cpu-baseline 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_graph_cfg2.json
-python bench.py --force-dist --graph --steps 30 --warmup 5 --no-cpu-baseline 2>>gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench_graph_rccl_world1_cfg2.json
+scripts/run.sh bench ${tag}_graph_cfg2 --full --graph --steps 30 --warmup 5 --no-cpu-baseline
+scripts/run.sh bench ${tag}_graph_rccl_world1_cfg2 --full --force-dist --graph --steps 30 --warmup 5 --no-cpu-baseline
 scripts/pmc_run.sh ${tag}_fetch FETCH_SIZE > /dev/null
 scripts/pmc_run.sh ${tag}_write WRITE_SIZE > /dev/null
 scripts/pmc_run.sh ${tag}_sq SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_LDS SQ_WAIT_INST_ANY > /dev/null

@@ -4,7 +4,7 @@
 #
 #   run.sh suite  <tag> [pytest args]            GPU suite (+ parity table) + smoke()
 #   run.sh bench  <tag> [bench args]             one bench line -> <tag>_bench.json (stderr -> <tag>_bench.err)
-#   run.sh frames <tag> "<bench args>" ...       frame time + top kernels of each argument string, one line each
+#   run.sh frames <tag> "<bench args>" ...       frame time (+ top kernels: --full among the args) of each argument string, one line each
 #   run.sh prof   <tag> <cfgkey> [bench args]    rocprofv3 --kernel-trace --stats of bench.py -> <tag>_kernel_stats_<cfgkey>.csv
 #   run.sh pmc    <tag> <cfgkey> [bench args]    three rocprofv3 --pmc passes (own runs, kernel-trace only): FETCH_SIZE, WRITE_SIZE, SQ_*
 #   run.sh lanes  <tag> <cfg> [--channels D]     scripts/lane_stats.py -> <tag>_lane_stats_<cfg>.json

@@ -54,7 +54,7 @@ def test_control_stats_sink_is_validated():
         engine._check_stats({**good, "batch_size": 0}, 5)
 
 
-def test_deferred_records_queue_up_and_are_all_verified():
+def test_deferred_records_queue_up_and_are_all_verified(monkeypatch):
     """Host logic of `deferred_size_check` without a GPU: several pending records per shape, every one is read, an
     overflow in ANY of them raises (only the newest used to survive)."""
     from deblur4dgs_amd import engine
@@ -69,6 +69,9 @@ def test_deferred_records_queue_up_and_are_all_verified():
         def synchronize(self):
             self.done = True
 
+    # the records below carry ordinary host tensors: once read they would be recycled into the pool of PINNED count buffers that
+    # later renders in this process draw from, so they go to a throwaway pool
+    monkeypatch.setattr(engine, "_PINNED_FREE", [])
     key = ("unit", 1, 2, 3, 4)
     mk = lambda n, mt, live=0: torch.tensor([n, mt, 50, live], dtype=torch.int64)  # D4gsProjOut.n_isect: 50 sampled entries
     engine._DEFERRED[key] = [(mk(100, 10, 45), Ev(True), 200, 2048), (mk(900, 10, 50), Ev(True), 200, 2048),

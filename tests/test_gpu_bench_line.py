@@ -1,6 +1,6 @@
 """bench.py's contract with the driver, checked on the device: ONE JSON line on stdout with the metric of BASELINE.json, the whole-job value,
-and the `roofline` and `cpu_baseline` objects (measurement section of the task: bound / achieved / peak / unit / frac / traffic; value / unit /
-cores / kind / sample)."""
+and with --full the `roofline` and `cpu_baseline` objects (measurement section of the task: bound / achieved / peak / unit / frac / traffic;
+value / unit / cores / kind / sample); a plain run carries the headline alone and --dump-outputs writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -13,8 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_bench_line_carries_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--pre-roll", "3"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--pre-roll", "3",
+                        "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -46,3 +46,25 @@ def test_default_bench_line_carries_the_contract_fields():
     sus = d["sustained"]
     assert sus["seconds"] >= 6.0 and sus["steps"] >= 1000 and 0.5 < sus["ms_per_step"] / d["ms_per_step"] < 1.5, sus
     assert 0.9 < sus["ms_per_step"] < 2.0 and abs(sus["value"] - 300000 / (sus["ms_per_step"] * 1e-3)) <= 1e-6 * sus["value"]
+
+
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--pre-roll", "3",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("Gaussians/s fwd+bwd, 288x512, N_exposure=8") and d["unit"] == "Gaussians/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["steps"] == 5 and d["warmup"] == 2 and 0.5 < d["ms_per_step"] < 10.0
+    assert abs(d["value"] - 300000 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert not {"roofline", "cpu_baseline", "sustained", "peaks_measured", "kernels_ms_per_step", "n_isect_per_step"} & set(d)
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert {"renders", "alphas", "blended", "acc", "grad_means", "grad_colors", "grad_motion_coefs", "grad_viewmat"} <= set(got), sorted(got)
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["blended"].shape == (288, 512, 4) and got["renders"].shape == (8, 288, 512, 4) and got["grad_means"].shape == (300000, 3)
+    for k, a in got.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), k
+    assert np.abs(got["grad_means"]).sum() > 0 and 0.0 <= got["acc"].min() and got["acc"].max() <= 1.0 + 1e-5

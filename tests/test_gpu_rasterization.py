@@ -284,7 +284,7 @@ def test_long_tile_lists_all_sort_paths():
         assert (d[1:] >= d[:-1]).all(), f"tile {t} not depth sorted ({counts[t]} splats)"
 
 
-def test_forward_variants_bitwise_equal():
+def test_forward_variants_bitwise_equal(tmp_path):
     """Variant B of the forward composite (4 quadrant-waves per tile + ballot culling) must equal variant A
     (one wave per tile) bit for bit - they differ only in which provably-invisible pairs they skip."""
     import os
@@ -310,8 +310,8 @@ torch.save((rc.cpu(), ra.cpu(), info["last_ids"].cpu()), sys.argv[1])
     # is the shipped library (k_raster_fwd_r)
     var = {"D4GS_LIB_PATH": build.VARIANTS_LIB}
     assert os.path.exists(build.VARIANTS_LIB), "run __graft_entry__.build() (builds tests/libd4gs_variants.so)"
-    for env_extra, name in (({}, "/tmp/d4gs_fwd_b.pt"), ({**var, "D4GS_FWD_WAVE_PER_TILE": "1"}, "/tmp/d4gs_fwd_a.pt"),
-                            (var, "/tmp/d4gs_fwd_d.pt"), ({**var, "D4GS_FWD_QUADS": "1"}, "/tmp/d4gs_fwd_q.pt")):
+    for env_extra, name in (({}, str(tmp_path / "fwd_b.pt")), ({**var, "D4GS_FWD_WAVE_PER_TILE": "1"}, str(tmp_path / "fwd_a.pt")),
+                            (var, str(tmp_path / "fwd_d.pt")), ({**var, "D4GS_FWD_QUADS": "1"}, str(tmp_path / "fwd_q.pt"))):
         env = {k: v for k, v in os.environ.items() if not k.startswith("D4GS_FWD_")}
         env.update(env_extra)
         subprocess.check_call([sys.executable, "-c", code, name], env=env)
@@ -434,7 +434,7 @@ def test_optimistic_list_sizes_relaunch_when_the_guess_is_too_small():
     assert engine._SIZE_STATS["relaunched"] == before + 1
 
 
-def test_tile_counting_paths_agree_and_huge_tile_grids_work():
+def test_tile_counting_paths_agree_and_huge_tile_grids_work(tmp_path):
     """k_count_tiles (LDS-aggregated ranks, tile grids up to 8192 tiles) and the in-kernel global atomics it replaces
     (kept for bigger grids; forced here with D4GS_COUNT_IN_PROJECT) must give bit-identical images and gradients:
     ranks only choose the unsorted slot, the per-tile order comes from the (depth, emission index) sort."""
@@ -463,8 +463,8 @@ torch.save(outs, sys.argv[1])
     res = []
     # default: k_count_tiles + fused emission-offset scan (k_emit finishes it); then the same counting with the stand-alone
     # scan kernels; then the in-kernel atomics
-    for env_extra, name in (({}, "/tmp/d4gs_cnt_a.pt"), ({"D4GS_NO_FUSED_SCAN": "1"}, "/tmp/d4gs_cnt_c.pt"),
-                            ({"D4GS_COUNT_IN_PROJECT": "1"}, "/tmp/d4gs_cnt_b.pt")):
+    for env_extra, name in (({}, str(tmp_path / "cnt_a.pt")), ({"D4GS_NO_FUSED_SCAN": "1"}, str(tmp_path / "cnt_c.pt")),
+                            ({"D4GS_COUNT_IN_PROJECT": "1"}, str(tmp_path / "cnt_b.pt"))):
         subprocess.check_call([sys.executable, "-c", code, name], env=dict(os.environ, **env_extra))
         res.append(torch.load(name))
     for other in res[1:]:
@@ -522,7 +522,7 @@ def test_seeded_random_sweep_forward_and_backward(i, mode, D, N, W, H, scale_mul
 
 
 @pytest.mark.parametrize("D", [3, 16])
-def test_backward_variants_agree(D):
+def test_backward_variants_agree(D, tmp_path):
     """Variant B (default; for D >= 16 with the colour rows on the matrix pipe), variant A (one wave per tile) and
     variant C (all reductions on MFMA) differ only in the order of their pixel sums."""
     import os
@@ -550,8 +550,8 @@ torch.save([t[k].grad.cpu() for k in ("means", "quats", "scales", "opac", "color
 
     var = {"D4GS_LIB_PATH": build.VARIANTS_LIB}  # variants A / C exist only in the A/B build (-DD4GS_VARIANTS)
     assert os.path.exists(build.VARIANTS_LIB), "run __graft_entry__.build() (builds tests/libd4gs_variants.so)"
-    for env_extra, name in (({}, "/tmp/d4gs_bwd_b.pt"), ({**var, "D4GS_BWD_WAVE_PER_TILE": "1"}, "/tmp/d4gs_bwd_a.pt"),
-                            ({**var, "D4GS_BWD_MFMA": "1"}, "/tmp/d4gs_bwd_c.pt")):
+    for env_extra, name in (({}, str(tmp_path / "bwd_b.pt")), ({**var, "D4GS_BWD_WAVE_PER_TILE": "1"}, str(tmp_path / "bwd_a.pt")),
+                            ({**var, "D4GS_BWD_MFMA": "1"}, str(tmp_path / "bwd_c.pt"))):
         env = {k: v for k, v in os.environ.items() if not k.startswith("D4GS_BWD_")}
         env.update(env_extra)
         subprocess.check_call([sys.executable, "-c", code, name], env=env)

@@ -33,7 +33,9 @@ def test_f2_activations(golden_dir):
     t = lambda k: torch.tensor(z[k])
     np.testing.assert_array_equal(deform.act_quats(t("raw_quats")).numpy(), z["quats"])
     np.testing.assert_array_equal(deform.act_colors(t("raw_colors")).numpy(), z["colors"])
-    np.testing.assert_array_equal(deform.act_scales(t("raw_scales")).numpy(), z["scales"])
+    # the stored scales are the correctly rounded exp; float32 torch.exp is within 1 ulp of it and its last bit depends on the host
+    # CPU's vector code, so the same activation is evaluated on the exactly promoted input and rounded once
+    np.testing.assert_array_equal(deform.act_scales(t("raw_scales").double()).float().numpy(), z["scales"])
     np.testing.assert_array_equal(deform.act_opacities(t("raw_opacities")).numpy(), z["opacities"])
     np.testing.assert_array_equal(deform.act_coefs(t("raw_motion_coefs")).numpy(), z["coefs"])
 

@@ -352,7 +352,7 @@ def test_bench_n_gt_1_control_flow_runs_on_gloo(flags, expect_launch):
     "GPU"): process group, the exposure-sharded step with its blend collectives and the armed gradient all-reduce, the eager
     measurement FIRST, then (default path) the graph attempt in which rank 0 fails to capture and the cross-rank MIN agreement must
     send BOTH ranks to the eager step, max-over-ranks timing, the secondary view-sharded measurement - and ONE JSON line on stdout."""
-    d, _ = _run_bench_dry(2, flags)
+    d, _ = _run_bench_dry(2, ["--full", *flags])
     assert d["scaling"] == "strong" and "cfg4" in d["config"]["parallelism"] and d["config"]["frames_per_step"] == 1
     assert d["views_weak_scaling"]["value"] > 0 and d["views_weak_scaling"]["scaling"] == "weak"
     assert "exposure_strong_scaling" not in d  # (it IS the primary at N = 2)
@@ -364,7 +364,7 @@ def test_bench_default_at_4_ranks_is_the_strict_cfg4_with_the_mesh_as_a_secondar
     sub-samples over all ranks, strong scaling, value = N / t - so that it means the same thing at N = 2 and N = 8; the (N/2) x 2
     views x exposure mesh (exposure sub-groups from dist.new_group, world gradient all-reduce) and the views-only number ride on
     the same line as secondary objects."""
-    d, _ = _run_bench_dry(4, [])
+    d, _ = _run_bench_dry(4, ["--full"])
     tiny_n = d["config"]["gaussians"]
     assert d["scaling"] == "strong" and d["config"]["frames_per_step"] == 1 and "cfg4" in d["config"]["parallelism"]
     assert abs(d["value"] - tiny_n / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
@@ -376,10 +376,49 @@ def test_bench_default_at_4_ranks_is_the_strict_cfg4_with_the_mesh_as_a_secondar
 
 
 def test_bench_mesh_as_the_primary_line_when_asked_for():
-    d, _ = _run_bench_dry(4, ["--shard", "mesh", "--mesh", "2x2"])
+    d, _ = _run_bench_dry(4, ["--full", "--shard", "mesh", "--mesh", "2x2"])
     assert d["scaling"] == "weak" and d["config"]["frames_per_step"] == 2 and "mesh 2x2" in d["config"]["parallelism"]
     ex = d["exposure_strong_scaling"]
     assert ex["scaling"] == "strong" and ex["frames_per_step"] == 1 and "views_x_exposure_mesh" not in d
+
+
+def test_bench_plain_run_times_the_primary_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the primary measurement alone (no secondary shardings), and --dump-outputs writes the last
+    timed step's leaf gradients (rank 0) as float32 .npy files."""
+    import numpy as np
+
+    d, _ = _run_bench_dry(2, ["--dump-outputs", str(tmp_path)])
+    assert d["scaling"] == "strong" and "cfg4" in d["config"]["parallelism"]
+    assert not {"views_weak_scaling", "views_x_exposure_mesh", "exposure_strong_scaling", "cpu_baseline", "roofline"} & set(d)
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert "grad_means.npy" in files and "grad_viewmat.npy" in files, files
+    g = np.load(tmp_path / "grad_means.npy")
+    assert g.dtype == np.float32 and g.shape == (d["config"]["gaussians"], 3) and np.isfinite(g).all() and np.abs(g).sum() > 0
+
+
+def test_bench_dump_sample_is_fixed_and_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs above its size limit: every large array keeps the same seeded sample of its elements, small ones stay whole."""
+    import importlib.util
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("d4gs_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    arrays = {"big": torch.randn(300_000, 3, generator=g), "img": torch.randn(64, 96, 4, generator=g).double(),
+              "small": torch.randn(11, generator=g)}
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert sum(a.nbytes for a in got.values()) <= 1 << 20
+    assert got["big"].dtype == np.float32 and got["img"].dtype == np.float64 and 0 < got["big"].size < arrays["big"].numel()
+    assert np.array_equal(got["small"], arrays["small"].numpy())
+    for k in arrays:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))
+    assert np.isin(got["big"], arrays["big"].numpy().reshape(-1)).all()  # a sample of the array's own elements
 
 
 def test_bench_prints_the_eager_line_when_the_graph_phase_hangs():
@@ -389,7 +428,7 @@ def test_bench_prints_the_eager_line_when_the_graph_phase_hangs():
     import time
 
     t0 = time.time()
-    d, err = _run_bench_dry(2, ["--graph-timeout", "6"], env={"D4GS_BENCH_INJECT_HANG": "graph"}, timeout=240)
+    d, err = _run_bench_dry(2, ["--full", "--graph-timeout", "6"], env={"D4GS_BENCH_INJECT_HANG": "graph"}, timeout=240)
     assert time.time() - t0 < 120
     assert "WATCHDOG" in d["config"]["launch"] and "HIP-graph capture" in d["watchdog_fired_in"]
     assert d["scaling"] == "strong" and "views_weak_scaling" not in d  # nothing after the hung phase ran
