@@ -55,3 +55,24 @@ def check(case: str, tensor: str, got, ref, tol: float = 1e-4, flips: float = 0.
         return r
     assert bad <= flips, f"{case} / {tensor}: {bad:.2e} of the elements off by > {tol:g} x max|ref| (max err {r:.2e})"
     return r
+
+
+def check_columns(case: str, tensor: str, got, ref, tol: float = 1e-4):
+    """Like `check` with no allowance, but normalised per COLUMN (last axis; a 1-D tensor is one column): every element of column c
+    within tol * max|ref[..., c]|.  A per-tensor norm lets a small column hide beside a large one (an expected-depth channel of 2 - 10
+    scene units beside colours in (0, 1); a small gradient column beside a large one).  Each column is logged through `record`."""
+    g = got.detach().double().cpu() if torch.is_tensor(got) else torch.as_tensor(np.asarray(got, np.float64))
+    r = ref.detach().double().cpu() if torch.is_tensor(ref) else torch.as_tensor(np.asarray(ref, np.float64))
+    assert g.shape == r.shape, (case, tensor, tuple(g.shape), tuple(r.shape))
+    ncol = r.shape[-1] if r.dim() > 1 else 1
+    g, r = g.reshape(-1, ncol), r.reshape(-1, ncol)
+    worst = []
+    for c in range(ncol):
+        err, _ = record(case, f"{tensor}[..., {c}]" if ncol > 1 else tensor, g[:, c], r[:, c])
+        PARITY_LOG[-1].update(asserted_tol=tol, asserted_flips=0.0, norm="per column")
+        worst.append(err)
+    if os.environ.get("D4GS_PARITY_MEASURE"):
+        return max(worst)
+    bad = [(c, f"{e:.2e}") for c, e in enumerate(worst) if not e <= tol]
+    assert not bad, f"{case} / {tensor}: columns off by > {tol:g} x max|ref[..., c]|: {bad}"
+    return max(worst)
