@@ -107,7 +107,7 @@ EXPORTS = (
     "d4gs_points_fwd", "d4gs_points_bwd", "d4gs_poses_fwd", "d4gs_poses_bwd", "d4gs_forward", "d4gs_backward", "d4gs_forward_cpu", "d4gs_backward_cpu", "d4gs_frame_workspace_bytes", "d4gs_frame_workspace_bytes_fwd", "d4gs_blend_shard_partial_fwd", "d4gs_blend_shard_finish_fwd",
     "d4gs_blend_shard_winner", "d4gs_blend_shard_bwd", "d4gs_control_stats", "d4gs_control_plan", "d4gs_gather_rows", "d4gs_camera_path_fwd", "d4gs_camera_path_bwd",
     "d4gs_pose_encode", "d4gs_pose_encode_bwd", "d4gs_move_model_fwd", "d4gs_move_model_bwd",
-    "d4gs_photometric_blocks", "d4gs_photometric_fwd", "d4gs_photometric_bwd", "d4gs_query_sizes", "d4gs_profile_enable", "d4gs_profile_collect", "d4gs_measure_peaks",
+    "d4gs_photometric_blocks", "d4gs_photometric_fwd", "d4gs_photometric_bwd", "d4gs_sh_partials_elems", "d4gs_sh_fwd", "d4gs_sh_bwd", "d4gs_query_sizes", "d4gs_profile_enable", "d4gs_profile_collect", "d4gs_measure_peaks",
 )
 
 _lib = None
@@ -174,6 +174,10 @@ def lib() -> C.CDLL:
                                            vp, vp]
         L.d4gs_photometric_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                            C.c_float, vp, vp]
+        L.d4gs_sh_partials_elems.argtypes = [C.c_int64]
+        L.d4gs_sh_partials_elems.restype = C.c_int64
+        L.d4gs_sh_fwd.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp]
+        L.d4gs_sh_bwd.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.d4gs_blend_fwd.argtypes = [C.c_int32, C.c_int64, C.c_int32, P(C.c_int32), vp, vp, vp, vp, vp]
         L.d4gs_blend_bwd.argtypes = [C.c_int32, C.c_int64, C.c_int32, P(C.c_int32), vp, vp, vp, vp, vp, vp, vp]
         if L.d4gs_version() != VERSION:

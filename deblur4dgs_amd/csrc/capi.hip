@@ -46,6 +46,11 @@ int d4gs_photometric_fwd_impl(const float *, const float *, const float *, int32
 int d4gs_photometric_bwd_impl(const float *, const float *, const float *, const float *, const float *, int32_t, int32_t,
                               int32_t, float, float, float *, hipStream_t);
 
+int d4gs_sh_fwd_impl(int64_t, int32_t, int32_t, const float *, const float *, const float *, const uint8_t *, int32_t, float *,
+                     hipStream_t);
+int d4gs_sh_bwd_impl(int64_t, int32_t, int32_t, const float *, const float *, const float *, const uint8_t *, int32_t,
+                     const float *, float *, float *, float *, float *, hipStream_t);
+
 static thread_local char g_err[512] = "";
 
 // ---- per-kernel event profiler -------------------------------------------------------------------------
@@ -553,6 +558,48 @@ int d4gs_photometric_bwd(const float *pred, const float *gt, const float *mask, 
     return D4GS_EINVAL;
   }
   return d4gs_photometric_bwd_impl(pred, gt, mask, maps, v_loss, B, H, W, w_l1, w_ssim, v_pred, (hipStream_t)stream);
+}
+
+static int sh_check_dims(const char *what, int64_t N, int32_t K, int32_t degree) {
+  if (N < 0) {
+    d4gs_set_error("%s: N < 0 (N=%lld)", what, (long long)N);
+    return D4GS_EINVAL;
+  }
+  if (degree < 0 || degree > 4) {
+    d4gs_set_error("%s: degree %d outside 0..4", what, degree);
+    return D4GS_EINVAL;
+  }
+  if (K < (degree + 1) * (degree + 1)) {
+    d4gs_set_error("%s: K=%d < (degree+1)^2=%d coefficients", what, K, (degree + 1) * (degree + 1));
+    return D4GS_EINVAL;
+  }
+  return D4GS_OK;
+}
+
+int d4gs_sh_fwd(int64_t N, int32_t K, int32_t degree, const float *p, const float *origin, const float *coeffs,
+                const uint8_t *mask, int32_t clamp, float *rgb, void *stream) {
+  if (int rc = sh_check_dims("sh_fwd", N, K, degree)) return rc;
+  if (!p || !coeffs || !rgb) {
+    d4gs_set_error("sh_fwd: NULL buffer (p, coeffs and rgb are required)");
+    return D4GS_EINVAL;
+  }
+  return d4gs_sh_fwd_impl(N, K, degree, p, origin, coeffs, mask, clamp, rgb, (hipStream_t)stream);
+}
+
+int d4gs_sh_bwd(int64_t N, int32_t K, int32_t degree, const float *p, const float *origin, const float *coeffs,
+                const uint8_t *mask, int32_t clamp, const float *v_rgb, float *v_coeffs, float *v_p, float *v_origin,
+                float *partials, void *stream) {
+  if (int rc = sh_check_dims("sh_bwd", N, K, degree)) return rc;
+  if (!p || !coeffs || !v_rgb) {
+    d4gs_set_error("sh_bwd: NULL buffer (p, coeffs and v_rgb are required)");
+    return D4GS_EINVAL;
+  }
+  if (v_origin && (!origin || !partials)) {
+    d4gs_set_error("sh_bwd: NULL buffer (v_origin needs origin and partials)");
+    return D4GS_EINVAL;
+  }
+  return d4gs_sh_bwd_impl(N, K, degree, p, origin, coeffs, mask, clamp, v_rgb, v_coeffs, v_p, v_origin, partials,
+                          (hipStream_t)stream);
 }
 
 }  // extern "C"

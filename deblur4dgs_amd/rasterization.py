@@ -5,6 +5,9 @@ Same argument names / meaning / return triple as gsplat 1.1.1:
     render_colors [C,H,W,D(+1)], render_alphas [C,H,W,1], info
 `info["means2d"]` is an autograd intermediate ([C,N,2], pixel units) on which callers may `.retain_grad()`;
 `info["radii"]` is int32 [C,N], > 0 <=> visible.
+
+`sh_degree=d` (0..4): `colors` are SH coefficients [N,K,3] or [1,N,K,3] with K >= (d+1)^2, evaluated per Gaussian towards
+the camera centre as gsplat does (`sh.sh_colors`), then composited like [N,3] colours.
 """
 from __future__ import annotations
 
@@ -13,6 +16,7 @@ import torch
 from . import _lib as L
 from . import engine
 from .engine import RenderCfg, render_instances
+from .sh import sh_colors, spherical_harmonics  # noqa: F401  (re-exported: gsplat.rendering's companion)
 
 _MODES = {"RGB": L.DEPTH_NONE, "RGB+ED": L.DEPTH_ED, "RGB+D": L.DEPTH_D}
 
@@ -22,7 +26,7 @@ def rasterization(
     quats: torch.Tensor,  # [N,4] wxyz
     scales: torch.Tensor,  # [N,3]
     opacities: torch.Tensor,  # [N]
-    colors: torch.Tensor,  # [N,D]
+    colors: torch.Tensor,  # [N,D], or SH coefficients [N,K,3] / [1,N,K,3] with sh_degree
     viewmats: torch.Tensor,  # [C,4,4]
     Ks: torch.Tensor,  # [C,3,3]
     width: int,
@@ -48,12 +52,28 @@ def rasterization(
 ):
     if viewmats.shape[0] != 1 or Ks.shape[0] != 1:
         raise ValueError("C must be 1 (the reference asserts it: flow3d/scene_model.py:249)")
-    if sh_degree is not None or packed or absgrad or sparse_grad or rasterize_mode != "classic" or tile_size != 16:
-        raise NotImplementedError("only the configuration the reference uses is implemented: "
-                                  "sh_degree=None, packed=False, classic, tile_size=16")
+    if packed or absgrad or sparse_grad or rasterize_mode != "classic" or tile_size != 16:
+        raise NotImplementedError("only packed=False, absgrad=False, sparse_grad=False, rasterize_mode='classic' and "
+                                  "tile_size=16 are implemented")
     if render_mode not in _MODES:
         raise ValueError(f"render_mode {render_mode!r} not supported (RGB, RGB+ED, RGB+D)")
     N = means.shape[0]
+    if sh_degree is not None:
+        d = int(sh_degree)
+        if not 0 <= d <= 4:
+            raise ValueError(f"sh_degree must be in 0..4, got {sh_degree}")
+        if colors.dim() == 4:
+            if colors.shape[0] != 1:
+                raise ValueError(f"SH coefficients [C,N,K,3] need C == 1, got {tuple(colors.shape)}")
+            colors = colors[0]
+        if colors.dim() != 3 or colors.shape[0] != N or colors.shape[-1] != 3:
+            raise ValueError(f"with sh_degree, colors must be [N,K,3] or [1,N,K,3] (N={N}), got {tuple(colors.shape)}")
+        if colors.shape[1] < (d + 1) ** 2:
+            raise ValueError(f"sh_degree {d} needs K >= {(d + 1) ** 2} coefficients, got K = {colors.shape[1]}")
+        # gsplat masks the evaluation with radii > 0.  Unmasked here: a Gaussian that mask would drop is in no tile list,
+        # so its colour is never read and its v_rgb is 0 - outputs and gradients equal the masked evaluation's, and the
+        # colours need not wait for the projection.
+        colors = sh_colors(means, viewmats[0], colors, d)
     assert quats.shape == (N, 4) and scales.shape == (N, 3) and opacities.shape == (N,) and colors.shape[0] == N
     bg = None if backgrounds is None else backgrounds[0]
     # any channel count: the engine composites it in chunks of <= 16 channels over one projection / one set of sorted

@@ -399,6 +399,27 @@ D4GS_API int d4gs_photometric_bwd(const float *pred, const float *gt, const floa
                          int32_t B, int32_t H, int32_t W, int32_t C, float w_l1, float w_ssim, float *v_pred,
                          void *stream);
 
+/* Spherical-harmonic colours (seam S1's `sh_degree`, gsplat 1.1.1 `spherical_harmonics` + its `rasterization` epilogue).
+ * Per Gaussian n, with dir = p[n] - origin (dir = p[n] when origin is NULL) and d = dir / |dir|:
+ *   raw[c] = sum_{k < (degree+1)^2} Y_k(d) coeffs[n,k,c],   rgb[n,c] = clamp ? max(raw[c] + 0.5, 0) : raw[c].
+ * Y_k is the real SH basis (degree 0..4) in the Inria / gsplat order and sign convention, e.g. Y_0 = 0.2820948,
+ * Y_1 = -0.4886025 y, Y_2 = 0.4886025 z, Y_3 = -0.4886025 x, ... (the full table: csrc/sh.hip).
+ * p [N,3], origin [3] or NULL, coeffs [N,K,3] with K >= (degree+1)^2 (coefficients k >= (degree+1)^2 are ignored),
+ * mask [N] (uint8 / bool, 0 = masked) or NULL, rgb [N,3].
+ * A masked Gaussian, and one with |dir| == 0 (on the camera centre: the near plane culls it), has raw = 0 and zero
+ * gradients (gsplat would produce NaN for the latter).
+ * Backward, from v_rgb [N,3] (the clamp's pass-through, raw + 0.5 >= 0, is recomputed from coeffs):
+ *   v_coeffs [N,K,3] or NULL: Y_k(d) v_rgb[n,:] below (degree+1)^2, exact zeros above and for masked Gaussians;
+ *   v_p [N,3] or NULL: dL/dp;  v_origin [3] or NULL: -sum_n dL/dp[n], summed in a fixed order (bitwise reproducible)
+ *   through partials [d4gs_sh_partials_elems(N)] scratch; needs origin.
+ * N == 0 launches nothing.  D4GS_EINVAL for N < 0, degree outside 0..4, K < (degree+1)^2 or a NULL required buffer. */
+D4GS_API int64_t d4gs_sh_partials_elems(int64_t N);
+D4GS_API int d4gs_sh_fwd(int64_t N, int32_t K, int32_t degree, const float *p, const float *origin, const float *coeffs,
+                         const uint8_t *mask, int32_t clamp, float *rgb, void *stream);
+D4GS_API int d4gs_sh_bwd(int64_t N, int32_t K, int32_t degree, const float *p, const float *origin, const float *coeffs,
+                         const uint8_t *mask, int32_t clamp, const float *v_rgb, float *v_coeffs, float *v_p,
+                         float *v_origin, float *partials, void *stream);
+
 /* a9 exposure blend (scene_model.py:386-397): out = mean_S; policy[c] 1 -> max over {raw_0..raw_{S-2}, mean},
  * 2 -> min over the same set (the reference's in-place quirk); acc = mean_S alphas. */
 D4GS_API int d4gs_blend_fwd(int32_t S, int64_t n_pixels, int32_t C, const int32_t *policy /* [host] [C] */,
