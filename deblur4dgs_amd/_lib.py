@@ -46,7 +46,8 @@ class Raster(C.Structure):
 class RasterGrads(C.Structure):
     _fields_ = [(n, F) for n in ("v_render_colors", "v_render_alphas", "isect_grad", "isect_live", "v_means2d", "v_conics",
                                  "v_depths", "v_opac_act", "v_ctab", "stats_grad_norm_acc", "stats_vis_count",
-                                 "stats_max_radii")] + [("stats_batch_size", C.c_int32), ("stats_update_max_radii", C.c_int32), ("row_mode", C.c_int32)]
+                                 "stats_max_radii")] + [("stats_batch_size", C.c_int32), ("stats_update_max_radii", C.c_int32), ("row_mode", C.c_int32),
+                                                        ("v_means2d_abs", F), ("stats_absgrad", C.c_int32)]
 
 
 class Sizes(C.Structure):
@@ -87,14 +88,15 @@ class FrameIO(C.Structure):
 class FrameGrads(C.Structure):
     _fields_ = [(n, F) for n in ("v_blended", "v_acc", "v_renders", "v_alphas", "v_means2d", "stats_grad_norm_acc",
                                  "stats_vis_count", "stats_max_radii")] + \
-               [("stats_batch_size", C.c_int32), ("stats_update_max_radii", C.c_int32), ("row_mode", C.c_int32)]
+               [("stats_batch_size", C.c_int32), ("stats_update_max_radii", C.c_int32), ("row_mode", C.c_int32),
+                ("v_means2d_abs", F), ("stats_absgrad", C.c_int32)]
 
 
 class Poses(C.Structure):
     _fields_ = [("means", F), ("quats", F), ("transforms", F), ("g_major", C.c_int32)]
 
 
-RAW_PARAMS, RAW_COLORS, EXACT_CULL, LAZY_SORT, EXACT_TILES = 1, 2, 4, 8, 16
+RAW_PARAMS, RAW_COLORS, EXACT_CULL, LAZY_SORT, EXACT_TILES, ABSGRAD = 1, 2, 4, 8, 16, 32
 DEPTH_NONE, DEPTH_ED, DEPTH_D = 0, 1, 2
 ROWS_AUTO, ROWS_DENSE, ROWS_SPARSE = 0, 1, 2
 TILE = 16

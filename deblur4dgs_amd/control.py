@@ -40,9 +40,11 @@ def accumulate_control_stats(running_stats: dict, xys_grad: torch.Tensor, radii:
             "d4gs_control_stats")
 
 
-def accumulate_from_model(running_stats: dict, model, batch_size: int, update_max_radii: bool = False):
-    """Same inputs the reference reads: `model._current_xys[i].grad`, `model._current_radii[i]`, `_current_img_wh`."""
-    xys = torch.cat([x.grad for x in model._current_xys], 0)
+def accumulate_from_model(running_stats: dict, model, batch_size: int, update_max_radii: bool = False, absgrad: bool = False):
+    """Same inputs the reference reads: `model._current_xys[i].grad`, `model._current_radii[i]`, `_current_img_wh`.
+    absgrad=True: `_current_xys[i].absgrad` instead (renders with `attach_control_stats(..., absgrad=True)`; the unfused
+    mirror of its statistics)."""
+    xys = torch.cat([x.absgrad if absgrad else x.grad for x in model._current_xys], 0)
     rad = torch.cat(list(model._current_radii), 0)
     accumulate_control_stats(running_stats, xys, rad, model._current_img_wh, batch_size, update_max_radii)
 

@@ -101,6 +101,20 @@ int d4gs_check_launch(const char *what) {
   return D4GS_OK;
 }
 
+// D4GS_ABSGRAD and its buffers come together: the flag needs v_means2d_abs, v_means2d_abs and stats_absgrad need the flag
+int d4gs_check_absgrad(const char *who, const D4gsDims *d, const float *v_means2d_abs, int32_t stats_absgrad) {
+  const bool flag = (d->flags & D4GS_ABSGRAD) != 0;
+  if (flag && !v_means2d_abs) {
+    d4gs_set_error("%s: D4GS_ABSGRAD needs v_means2d_abs", who);
+    return D4GS_EINVAL;
+  }
+  if (!flag && (v_means2d_abs || stats_absgrad)) {
+    d4gs_set_error("%s: v_means2d_abs / stats_absgrad given without D4GS_ABSGRAD in dims->flags", who);
+    return D4GS_EINVAL;
+  }
+  return D4GS_OK;
+}
+
 static int check_dims(const D4gsDims *d) {
   if (!d) {
     d4gs_set_error("dims is NULL");
@@ -174,7 +188,7 @@ int d4gs_query_sizes(const D4gsDims *d, D4gsSizes *z) {
   z->tile_counts = 2 * S * tw * th, z->tile_offsets = S * tw * th + 1, z->n_isect = 4;
   z->scan_ws = (int64_t)d4gs_scan_ws_elems(SN);
   z->render_colors = S * H * W * nch, z->render_alphas = S * H * W, z->last_ids = S * H * W, z->final_T = S * H * W;
-  z->isect_grad_row = 6 + nch;
+  z->isect_grad_row = 6 + nch + ((d->flags & D4GS_ABSGRAD) ? 2 : 0);  // absgrad: |dL/dx|, |dL/dy| behind the channels
   z->bwd_partials = (int64_t)d4gs_bwd_partials_elems(d);
   z->seg_state = d4gs_seg_state_elems(d);
   z->lazy_ws = d4gs_lazy_ws_elems((int)S, (int)(tw * th));
@@ -296,6 +310,7 @@ int d4gs_raster_bwd(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIse
     d4gs_set_error("d4gs_raster_bwd: fused statistics need vis_count, max_radii, radii and a positive batch size");
     return D4GS_EINVAL;
   }
+  if ((rc = d4gs_check_absgrad("d4gs_raster_bwd", dims, g->v_means2d_abs, g->stats_absgrad))) return rc;
   return d4gs_raster_bwd_impl(dims, proj, isect, r, g, nullptr, (hipStream_t)stream);
 }
 

@@ -16,6 +16,7 @@ int d4gs_project_bwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsProjOu
 int d4gs_blend_fwd_impl(int32_t, int64_t, int32_t, const int32_t *, const float *, const float *, float *, float *, int8_t *,
                         hipStream_t, const int64_t *n_isect = nullptr, int64_t *counts_pinned = nullptr);
 int d4gs_copy_counts_impl(const int64_t *n_isect, int64_t *host_pinned, hipStream_t stream);
+int d4gs_check_absgrad(const char *who, const D4gsDims *d, const float *v_means2d_abs, int32_t stats_absgrad);
 int d4gs_blend_bwd_add_impl(int32_t, int64_t, int32_t, const int32_t *, const float *, const float *, const float *,
                             const float *, float *, float *, const float *, const float *, hipStream_t, const int8_t *win = nullptr);
 
@@ -162,6 +163,7 @@ int d4gs_backward(const D4gsDims *dims, const D4gsProjIn *in, const D4gsFrameIO 
                    "unblended one v_renders [+ v_alphas])");
     return D4GS_EINVAL;
   }
+  if ((rc = d4gs_check_absgrad("d4gs_backward", dims, g->v_means2d_abs, g->stats_absgrad))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   FrameBufs b = carve(dims, isect_capacity, ws);
   bind_io(b, io, isect_capacity, max_tile_hint);
@@ -196,6 +198,7 @@ int d4gs_backward(const D4gsDims *dims, const D4gsProjIn *in, const D4gsFrameIO 
   rg.stats_grad_norm_acc = g->stats_grad_norm_acc, rg.stats_vis_count = g->stats_vis_count;
   rg.stats_max_radii = g->stats_max_radii, rg.stats_batch_size = g->stats_batch_size;
   rg.stats_update_max_radii = g->stats_update_max_radii, rg.row_mode = g->row_mode;
+  rg.v_means2d_abs = g->v_means2d_abs, rg.stats_absgrad = g->stats_absgrad;
   if (rg.stats_grad_norm_acc && (!rg.stats_vis_count || !rg.stats_max_radii || rg.stats_batch_size <= 0)) {
     d4gs_set_error("d4gs_backward: fused statistics need vis_count, max_radii and a positive batch size");
     return D4GS_EINVAL;

@@ -101,13 +101,19 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // transmittance the forward stored at that boundary and the suffix dot product <v_out, C_final - C_boundary> (what `bsum` has
 // accumulated by then).  Rows are still written once, by the segment that owns them: no atomics, run-to-run deterministic;
 // against the unsegmented replay the gradients differ by the fp32 rounding of that hand-off.
-template <int D, bool DEPTH, bool SEG = false>
+// ABS (absgrad, D4GS_ABSGRAD): every replayed (pixel, splat) pair also yields the pixel's own dL/dx, dL/dy - the conic map that o0 / o1
+// apply to the wave sums, applied per pixel - and their absolute values are reduced over the wave in a wave_sum_store<2> call of
+// their own (the row[RV] call, and so the existing rows' summation trees, stay as they are).  isect_grad rows grow by two floats,
+// [6 moments | NCH channels | |dL/dx| | |dL/dy|]; in the slab the two sums sit behind everything else (column AB, AB + 1; AB + 2
+// takes wave_sum_store's spare writes).
+template <int D, bool DEPTH, bool SEG = false, bool ABS = false>
 __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
 #pragma clang fp contract(off)
   constexpr int NCH = D + (DEPTH ? 1 : 0);
   constexpr int DP = (D + 3) & ~3;
   constexpr int DV = DP / 4;
   constexpr int R = 6 + NCH;
+  constexpr int RW = R + (ABS ? 2 : 0);  // floats per isect_grad row
   // >= 16 channels (the reference's 17-channel training renders): 4 waves per SIMD instead of 3 (round 4).  The kernel's time goes
   // with 1 / occupancy and its workgroup needed 50.4 KB of LDS and 140 VGPRs; an 8-hit `fac` tile (the MFMA's other 8 columns idle:
   // twice the matrix instructions per hit), the staged boxes as 4 x f16 and an even slab stride bring it to 40.6 KB / 113 VGPRs
@@ -116,7 +122,6 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
 #define D4GS_BWD16_4W 1
 #endif
   constexpr bool W4 = D4GS_BWD16_4W && D >= 16;
-  constexpr int RP = W4 ? (R + 1) : ((R + 1) | 1);
   constexpr int NB = 64;  // splats per batch
   // With >= 16 colour channels the colour gradients V_c[j] = sum_p vo[c][p] * fac[p][j] of channels 0..15 leave the
   // VALU: they are a [16 ch x 64 px] x [64 px x 16 hits] product, A = this quadrant's image gradient (fixed for the
@@ -125,6 +130,8 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
   constexpr int MC = D >= 16 ? 16 : 0;        // channels reduced on the matrix pipe
   constexpr int RV = R - MC;                  // rows reduced on the VALU
   constexpr int CB = MC ? RV + 1 : 6;         // slab column of channel 0 (VALU rows, their pad slot, then colours)
+  constexpr int AB = MC ? CB + MC : RV + 1;   // ABS: slab column of the two absolute-value sums
+  constexpr int RP = ABS ? (W4 ? AB + 3 : ((AB + 3) | 1)) : W4 ? (R + 1) : ((R + 1) | 1);
   constexpr int MH = W4 ? 8 : 16;             // hits parked per flush (the MFMA's 16 columns: the upper 8 idle when MH = 8)
   constexpr int FS = MH + 1;                  // fac tile [64 px][MH hits], row stride (bank-conflict padding)
   static_assert(!MC || CB + MC <= RP, "slab row too short");
@@ -287,9 +294,9 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
   // large-footprint scenes that is most rows and zero-filling them costs more than the replay itself.
   if (!a.sparse)
     for (int idx = hi + 1 + tid; idx < end; idx += 256) {
-      float *dst = a.isect_grad + (size_t)a.sorted_emit[idx] * R;
+      float *dst = a.isect_grad + (size_t)a.sorted_emit[idx] * RW;
 #pragma unroll
-      for (int r = 0; r < R; r++) dst[r] = 0.f;
+      for (int r = 0; r < RW; r++) dst[r] = 0.f;
     }
 
   // va - (the suffix sum of fac * d over the contributors behind the current one), kept as ONE running value: a multiply-add per hit
@@ -416,6 +423,12 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
         row[4] = vsy * dy;
         row[5] = vs;
         wave_sum_store(row, sgrad, (wvs * NB + j) * RP, lane);
+        if constexpr (ABS) {  // this pixel's dL/dx, dL/dy (o0 / o1 below, on one pixel's terms), then |.|
+          float ab[2];
+          ab[0] = fabsf((2.f * g1.x * vsx + g1.y * vsy) * LN2);
+          ab[1] = fabsf((g1.y * vsx + 2.f * g1.z * vsy) * LN2);
+          wave_sum_store(ab, sgrad, (wvs * NB + j) * RP + AB, lane);
+        }
         if constexpr (MC > 0) {
           if (++nh == MH) {
             flush(MH);
@@ -441,9 +454,15 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
         }
       }
       const float4 g1 = sg1[tid];  // conic * log2(e), 1 / opacity
-      float *dst = a.isect_grad + (size_t)emit * R;
+      float *dst = a.isect_grad + (size_t)emit * RW;
       const float o0 = (2.f * g1.x * sum[0] + g1.y * sum[1]) * LN2;  // dL/dx = a Sum(vs dx) + b Sum(vs dy); g1 = (a/2, b, c/2) log2e
       const float o1 = (g1.y * sum[0] + 2.f * g1.z * sum[1]) * LN2;
+      float abs_x = 0.f, abs_y = 0.f;
+      if constexpr (ABS) {
+        abs_x = (sgrad[tid * RP + AB] + sgrad[(NB + tid) * RP + AB]) + (sgrad[(2 * NB + tid) * RP + AB] + sgrad[(3 * NB + tid) * RP + AB]);
+        abs_y = (sgrad[tid * RP + AB + 1] + sgrad[(NB + tid) * RP + AB + 1]) +
+                (sgrad[(2 * NB + tid) * RP + AB + 1] + sgrad[(3 * NB + tid) * RP + AB + 1]);
+      }
       if constexpr (R % 2 == 0 && R <= 12) {  // even rows start on 8-byte boundaries: half as many stores (narrow rows only: registers)
         float2 *d2 = reinterpret_cast<float2 *>(dst);
         d2[0] = make_float2(o0, o1);
@@ -451,6 +470,7 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
         d2[2] = make_float2(0.5f * sum[4], -sum[5] * g1.w);
 #pragma unroll
         for (int c = 0; c < NCH; c += 2) d2[3 + c / 2] = make_float2(sum[6 + c], sum[7 + c]);
+        if constexpr (ABS) d2[R / 2] = make_float2(abs_x, abs_y);
       } else {
         dst[0] = o0;
         dst[1] = o1;
@@ -460,6 +480,7 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
         dst[5] = -sum[5] * g1.w;
 #pragma unroll
         for (int c = 0; c < NCH; c++) dst[6 + c] = sum[6 + c];
+        if constexpr (ABS) dst[R] = abs_x, dst[R + 1] = abs_y;
       }
       if (a.sparse) a.live[emit] = 1;
     }
@@ -468,26 +489,27 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
 }
 // Two entry points over one body: the narrow instantiations (D <= 5) are asked for 8 waves per SIMD (the hint changes the
 // scheduler's register budget); the wide ones keep the compiler's default - the hint cannot be met there and only perturbs them.
-template <int D, bool DEPTH>
+// (ABS: the absgrad instantiations, same hints)
+template <int D, bool DEPTH, bool ABS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_raster_bwd_q8(const RasterBwdArgs a) {
-  raster_bwd_q_body<D, DEPTH>(a);
+  raster_bwd_q_body<D, DEPTH, false, ABS>(a);
 }
-template <int D, bool DEPTH>
+template <int D, bool DEPTH, bool ABS = false>
 __global__ void __launch_bounds__(256)
 #if defined(D4GS_BWD16_4W) && D4GS_BWD16_4W
 __attribute__((amdgpu_waves_per_eu(D >= 16 ? 4 : 1, D >= 16 ? 4 : 10)))
 #endif
 k_raster_bwd_q(const RasterBwdArgs a) {
-  raster_bwd_q_body<D, DEPTH>(a);
+  raster_bwd_q_body<D, DEPTH, false, ABS>(a);
 }
 // the same two over (tile, depth segment) workgroups
-template <int D, bool DEPTH>
+template <int D, bool DEPTH, bool ABS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_raster_bwd_qs8(const RasterBwdArgs a) {
-  raster_bwd_q_body<D, DEPTH, true>(a);
+  raster_bwd_q_body<D, DEPTH, true, ABS>(a);
 }
-template <int D, bool DEPTH>
+template <int D, bool DEPTH, bool ABS = false>
 __global__ void __launch_bounds__(256) k_raster_bwd_qs(const RasterBwdArgs a) {
-  raster_bwd_q_body<D, DEPTH, true>(a);
+  raster_bwd_q_body<D, DEPTH, true, ABS>(a);
 }
 
 #ifdef D4GS_VARIANTS
@@ -514,6 +536,9 @@ struct GatherArgs {
   float *stats_mr;
   float sx, sy, max_wh;
   int update_mr;
+  // ABS instantiations: [S,N,2] sums of the rows' two absolute-value columns; stats_abs: the statistics use them instead of v_means2d
+  float *v_means2d_abs;
+  int stats_abs;
 };
 
 // The rows of the 64 instances a wave owns (same sub-sample, consecutive Gaussians) form ONE contiguous span of
@@ -533,11 +558,12 @@ struct GatherArgs {
 #endif
 constexpr int gather_rows(int D, bool sparse) { return D >= 8 ? 96 : sparse ? D4GS_GATHER_ROWS_SPARSE : 192; }
 constexpr int GATHER_SC = 1024;                         // rows per super-chunk of the cooperative sparse path (16 flags per lane)
-template <int D, bool DEPTH, bool SPARSE, int SLOTS /* waves per block: 4, or S when the call has fewer sub-samples */>
+// ABS: rows of 6 + NCH + 2 floats (raster_bwd_q_body); the last two columns are summed, in the same order, into v_means2d_abs
+template <int D, bool DEPTH, bool SPARSE, int SLOTS /* waves per block: 4, or S when the call has fewer sub-samples */, bool ABS = false>
 __global__ void __launch_bounds__(SLOTS * 64) k_gather(const GatherArgs a) {
   constexpr int NCH = D + (DEPTH ? 1 : 0);
   constexpr int DP = (D + 3) & ~3;
-  constexpr int R = 6 + NCH;
+  constexpr int R = 6 + NCH + (ABS ? 2 : 0);
   constexpr int GATHER_ROWS = gather_rows(D, SPARSE);
   __shared__ __attribute__((aligned(16))) float stage[SLOTS * GATHER_ROWS * R];
   __shared__ uint32_t slive[SPARSE ? SLOTS * 64 : 1];  // flags of a chunk as 4-byte words (<= GATHER_ROWS + 3 bytes)
@@ -752,13 +778,15 @@ __global__ void __launch_bounds__(SLOTS * 64) k_gather(const GatherArgs a) {
       a.v_conics[i * 3 + 1] = acc[3];
       a.v_conics[i * 3 + 2] = acc[4];
       a.v_depths[i] = DEPTH ? acc[6 + (DEPTH ? D : 0)] : 0.f;
+      if constexpr (ABS) *reinterpret_cast<float2 *>(a.v_means2d_abs + i * 2) = make_float2(acc[R - 2], acc[R - 1]);
     }
     }  // s < S
     // hand-off: (v_opacity, v_colour[D], v_x, v_y) of this slot's sub-sample, element-major in the slot's (now idle) stage slice
     mine[lane] = acc[5];
 #pragma unroll
     for (int c = 0; c < D; c++) mine[(1 + c) * 64 + lane] = acc[6 + c];
-    mine[(1 + D) * 64 + lane] = acc[0], mine[(2 + D) * 64 + lane] = acc[1];
+    const bool st_abs = ABS && a.stats_abs;  // (grid-uniform) the statistics take absgrad
+    mine[(1 + D) * 64 + lane] = st_abs ? acc[R - 2] : acc[0], mine[(2 + D) * 64 + lane] = st_abs ? acc[R - 1] : acc[1];
     __syncthreads();
     if (wv == 0) {
       for (int w = 0; w < SLOTS && s0 + w < a.S; w++) {  // ascending s: the order of the single-wave loop
@@ -802,7 +830,7 @@ static bool choose_sparse(int row_mode, int64_t n_isect, int64_t n_inst, bool la
   return n_isect >= 6 * (n_inst > 0 ? n_inst : 1);
 }
 
-template <int D, bool DEPTH>
+template <int D, bool DEPTH, bool ABS>
 int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, int64_t n_isect, int row_mode, bool lazy, hipStream_t stream) {
   const int n_tiles = a.S * a.tw * a.th;
   const int blocks = ((n_tiles + 7) / 8) * 8;
@@ -811,7 +839,7 @@ int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, int64_t n_isect, int row_mode, 
 #ifdef D4GS_VARIANTS  // the A/B build only (tests/libd4gs_variants.so): environment-selected reference variants, dense rows
   static const bool wave_per_tile = getenv("D4GS_BWD_WAVE_PER_TILE") != nullptr;  // variant A
   static const bool use_mfma = getenv("D4GS_BWD_MFMA") != nullptr;                // variant C
-  if (wave_per_tile || use_mfma) {
+  if (!ABS && (wave_per_tile || use_mfma)) {
     constexpr int R = 6 + D + (DEPTH ? 1 : 0);
     a.sparse = ga.sparse = 0;
     if (wave_per_tile) {  // variant A relies on a zeroed buffer
@@ -838,16 +866,16 @@ int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, int64_t n_isect, int row_mode, 
     }
     if (n_isect > 0 && a.seg_state) {
       const int sblocks = ((n_tiles + 7) / 8) * 8 * D4GS_SEG_MAX;
-      if constexpr (D <= 5) D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_qs8<D, DEPTH>), dim3(sblocks), dim3(256), 0, stream, a);
-      else D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_qs<D, DEPTH>), dim3(sblocks), dim3(256), 0, stream, a);
+      if constexpr (D <= 5) D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_qs8<D, DEPTH, ABS>), dim3(sblocks), dim3(256), 0, stream, a);
+      else D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_qs<D, DEPTH, ABS>), dim3(sblocks), dim3(256), 0, stream, a);
     } else if (n_isect > 0) {
       static const int q_env = getenv("D4GS_BWD_Q") ? atoi(getenv("D4GS_BWD_Q")) : 0;  // A/B hook: workgroups per CU
       if constexpr (D <= 5) {
-        const int pad = d4gs_lds_pad_for_wgs_per_cu((const void *)k_raster_bwd_q8<D, DEPTH>, q_env);
-        D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_q8<D, DEPTH>), dim3(blocks), dim3(256), pad, stream, a);
+        const int pad = d4gs_lds_pad_for_wgs_per_cu((const void *)k_raster_bwd_q8<D, DEPTH, ABS>, q_env);
+        D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_q8<D, DEPTH, ABS>), dim3(blocks), dim3(256), pad, stream, a);
       } else {
-        const int pad = d4gs_lds_pad_for_wgs_per_cu((const void *)k_raster_bwd_q<D, DEPTH>, q_env);
-        D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_q<D, DEPTH>), dim3(blocks), dim3(256), pad, stream, a);
+        const int pad = d4gs_lds_pad_for_wgs_per_cu((const void *)k_raster_bwd_q<D, DEPTH, ABS>, q_env);
+        D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_q<D, DEPTH, ABS>), dim3(blocks), dim3(256), pad, stream, a);
       }
     }
   }
@@ -856,7 +884,7 @@ int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, int64_t n_isect, int row_mode, 
   // 4 sub-sample slots per block; a call with fewer sub-samples (a rank's share of an exposure-sharded frame) would idle the rest
   const int slots = ga.S >= 3 ? 4 : ga.S == 2 ? 2 : 1;
   const dim3 ggrid((ga.N + 63) / 64), gblock(slots * 64);
-#define D4GS_GATHER(SP_, SL_) D4GS_LAUNCH("k_gather", (k_gather<D, DEPTH, SP_, SL_>), ggrid, gblock, 0, stream, ga)
+#define D4GS_GATHER(SP_, SL_) D4GS_LAUNCH("k_gather", (k_gather<D, DEPTH, SP_, SL_, ABS>), ggrid, gblock, 0, stream, ga)
   if (ga.sparse) {
     if (slots == 4) D4GS_GATHER(true, 4);
     else if (slots == 2) D4GS_GATHER(true, 2);
@@ -904,12 +932,16 @@ int d4gs_raster_bwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   // xys_grad[..., 0] *= W / 2 * batch_size * S ; [..., 1] *= H / 2 * batch_size * S   (trainer.py:976-977)
   ga.sx = (float)dims->width / 2.0f * (float)g->stats_batch_size * (float)dims->S;
   ga.sy = (float)dims->height / 2.0f * (float)g->stats_batch_size * (float)dims->S;
+  const bool absg = (dims->flags & D4GS_ABSGRAD) != 0;
+  ga.v_means2d_abs = absg ? g->v_means2d_abs : nullptr, ga.stats_abs = absg && g->stats_absgrad;
   ga.max_wh = (float)(dims->width > dims->height ? dims->width : dims->height);
   const bool dep = dims->depth_mode != D4GS_DEPTH_NONE;
   const bool lazy = d4gs_lazy_on(dims, proj);
-#define D4GS_CASE(DD)                                                                             \
-  case DD:                                                                                        \
-    return dep ? launch_bwd<DD, true>(a, ga, isect->n_isect, g->row_mode, lazy, stream) : launch_bwd<DD, false>(a, ga, isect->n_isect, g->row_mode, lazy, stream);
+#define D4GS_LB(DD, DEP) (absg ? launch_bwd<DD, DEP, true>(a, ga, isect->n_isect, g->row_mode, lazy, stream) \
+                              : launch_bwd<DD, DEP, false>(a, ga, isect->n_isect, g->row_mode, lazy, stream))
+#define D4GS_CASE(DD) \
+  case DD:            \
+    return dep ? D4GS_LB(DD, true) : D4GS_LB(DD, false);
   switch (dims->D) {
     D4GS_CASE(1)
     D4GS_CASE(2)
@@ -924,6 +956,7 @@ int d4gs_raster_bwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
       return D4GS_EINVAL;
   }
 #undef D4GS_CASE
+#undef D4GS_LB
 }
 
 #ifdef D4GS_VARIANTS

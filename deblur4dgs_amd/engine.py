@@ -54,7 +54,11 @@ class RenderCfg:
     #                                  a flat all-reduce buffer) instead of fresh tensors; shapes / dtype must match
     control_stats: dict | None = None  # optional densification-statistics sink, updated by the backward's gather epilogue
     #                                  (SURVEY 8f-1): {"xys_grad_norm_acc" f32[N], "vis_count" i64[N], "max_radii" f32[N],
-    #                                  "batch_size" int, "update_max_radii" bool}
+    #                                  "batch_size" int, "update_max_radii" bool, "absgrad" bool (needs cfg.absgrad: the
+    #                                  statistics accumulate the norm of absgrad instead of the gradient's)}
+    absgrad: bool = False  # D4GS_ABSGRAD (include/d4gs.h): the backward also returns gsplat's `means2d.absgrad` [S,N,2] - per pixel
+    #                        |dL/dx|, |dL/dy|, summed - as the `.absgrad` attribute of the means2d tensor (staged chain) or of the
+    #                        xys_sink tensors and st.v_means2d_abs (FrameFn).  One channel chunk only (<= 16 colour channels)
     lazy_sort: bool | None = None  # D4GS_LAZY_SORT (include/d4gs.h): near / far partition of the tile lists, far parts sorted only
     #                                  for tiles that did not saturate within the near part.  Same image and gradients bit for bit, but the tail of a list behind
     #                                  its tile's last contributor is then left UNSORTED in `flatten_ids`.  None -> resolved once per
@@ -81,7 +85,8 @@ class RenderCfg:
     def dims(self) -> L.Dims:
         return L.Dims(self.N, self.G, self.K, self.T, self.S, self.D, self.width, self.height, self.depth_mode,
                       self.flags | (L.EXACT_CULL if self.exact_cull else 0) | (L.LAZY_SORT if self.lazy_sort else 0)
-                      | (L.EXACT_TILES if (self.exact_tiles and self.exact_cull) else 0), self.n_sigmoid, self.near_plane, self.far_plane,
+                      | (L.EXACT_TILES if (self.exact_tiles and self.exact_cull) else 0) | (L.ABSGRAD if self.absgrad else 0),
+                      self.n_sigmoid, self.near_plane, self.far_plane,
                       self.eps2d, self.radius_clip)
 
 
@@ -108,6 +113,7 @@ class State:
     policy: object = None
     xys_sink: list | None = None
     v_means2d: object = None
+    v_means2d_abs: object = None  # cfg.absgrad: [S,N,2]
 
 
 # "auto" | "dense" | "sparse": gradient-row mode of the composite backward (D4gsRasterGrads.row_mode); "auto" lets the library
@@ -727,6 +733,7 @@ class RasterFn(torch.autograd.Function):
             st.binned = True
             st.raster = rst
         ctx.st, ctx.cfg, ctx.rst, ctx.ctab = st, cfg, rst, ctab
+        ctx.means2d = means2d if cfg.absgrad else None  # the backward hangs `.absgrad` on it (gsplat's contract)
         ctx.max_hint = hint_used[0]  # the longest-list bound the forward composited under: the backward must see the same one
         return rst["render_colors"].view(S, H, W, cfg.NCH), rst["render_alphas"].unsqueeze(-1)
 
@@ -744,10 +751,11 @@ class RasterFn(torch.autograd.Function):
         v_alphas = None if v_alphas is None else v_alphas.to(torch.float32).contiguous()
         g = dict(
             v_render_colors=v_colors, v_render_alphas=v_alphas,
-            isect_grad=torch.empty(max(st.n_isect, 1), 6 + cfg.NCH, **f32),
+            isect_grad=torch.empty(max(st.n_isect, 1), 6 + cfg.NCH + (2 if cfg.absgrad else 0), **f32),
             isect_live=torch.empty((max(st.n_isect, 1) + 3) // 4 * 4, dtype=torch.uint8, device=dev),
             v_means2d=torch.empty(S, N, 2, **f32), v_conics=torch.empty(S, N, 3, **f32),
             v_depths=torch.empty(S, N, **f32), v_opac_act=torch.empty(N, **f32), v_ctab=torch.empty(N, cfg.DP, **f32),
+            v_means2d_abs=torch.empty(S, N, 2, **f32) if cfg.absgrad else None,
         )
         dims = cfg.dims()
         pout = L.fill(L.ProjOut(), **{**st.proj_out, "ctab": ctx.ctab})
@@ -761,8 +769,12 @@ class RasterFn(torch.autograd.Function):
             rg.stats_grad_norm_acc, rg.stats_vis_count = L.ptr(cs["xys_grad_norm_acc"]), L.ptr(cs["vis_count"])
             rg.stats_max_radii = L.ptr(cs["max_radii"])
             rg.stats_batch_size, rg.stats_update_max_radii = int(cs["batch_size"]), int(bool(cs.get("update_max_radii", False)))
+            rg.stats_absgrad = _stats_absgrad(cfg, cs)
         L.check(lib.d4gs_raster_bwd(C.byref(dims), C.byref(pout), C.byref(isect), C.byref(ras), C.byref(rg), _stream()),
                 "d4gs_raster_bwd")
+        if cfg.absgrad:
+            st.v_means2d_abs = g["v_means2d_abs"]
+            ctx.means2d.absgrad = g["v_means2d_abs"]
         return None, None, g["v_means2d"], g["v_conics"], g["v_depths"], g["v_opac_act"], g["v_ctab"], None
 
 
@@ -862,15 +874,17 @@ class FrameFn(torch.autograd.Function):
             v_times=buf("times", cfg.S) if dyn else None, v_RTs=buf("RTs", cfg.S, 3, 4) if pi["RTs"] is not None else None,
             v_viewmat=buf("viewmat", 4, 4), partials=None)
         v_m2d = torch.empty(cfg.S, cfg.N, 2, **f32)
+        v_abs = torch.empty(cfg.S, cfg.N, 2, **f32) if cfg.absgrad else None
         fg = L.FrameGrads()
         fg.v_blended, fg.v_acc, fg.v_renders, fg.v_alphas = L.ptr(v_blended), L.ptr(v_acc), L.ptr(v_renders), L.ptr(v_alphas)
-        fg.v_means2d = L.ptr(v_m2d)
+        fg.v_means2d, fg.v_means2d_abs = L.ptr(v_m2d), L.ptr(v_abs)
         fg.row_mode = row_mode_for(cfg, dev)
         if cfg.control_stats is not None:
             cs = _check_stats(cfg.control_stats, cfg.N)
             fg.stats_grad_norm_acc, fg.stats_vis_count = L.ptr(cs["xys_grad_norm_acc"]), L.ptr(cs["vis_count"])
             fg.stats_max_radii = L.ptr(cs["max_radii"])
             fg.stats_batch_size, fg.stats_update_max_radii = int(cs["batch_size"]), int(bool(cs.get("update_max_radii", False)))
+            fg.stats_absgrad = _stats_absgrad(cfg, cs)
         fio = L.fill(L.FrameIO(), **io)
         fio.near_target = cfg.near_target
         if blended:
@@ -878,14 +892,22 @@ class FrameFn(torch.autograd.Function):
         L.check(lib.d4gs_backward(C.byref(dims), C.byref(L.fill(L.ProjIn(), **pi)), C.byref(fio), C.byref(fg),
                                   C.byref(L.fill(L.LeafGrads(), **g)), C.c_void_p(st.ws_ptr), st.ws_bytes, st.ws_cap[0], st.ws_cap[1],
                                   _stream()), "d4gs_backward")
-        st.v_means2d = v_m2d
-        if st.xys_sink is not None:  # the `_current_xys[i].grad` side channel
+        st.v_means2d, st.v_means2d_abs = v_m2d, v_abs
+        if st.xys_sink is not None:  # the `_current_xys[i].grad` side channel (and `.absgrad`)
             for s, x in enumerate(st.xys_sink):
                 x.grad = v_m2d[s:s + 1]
+                if v_abs is not None:
+                    x.absgrad = v_abs[s:s + 1]
         outs = [g["v_means"], g["v_quats"], g["v_scales"], g["v_opacities"], g["v_colors"], g["v_motion_coefs"],
                 g["v_rots"], g["v_transls"], g["v_times"], g["v_RTs"], g["v_viewmat"]]
         outs = [x if need else None for x, need in zip(outs, ctx.needs)]
         return (None, None, *outs, None, None)
+
+
+def _stats_absgrad(cfg: RenderCfg, cs: dict) -> int:
+    if cs.get("absgrad", False) and not cfg.absgrad:
+        raise ValueError("control_stats['absgrad'] needs RenderCfg.absgrad")
+    return int(bool(cs.get("absgrad", False)))
 
 
 def frame_supported(cfg: RenderCfg) -> bool:
@@ -1018,6 +1040,18 @@ def render_instances(cfg: RenderCfg, means, quats, scales, opacities, colors, mo
     chunks = channel_chunks(cfg.D)
     if len(chunks) == 1 and chunks[0][2] == cfg.D:  # the common case: one kernel width, nothing to slice or pad
         rc, ra = RasterFn.apply(st, cfg, means2d, conics, depths, opac_act, ctab, background)
+        return rc, ra, means2d, radii, st
+    if cfg.absgrad and len(chunks) > 1:
+        raise NotImplementedError(f"absgrad with {cfg.D} colour channels: a render of more than {SUPPORTED_D[-1]} channels is "
+                                  "composited in several channel chunks, and the per-pixel absolute values absgrad sums cannot be "
+                                  "assembled from per-chunk sums")
+    if cfg.absgrad:  # one zero-padded chunk: it sees every pixel's whole gradient, so the kernels' absgrad (and statistics) hold
+        ck = replace(cfg, D=chunks[0][2], grad_arena=None)
+        F = torch.nn.functional
+        tab = F.pad(ctab[:, :cfg.D], (0, ck.DP - cfg.D))
+        bgk = None if background is None else F.pad(background.to(torch.float32).reshape(-1), (0, ck.D - cfg.D))
+        rck, ra = RasterFn.apply(st, ck, means2d, conics, depths, opac_act, tab, bgk)
+        rc = rck[..., :cfg.D] if cfg.depth_mode == L.DEPTH_NONE else torch.cat([rck[..., :cfg.D], rck[..., ck.D:ck.D + 1]], -1)
         return rc, ra, means2d, radii, st
     # any other channel count: chunks of <= 16 channels composited from the SAME projection + sorted tile lists
     # (gsplat renders wide feature vectors in `channel_chunk`-sized passes the same way); autograd sums the chunks'

@@ -8,6 +8,10 @@ Same argument names / meaning / return triple as gsplat 1.1.1:
 
 `sh_degree=d` (0..4): `colors` are SH coefficients [N,K,3] or [1,N,K,3] with K >= (d+1)^2, evaluated per Gaussian towards
 the camera centre as gsplat does (`sh.sh_colors`), then composited like [N,3] colours.
+
+`absgrad=True`: after a backward, `info["means2d"].absgrad` [C,N,2] holds sum over pixels of (|dL_p/dx|, |dL_p/dy|) (zeros for
+culled Gaussians), what gsplat's `DefaultStrategy(absgrad=True)` reads.  Computed inside the composite backward (D4GS_ABSGRAD);
+up to 16 colour channels (wider renders are composited in several channel chunks: NotImplementedError).
 """
 from __future__ import annotations
 
@@ -52,9 +56,9 @@ def rasterization(
 ):
     if viewmats.shape[0] != 1 or Ks.shape[0] != 1:
         raise ValueError("C must be 1 (the reference asserts it: flow3d/scene_model.py:249)")
-    if packed or absgrad or sparse_grad or rasterize_mode != "classic" or tile_size != 16:
-        raise NotImplementedError("only packed=False, absgrad=False, sparse_grad=False, rasterize_mode='classic' and "
-                                  "tile_size=16 are implemented")
+    if packed or sparse_grad or rasterize_mode != "classic" or tile_size != 16:
+        raise NotImplementedError("only packed=False, sparse_grad=False, rasterize_mode='classic' and tile_size=16 are "
+                                  "implemented")
     if render_mode not in _MODES:
         raise ValueError(f"render_mode {render_mode!r} not supported (RGB, RGB+ED, RGB+D)")
     N = means.shape[0]
@@ -85,7 +89,7 @@ def rasterization(
     cfg = RenderCfg(N=N, G=0, K=0, T=0, S=1, D=colors.shape[-1], width=width, height=height,
                     depth_mode=_MODES[render_mode], flags=0, near_plane=near_plane, far_plane=far_plane, eps2d=eps2d,
                     radius_clip=radius_clip, exact_cull=exact_cull, lazy_sort=lazy_sort, near_target=near_target,
-                    exact_tiles=exact_tiles)
+                    exact_tiles=exact_tiles, absgrad=bool(absgrad))
     rc, ra, means2d, radii, st = render_instances(cfg, means, quats, scales, opacities, colors, None, None, None,
                                                   None, None, viewmats[0], Ks[0], bg)
     tw, th = cfg.tiles

@@ -163,14 +163,17 @@ class SceneModel(nn.Module):
         self.deferred_size_check = False  # True: renders never wait for the device-side intersection count (engine
         #                                   RenderCfg.deferred_size_check; call engine.check_deferred() once per step)
 
-    def attach_control_stats(self, running_stats: dict, batch_size: int, update_max_radii: bool = False):
+    def attach_control_stats(self, running_stats: dict, batch_size: int, update_max_radii: bool = False, absgrad: bool = False):
         """SURVEY 8f-1, fused: until `detach_control_stats()`, the backward of every full render (all Gaussians, no
         filter mask) adds this step's densification statistics to `running_stats` inside the rasterizer's gather
         epilogue - what `Trainer._prepare_control_step` (flow3d/trainer.py:953-990) computes from
         `_current_xys[i].grad` / `_current_radii` after the step, without the S x 10 torch launches or the extra pass.
-        `batch_size` = number of render groups of the step (trainer.py:965)."""
-        self._stats_sink = (running_stats, int(batch_size), bool(update_max_radii))  # the dict itself: control steps
-        #                                                                  replace its tensors when N changes
+        `batch_size` = number of render groups of the step (trainer.py:965).
+        absgrad=True: the grow criterion of gsplat's `DefaultStrategy(absgrad=True)` - the statistics accumulate the norm of
+        absgrad (per pixel |dL/dx|, |dL/dy|, summed) instead of the gradient's, and after a backward `_current_xys[i].absgrad`
+        holds it.  Renders of more than 16 colour channels cannot compute absgrad (NotImplementedError)."""
+        self._stats_sink = (running_stats, int(batch_size), bool(update_max_radii), bool(absgrad))  # the dict itself: control
+        #                                                                  steps replace its tensors when N changes
 
     def detach_control_stats(self):
         self._stats_sink = None
@@ -178,10 +181,10 @@ class SceneModel(nn.Module):
     def _sink_for(self, N: int):
         if self._stats_sink is None or not torch.is_grad_enabled():
             return None
-        stats, batch_size, upd = self._stats_sink
+        stats, batch_size, upd, absgrad = self._stats_sink
         if stats["vis_count"].shape[0] != N:
             return None
-        return dict(stats, batch_size=batch_size, update_max_radii=upd)
+        return dict(stats, batch_size=batch_size, update_max_radii=upd, absgrad=absgrad)
 
     num_gaussians = property(lambda self: self.num_bg_gaussians + self.num_fg_gaussians)
     num_bg_gaussians = property(lambda self: self.bg.num_gaussians if self.bg is not None else 0)
@@ -356,7 +359,8 @@ class SceneModel(nn.Module):
             times_s if G > 0 else None, RTs_s, w2cs[0], Ks[0], W, H, background=bg_color[0], return_depth=return_depth,
             policy=None, blend=True,
             control_stats=self._sink_for(N) if (which == "all" and filter_mask is None) else None,
-            deferred_size_check=self.deferred_size_check, fused=self.fused)
+            deferred_size_check=self.deferred_size_check, fused=self.fused,
+            absgrad=self._stats_sink is not None and self._stats_sink[3] and torch.is_grad_enabled())
         blended = res["blended"][None]  # [1,H,W,D']
         renders = res["renders"]
 
@@ -368,9 +372,11 @@ class SceneModel(nn.Module):
             if one_call:
                 res["state"].xys_sink = xys  # the backward deposits d loss / d means2d there
             else:
-                def _deposit(g, xys=xys):
+                def _deposit(g, xys=xys, st=res["state"]):
                     for s, x in enumerate(xys):
                         x.grad = g[s:s + 1]
+                        if st.v_means2d_abs is not None:  # (the composite backward ran just before: RasterFn)
+                            x.absgrad = st.v_means2d_abs[s:s + 1]
 
                 m2d.register_hook(_deposit)
             self._current_xys = xys

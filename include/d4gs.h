@@ -60,6 +60,13 @@ enum { /* D4gsDims.flags */
                            The flag must be THE SAME in the dims passed to d4gs_project_fwd, d4gs_bin_sort, d4gs_raster_fwd and
                            d4gs_raster_bwd of one render (the counts and offsets are built from the masks; the binning walks them):
                            with the flag and no tile_masks those calls return D4GS_EINVAL. */
+  D4GS_ABSGRAD = 32,    /* (v305) absgrad (gsplat's `absgrad=True`, the AbsGS grow criterion): d4gs_raster_bwd / d4gs_backward also
+                           return v_means2d_abs [S,N,2] = sum over pixels p of (|dL_p/dx|, |dL_p/dy|) per instance - each pixel's own
+                           contribution to v_means2d, every channel, the depth channel, v_alphas and the background included, made
+                           absolute before the sum.  Rows of isect_grad grow by two floats (D4gsSizes.isect_grad_row = 8 + D'), the
+                           frame workspace with them.  Needs D4gsRasterGrads / D4gsFrameGrads.v_means2d_abs (and v_means2d_abs
+                           needs the flag); renders of more than 16 colour channels (several channel chunks) cannot be assembled from
+                           per-chunk sums.  The CPU twins do not implement it (D4GS_EINVAL). */
   D4GS_EXACT_CULL = 4   /* bin a splat only into tiles that hold a pixel with alpha >= 1/255 (tight ellipse
                            sigma <= ln(255*opacity), intersected with gsplat's 3-sigma tile rectangle).  Pixels in
                            the dropped tiles would fail gsplat's alpha test anyway, so images and gradients are
@@ -197,6 +204,9 @@ typedef struct D4gsRasterGrads {
   int32_t stats_batch_size;
   int32_t stats_update_max_radii;
   int32_t row_mode;             /* D4GS_ROWS_*: AUTO picks dense / sparse rows from the list capacity per instance */
+  float *v_means2d_abs;         /* [S,N,2] (v305, appended) out with D4GS_ABSGRAD (required then, NULL otherwise): the absgrad contract */
+  int32_t stats_absgrad;        /* (v305, appended) with D4GS_ABSGRAD only: the fused statistics accumulate |v_means2d_abs * (W/2, H/2) *
+                                   stats_batch_size * S| instead (same arithmetic and order) */
 } D4gsRasterGrads;
 
 /* leaf gradients produced by d4gs_project_bwd (all overwritten, not accumulated) */
@@ -462,6 +472,8 @@ typedef struct D4gsFrameGrads {
   int64_t *stats_vis_count;
   float *stats_max_radii;
   int32_t stats_batch_size, stats_update_max_radii, row_mode;
+  float *v_means2d_abs;               /* [S,N,2] out (v305, appended): as in D4gsRasterGrads, with D4GS_ABSGRAD */
+  int32_t stats_absgrad;              /* (v305, appended) as in D4gsRasterGrads */
 } D4gsFrameGrads;
 D4GS_API size_t d4gs_frame_workspace_bytes(const D4gsDims *dims, int64_t isect_capacity);
 /* The prefix of that workspace d4gs_forward alone touches (everything but the backward's scratch: image-gradient stack, per-
