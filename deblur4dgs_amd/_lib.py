@@ -31,7 +31,7 @@ class ProjIn(C.Structure):
 class ProjOut(C.Structure):
     _fields_ = [(n, F) for n in ("means2d", "depths", "conics", "radii", "opac_act", "ctab", "geom", "tile_rects", "tiles_touched",
                                  "isect_offsets", "lazy_ws", "tile_counts", "tile_offsets", "n_isect", "scan_ws", "blend_bases",
-                                 "tile_masks")]
+                                 "tile_masks", "compensations")]
 
 
 class Isect(C.Structure):
@@ -55,7 +55,8 @@ class Sizes(C.Structure):
                                          "tiles_touched", "isect_offsets", "tile_counts", "tile_offsets", "n_isect",
                                          "scan_ws", "render_colors", "render_alphas", "last_ids", "final_T",
                                          "isect_grad_row", "bwd_partials", "seg_state", "lazy_ws")] + \
-               [(n, C.c_int32) for n in ("tiles_x", "tiles_y", "channels")] + [("blend_bases", C.c_int64), ("tile_masks", C.c_int64)]
+               [(n, C.c_int32) for n in ("tiles_x", "tiles_y", "channels")] + [("blend_bases", C.c_int64), ("tile_masks", C.c_int64),
+                                                                                                  ("compensations", C.c_int64)]
 
 
 class MoveModelParams(C.Structure):
@@ -96,7 +97,7 @@ class Poses(C.Structure):
     _fields_ = [("means", F), ("quats", F), ("transforms", F), ("g_major", C.c_int32)]
 
 
-RAW_PARAMS, RAW_COLORS, EXACT_CULL, LAZY_SORT, EXACT_TILES, ABSGRAD = 1, 2, 4, 8, 16, 32
+RAW_PARAMS, RAW_COLORS, EXACT_CULL, LAZY_SORT, EXACT_TILES, ABSGRAD, ANTIALIASED = 1, 2, 4, 8, 16, 32, 64
 DEPTH_NONE, DEPTH_ED, DEPTH_D = 0, 1, 2
 ROWS_AUTO, ROWS_DENSE, ROWS_SPARSE = 0, 1, 2
 TILE = 16

@@ -115,6 +115,20 @@ int d4gs_check_absgrad(const char *who, const D4gsDims *d, const float *v_means2
   return D4GS_OK;
 }
 
+// D4GS_ANTIALIASED and D4gsProjOut.compensations come together, like D4GS_ABSGRAD and its buffers
+int d4gs_check_antialiased(const char *who, const D4gsDims *d, const float *compensations) {
+  const bool flag = (d->flags & D4GS_ANTIALIASED) != 0;
+  if (flag && !compensations) {
+    d4gs_set_error("%s: D4GS_ANTIALIASED needs D4gsProjOut.compensations", who);
+    return D4GS_EINVAL;
+  }
+  if (!flag && compensations) {
+    d4gs_set_error("%s: D4gsProjOut.compensations given without D4GS_ANTIALIASED in dims->flags", who);
+    return D4GS_EINVAL;
+  }
+  return D4GS_OK;
+}
+
 static int check_dims(const D4gsDims *d) {
   if (!d) {
     d4gs_set_error("dims is NULL");
@@ -195,6 +209,7 @@ int d4gs_query_sizes(const D4gsDims *d, D4gsSizes *z) {
   z->tiles_x = (int32_t)tw, z->tiles_y = (int32_t)th, z->channels = (int32_t)nch;
   z->blend_bases = d->G > 0 ? S * (int64_t)d->K * 16 : 0;
   z->tile_masks = SN;
+  z->compensations = (d->flags & D4GS_ANTIALIASED) ? SN : 0;
   return D4GS_OK;
 }
 
@@ -251,6 +266,7 @@ int d4gs_project_fwd(const D4gsDims *dims, const D4gsProjIn *in, const D4gsProjO
     d4gs_set_error("d4gs_project_fwd: D4gsProjOut.ctab must be 16-byte aligned");
     return D4GS_EINVAL;
   }
+  if ((rc = d4gs_check_antialiased("d4gs_project_fwd", dims, out->compensations))) return rc;
   return d4gs_project_fwd_impl(dims, in, out, (hipStream_t)stream);
 }
 
@@ -311,6 +327,11 @@ int d4gs_raster_bwd(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIse
     return D4GS_EINVAL;
   }
   if ((rc = d4gs_check_absgrad("d4gs_raster_bwd", dims, g->v_means2d_abs, g->stats_absgrad))) return rc;
+  if ((rc = d4gs_check_antialiased("d4gs_raster_bwd", dims, proj->compensations))) return rc;
+  if ((dims->flags & D4GS_ANTIALIASED) && !proj->opac_act) {  // the compensation adjoint needs the activated opacity
+    d4gs_set_error("d4gs_raster_bwd: D4GS_ANTIALIASED needs D4gsProjOut.opac_act");
+    return D4GS_EINVAL;
+  }
   return d4gs_raster_bwd_impl(dims, proj, isect, r, g, nullptr, (hipStream_t)stream);
 }
 

@@ -265,6 +265,7 @@ struct ProjOut {
   float rz;
   float a, b, c;    // blurred 2-D covariance
   float det;
+  float det0;       // determinant of the 2-D covariance BEFORE the eps2d blur (D4GS_ANTIALIASED's compensation)
   float mx, my;
   int radius;       // 0 = culled
   bool in_x, in_y;  // inside the 1.3*tan(fov) clamp
@@ -309,6 +310,9 @@ __device__ __forceinline__ void project_instance(const Cam &cam, const float *mw
   o.b = c01;
   o.c = c11 + d.eps2d;
   o.det = o.a * o.c - o.b * o.b;
+  // (an fma on purpose: a plain c01 * c01 would be common with b * b above, and sharing that product changes how the compiler
+  // contracts `det` - the classic conic must keep its bits)
+  o.det0 = __builtin_fmaf(-c01, c01, c00 * c11);
   if (!(o.det > 0.f)) return;
   float mid = 0.5f * (o.a + o.c);
   float v1 = mid + sqrtf(fmaxf(0.01f, mid * mid - o.det));

@@ -258,6 +258,10 @@ int check_args(const D4gsDims *d, const D4gsProjIn *in, const D4gsFrameIO *io, c
     d4gs_set_error("%s: D4GS_ABSGRAD is not implemented by the CPU twins (d4gs_backward computes absgrad)", who);
     return D4GS_EINVAL;
   }
+  if (d->flags & D4GS_ANTIALIASED) {
+    d4gs_set_error("%s: D4GS_ANTIALIASED is not implemented by the CPU twins (d4gs_forward / d4gs_backward compute it)", who);
+    return D4GS_EINVAL;
+  }
   return D4GS_OK;
 }
 

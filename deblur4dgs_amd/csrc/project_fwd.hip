@@ -50,7 +50,8 @@ __device__ __forceinline__ void preblend_bases(const FwdArgs &a, float *Bs) {
 }
 
 template <bool XT /* D4GS_EXACT_TILES: the wave-cooperative per-tile ellipse test (its own instantiation: 88 instead of 64 VGPRs) */,
-          bool TAB /* FwdArgs.use_table: blended bases from the global table (scalar loads) instead of the block's LDS slab */>
+          bool TAB /* FwdArgs.use_table: blended bases from the global table (scalar loads) instead of the block's LDS slab */,
+          bool AA = false /* D4GS_ANTIALIASED: opacity * compensation in the geom record and the culls, compensation -> out.compensations */>
 __global__ void __launch_bounds__(D4GS_PROJ_BLOCK)
 #ifdef XT_WAVES  // (A/B) the exact-tiles instantiations at XT_WAVES waves per SIMD (6: 80 VGPRs + a 16-byte scratch frame; default: 83-85, 5 waves)
 __attribute__((amdgpu_waves_per_eu(XT ? XT_WAVES : 1, XT ? XT_WAVES : 10)))
@@ -166,6 +167,7 @@ k_project_fwd(const FwdArgs a) {
     int cnt = 0, radius_out = 0;
     int2 rect = make_int2(0, 0);
     float m2x = 0.f, m2y = 0.f, dep = 0.f, ca = 0.f, cb = 0.f, cc = 0.f;
+    float comp = 0.f, opeff = 0.f;  // AA: gsplat's compensation sqrt(det(cov2d) / det(cov2d + eps2d I)) and opacity * compensation
     float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
     if (active) {
     float mw[3], Rm[9];
@@ -219,11 +221,15 @@ k_project_fwd(const FwdArgs a) {
       float idet = 1.f / p.det;
       ca = p.c * idet, cb = -p.b * idet, cc = p.a * idet;
       m2x = p.mx, m2y = p.my, dep = p.pc[2];
-      g0 = make_float4(m2x, m2y, opac, dep);
+      if constexpr (AA) {  // from the pre-blur determinant: more accurate than the conic identity for thin splats
+        comp = d.eps2d != 0.f ? sqrtf(fmaxf(0.f, p.det0 / p.det)) : 1.f;  // (no blur: exactly 1, whatever the rounding of the two dets)
+        opeff = opac * comp;
+      }
+      g0 = make_float4(m2x, m2y, AA ? opeff : opac, dep);
       g1 = make_float4(ca, cb, cc, 0.f);
       int x0, y0, x1, y1;
       tile_rect(m2x, m2y, p.radius, a.tw, a.th, x0, y0, x1, y1);
-      if (d.flags & D4GS_EXACT_CULL) tight_rect(m2x, m2y, opac, p.a, p.c, x0, y0, x1, y1);
+      if (d.flags & D4GS_EXACT_CULL) tight_rect(m2x, m2y, AA ? opeff : opac, p.a, p.c, x0, y0, x1, y1);
       rect = make_int2(x0 | (x1 << 16), y0 | (y1 << 16));
       cnt = (x1 - x0) * (y1 - y0);
     }
@@ -238,6 +244,7 @@ k_project_fwd(const FwdArgs a) {
       float4 *gp = reinterpret_cast<float4 *>(a.out.geom + i * D4GS_GEOM_STRIDE);
       gp[0] = g0;
       gp[1] = g1;
+      if constexpr (AA) a.out.compensations[i] = comp;
     }
     }  // active
     // ---- D4GS_EXACT_TILES: which tiles of the tight rectangle does the alpha >= 1/255 ellipse reach?  The (instance, tile) pairs of
@@ -261,8 +268,8 @@ k_project_fwd(const FwdArgs a) {
       const int total = __shfl(inc, 63);
       if (total > 0) {  // (wave-uniform)
         xt_pre[tid] = inc - np;
-        // conic of the BLURRED covariance = the geom record's; tau as tight_rect computes it
-        const float tau = __logf(255.f * opac) * 1.01f + 0.02f;
+        // conic of the BLURRED covariance = the geom record's; tau as tight_rect computes it (from the opacity the composite sees)
+        const float tau = __logf(255.f * (AA ? opeff : opac)) * 1.01f + 0.02f;
         xt_rec[tid][0] = make_float4(m2x, m2y, ca, cb);
         xt_rec[tid][1] = make_float4(cc, tau, __int_as_float(x0 | (y0 << 16)), __int_as_float(w));
         xt_mask[tid][0] = 0u, xt_mask[tid][1] = 0u;
@@ -323,6 +330,7 @@ k_project_fwd(const FwdArgs a) {
       float4 *gp = reinterpret_cast<float4 *>(a.out.geom + i * D4GS_GEOM_STRIDE);
       gp[0] = g0;
       gp[1] = g1;
+      if constexpr (AA) a.out.compensations[i] = comp;
     }
   }
 }
@@ -851,6 +859,9 @@ int d4gs_project_fwd_impl(const D4gsDims *dims, const D4gsProjIn *in, const D4gs
     const bool xt = dims->flags & D4GS_EXACT_TILES;
     const void *fn = xt ? (a.use_table ? (const void *)k_project_fwd<true, true> : (const void *)k_project_fwd<true, false>)
                         : (a.use_table ? (const void *)k_project_fwd<false, true> : (const void *)k_project_fwd<false, false>);
+    if (dims->flags & D4GS_ANTIALIASED)
+      fn = xt ? (a.use_table ? (const void *)k_project_fwd<true, true, true> : (const void *)k_project_fwd<true, false, true>)
+              : (a.use_table ? (const void *)k_project_fwd<false, true, true> : (const void *)k_project_fwd<false, false, true>);
     // sub-sample groups (the kernel's header comment): as many as keep the launch within ONE round of the chip's 2 048 four-wave slots
     static const int sg_env = getenv("D4GS_PROJ_SG") ? atoi(getenv("D4GS_PROJ_SG")) : 0;  // A/B hook
     // (measured, profiles/r06_ab_proj_groups.txt: the training shape - 547 blocks - 57.7 -> 44.1 us with 3 groups; cfg2 - 1 172 blocks - 65.3 -> 62.3

@@ -540,6 +540,15 @@ struct GatherArgs {
   float *v_means2d_abs;
   int stats_abs;
 };
+// AA instantiations (D4GS_ANTIALIASED) get these behind the common arguments; the others take exactly GatherArgs (same kernarg segment)
+struct GatherAA {
+  const float *comp;      // [S,N] compensations
+  const float *opac_act;  // [N]
+  const float *geom;      // [S*N,8] the conic of the record (g1.xyz)
+  float eps2d;
+};
+template <bool AA> struct GatherArgsT : GatherArgs {};
+template <> struct GatherArgsT<true> : GatherArgs { GatherAA aa; };
 
 // The rows of the 64 instances a wave owns (same sub-sample, consecutive Gaussians) form ONE contiguous span of
 // isect_grad: the wave streams it into LDS with coalesced loads and every lane then sums its own rows from there, in
@@ -559,8 +568,11 @@ struct GatherArgs {
 constexpr int gather_rows(int D, bool sparse) { return D >= 8 ? 96 : sparse ? D4GS_GATHER_ROWS_SPARSE : 192; }
 constexpr int GATHER_SC = 1024;                         // rows per super-chunk of the cooperative sparse path (16 flags per lane)
 // ABS: rows of 6 + NCH + 2 floats (raster_bwd_q_body); the last two columns are summed, in the same order, into v_means2d_abs
-template <int D, bool DEPTH, bool SPARSE, int SLOTS /* waves per block: 4, or S when the call has fewer sub-samples */, bool ABS = false>
-__global__ void __launch_bounds__(SLOTS * 64) k_gather(const GatherArgs a) {
+// AA: the rows' opacity column (the gradient of the effective opacity opac_act * comp) is split into comp * it for v_opac_act and the
+// compensation's adjoint opac_act * it * d comp / d conic, added to v_conics
+template <int D, bool DEPTH, bool SPARSE, int SLOTS /* waves per block: 4, or S when the call has fewer sub-samples */, bool ABS = false,
+          bool AA = false>
+__global__ void __launch_bounds__(SLOTS * 64) k_gather(const GatherArgsT<AA> a) {
   constexpr int NCH = D + (DEPTH ? 1 : 0);
   constexpr int DP = (D + 3) & ~3;
   constexpr int R = 6 + NCH + (ABS ? 2 : 0);
@@ -588,6 +600,8 @@ __global__ void __launch_bounds__(SLOTS * 64) k_gather(const GatherArgs a) {
   float st_acc = 0.f, st_mr = 0.f;
   int64_t st_vis = 0;
   if (stats && in) st_acc = a.stats_acc[g], st_vis = a.stats_vis[g], st_mr = a.stats_mr[g];
+  float oa = 0.f;
+  if constexpr (AA) oa = in ? a.aa.opac_act[g] : 0.f;
   // the (count, offset) pair of the next sub-sample is fetched while the current one is streamed and summed
   const size_t gi = in ? g : a.N - 1;
   // (an overflowed render never wrote isect_offsets - k_emit returned early: do not read it, stream nothing)
@@ -773,6 +787,20 @@ __global__ void __launch_bounds__(SLOTS * 64) k_gather(const GatherArgs a) {
       __builtin_amdgcn_wave_barrier();
     }
     if (in) {
+      if constexpr (AA) {
+        // comp^2 = 1 - e (qa + qc) + e^2 (qa qc - qb^2) for the stored conic (qa, qb, qc) = inv(cov2d + e I): the derivative in the
+        // conic's terms; 0 where comp == 0 (such an instance has alpha 0 at every pixel: its row sums are 0 as well).  Explicit fmas and
+        // no contraction: every instantiation (dense / sparse rows, slots) computes the same bits.
+#pragma clang fp contract(off)
+        const float cp = a.aa.comp[i];
+        const float4 q = *reinterpret_cast<const float4 *>(a.aa.geom + i * D4GS_GEOM_STRIDE + 4);
+        const float e = a.aa.eps2d, e2 = e * e;
+        const float h = cp > 0.f ? acc[5] * oa * 0.5f / cp : 0.f;  // v_comp / (2 comp), v_comp = v_opacity * opac_act
+        acc[2] = __builtin_fmaf(h, __builtin_fmaf(e2, q.z, -e), acc[2]);
+        acc[3] = __builtin_fmaf(h, -2.f * e2 * q.y, acc[3]);
+        acc[4] = __builtin_fmaf(h, __builtin_fmaf(e2, q.x, -e), acc[4]);
+        acc[5] = cp > 0.f ? acc[5] * cp : 0.f;  // (comp 0: the composite's opacity column is 0 * (1 / 0), not a number)
+      }
       *reinterpret_cast<float2 *>(a.v_means2d + i * 2) = make_float2(acc[0], acc[1]);
       a.v_conics[i * 3] = acc[2];
       a.v_conics[i * 3 + 1] = acc[3];
@@ -830,8 +858,8 @@ static bool choose_sparse(int row_mode, int64_t n_isect, int64_t n_inst, bool la
   return n_isect >= 6 * (n_inst > 0 ? n_inst : 1);
 }
 
-template <int D, bool DEPTH, bool ABS>
-int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, int64_t n_isect, int row_mode, bool lazy, hipStream_t stream) {
+template <int D, bool DEPTH, bool ABS, bool AA>
+int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, const GatherAA &gaa, int64_t n_isect, int row_mode, bool lazy, hipStream_t stream) {
   const int n_tiles = a.S * a.tw * a.th;
   const int blocks = ((n_tiles + 7) / 8) * 8;
   bool launched = false;
@@ -884,7 +912,10 @@ int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, int64_t n_isect, int row_mode, 
   // 4 sub-sample slots per block; a call with fewer sub-samples (a rank's share of an exposure-sharded frame) would idle the rest
   const int slots = ga.S >= 3 ? 4 : ga.S == 2 ? 2 : 1;
   const dim3 ggrid((ga.N + 63) / 64), gblock(slots * 64);
-#define D4GS_GATHER(SP_, SL_) D4GS_LAUNCH("k_gather", (k_gather<D, DEPTH, SP_, SL_, ABS>), ggrid, gblock, 0, stream, ga)
+  GatherArgsT<AA> gx;
+  static_cast<GatherArgs &>(gx) = ga;
+  if constexpr (AA) gx.aa = gaa;
+#define D4GS_GATHER(SP_, SL_) D4GS_LAUNCH("k_gather", (k_gather<D, DEPTH, SP_, SL_, ABS, AA>), ggrid, gblock, 0, stream, gx)
   if (ga.sparse) {
     if (slots == 4) D4GS_GATHER(true, 4);
     else if (slots == 2) D4GS_GATHER(true, 2);
@@ -935,10 +966,14 @@ int d4gs_raster_bwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   const bool absg = (dims->flags & D4GS_ABSGRAD) != 0;
   ga.v_means2d_abs = absg ? g->v_means2d_abs : nullptr, ga.stats_abs = absg && g->stats_absgrad;
   ga.max_wh = (float)(dims->width > dims->height ? dims->width : dims->height);
+  const bool aa = (dims->flags & D4GS_ANTIALIASED) != 0;
+  GatherAA gaa;
+  gaa.comp = proj->compensations, gaa.opac_act = proj->opac_act, gaa.geom = proj->geom, gaa.eps2d = dims->eps2d;
   const bool dep = dims->depth_mode != D4GS_DEPTH_NONE;
   const bool lazy = d4gs_lazy_on(dims, proj);
-#define D4GS_LB(DD, DEP) (absg ? launch_bwd<DD, DEP, true>(a, ga, isect->n_isect, g->row_mode, lazy, stream) \
-                              : launch_bwd<DD, DEP, false>(a, ga, isect->n_isect, g->row_mode, lazy, stream))
+#define D4GS_LBA(DD, DEP, ABS_) (aa ? launch_bwd<DD, DEP, ABS_, true>(a, ga, gaa, isect->n_isect, g->row_mode, lazy, stream) \
+                                    : launch_bwd<DD, DEP, ABS_, false>(a, ga, gaa, isect->n_isect, g->row_mode, lazy, stream))
+#define D4GS_LB(DD, DEP) (absg ? D4GS_LBA(DD, DEP, true) : D4GS_LBA(DD, DEP, false))
 #define D4GS_CASE(DD) \
   case DD:            \
     return dep ? D4GS_LB(DD, true) : D4GS_LB(DD, false);
@@ -957,6 +992,7 @@ int d4gs_raster_bwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   }
 #undef D4GS_CASE
 #undef D4GS_LB
+#undef D4GS_LBA
 }
 
 #ifdef D4GS_VARIANTS

@@ -59,6 +59,8 @@ class RenderCfg:
     absgrad: bool = False  # D4GS_ABSGRAD (include/d4gs.h): the backward also returns gsplat's `means2d.absgrad` [S,N,2] - per pixel
     #                        |dL/dx|, |dL/dy|, summed - as the `.absgrad` attribute of the means2d tensor (staged chain) or of the
     #                        xys_sink tensors and st.v_means2d_abs (FrameFn).  One channel chunk only (<= 16 colour channels)
+    antialiased: bool = False  # D4GS_ANTIALIASED (include/d4gs.h): gsplat's rasterize_mode="antialiased" - composite with opacity *
+    #                            compensation, compensation = sqrt(det(cov2d) / det(cov2d + eps2d I)), kept in proj_out["compensations"] [S,N]
     lazy_sort: bool | None = None  # D4GS_LAZY_SORT (include/d4gs.h): near / far partition of the tile lists, far parts sorted only
     #                                  for tiles that did not saturate within the near part.  Same image and gradients bit for bit, but the tail of a list behind
     #                                  its tile's last contributor is then left UNSORTED in `flatten_ids`.  None -> resolved once per
@@ -85,7 +87,8 @@ class RenderCfg:
     def dims(self) -> L.Dims:
         return L.Dims(self.N, self.G, self.K, self.T, self.S, self.D, self.width, self.height, self.depth_mode,
                       self.flags | (L.EXACT_CULL if self.exact_cull else 0) | (L.LAZY_SORT if self.lazy_sort else 0)
-                      | (L.EXACT_TILES if (self.exact_tiles and self.exact_cull) else 0) | (L.ABSGRAD if self.absgrad else 0),
+                      | (L.EXACT_TILES if (self.exact_tiles and self.exact_cull) else 0) | (L.ABSGRAD if self.absgrad else 0)
+                      | (L.ANTIALIASED if self.antialiased else 0),
                       self.n_sigmoid, self.near_plane, self.far_plane,
                       self.eps2d, self.radius_clip)
 
@@ -493,6 +496,7 @@ class ProjectFn(torch.autograd.Function):
             scan_ws=torch.empty(lib.d4gs_scan_ws_elems(S * N), **i32),
             blend_bases=torch.empty(S * cfg.K * 16, **f32) if cfg.G > 0 else None,  # the backward's scalar-load table (include/d4gs.h)
             tile_masks=torch.empty(S * N, dtype=torch.int64, device=dev) if (cfg.exact_tiles and cfg.exact_cull) else None,
+            compensations=torch.empty(S, N, **f32) if cfg.antialiased else None,
         )
         dims = cfg.dims()
         pin, pout = _proj_structs(st)

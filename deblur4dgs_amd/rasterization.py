@@ -12,6 +12,10 @@ the camera centre as gsplat does (`sh.sh_colors`), then composited like [N,3] co
 `absgrad=True`: after a backward, `info["means2d"].absgrad` [C,N,2] holds sum over pixels of (|dL_p/dx|, |dL_p/dy|) (zeros for
 culled Gaussians), what gsplat's `DefaultStrategy(absgrad=True)` reads.  Computed inside the composite backward (D4GS_ABSGRAD);
 up to 16 colour channels (wider renders are composited in several channel chunks: NotImplementedError).
+
+`rasterize_mode="antialiased"`: gsplat's Mip-Splatting 2-D filter.  Every splat composites with opacity * compensation,
+compensation = sqrt(max(0, det(cov2d) / det(cov2d + eps2d I))), computed by the projection kernel (D4GS_ANTIALIASED);
+`info["opacities"]` is then that product [C,N] (0 where radii == 0).  Everything else in `info` keeps its classic definition.
 """
 from __future__ import annotations
 
@@ -56,9 +60,10 @@ def rasterization(
 ):
     if viewmats.shape[0] != 1 or Ks.shape[0] != 1:
         raise ValueError("C must be 1 (the reference asserts it: flow3d/scene_model.py:249)")
-    if packed or sparse_grad or rasterize_mode != "classic" or tile_size != 16:
-        raise NotImplementedError("only packed=False, sparse_grad=False, rasterize_mode='classic' and tile_size=16 are "
-                                  "implemented")
+    if rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError(f"rasterize_mode {rasterize_mode!r} not supported (classic, antialiased)")
+    if packed or sparse_grad or tile_size != 16:
+        raise NotImplementedError("only packed=False, sparse_grad=False and tile_size=16 are implemented")
     if render_mode not in _MODES:
         raise ValueError(f"render_mode {render_mode!r} not supported (RGB, RGB+ED, RGB+D)")
     N = means.shape[0]
@@ -89,16 +94,19 @@ def rasterization(
     cfg = RenderCfg(N=N, G=0, K=0, T=0, S=1, D=colors.shape[-1], width=width, height=height,
                     depth_mode=_MODES[render_mode], flags=0, near_plane=near_plane, far_plane=far_plane, eps2d=eps2d,
                     radius_clip=radius_clip, exact_cull=exact_cull, lazy_sort=lazy_sort, near_target=near_target,
-                    exact_tiles=exact_tiles, absgrad=bool(absgrad))
+                    exact_tiles=exact_tiles, absgrad=bool(absgrad), antialiased=rasterize_mode == "antialiased")
     rc, ra, means2d, radii, st = render_instances(cfg, means, quats, scales, opacities, colors, None, None, None,
                                                   None, None, viewmats[0], Ks[0], bg)
     tw, th = cfg.tiles
+    opacities = st.proj_out["opac_act"][None]
+    if cfg.antialiased and N > 0:  # gsplat's info["opacities"] is what was composited (N == 0: nothing was projected)
+        opacities = opacities * st.proj_out["compensations"]
     info = {
         "means2d": means2d,
         "radii": radii,
         "depths": st.proj_out["depths"],
         "conics": st.proj_out["conics"],
-        "opacities": st.proj_out["opac_act"][None],
+        "opacities": opacities,
         "tiles_per_gauss": st.proj_out["tiles_touched"].view(1, N),
         "flatten_ids": st.isect["sorted_gid"][: st.n_isect],
         "isect_offsets": st.proj_out["tile_offsets"][:-1].view(1, th, tw),

@@ -67,6 +67,14 @@ enum { /* D4gsDims.flags */
                            frame workspace with them.  Needs D4gsRasterGrads / D4gsFrameGrads.v_means2d_abs (and v_means2d_abs
                            needs the flag); renders of more than 16 colour channels (several channel chunks) cannot be assembled from
                            per-chunk sums.  The CPU twins do not implement it (D4GS_EINVAL). */
+  D4GS_ANTIALIASED = 64, /* (v305) gsplat's rasterize_mode="antialiased" (the Mip-Splatting 2-D filter): d4gs_project_fwd computes per
+                           instance compensation = sqrt(max(0, det(cov2d) / det(cov2d + eps2d I))) (0 for culled instances), writes it to
+                           D4gsProjOut.compensations and composites - and culls, under D4GS_EXACT_CULL / D4GS_EXACT_TILES - with opacity *
+                           compensation.  means2d, conics, depths, radii and the tile rectangles keep their classic definitions.
+                           d4gs_raster_bwd / d4gs_backward fold the compensation's adjoint into v_conics and return v_opac_act = sum over s
+                           of compensation * (gradient of the effective opacity).  Needs D4gsProjOut.compensations (and it needs the flag)
+                           in d4gs_project_fwd and d4gs_raster_bwd; the one-call frame carves it from the workspace.  The CPU twins do
+                           not implement it (D4GS_EINVAL). */
   D4GS_EXACT_CULL = 4   /* bin a splat only into tiles that hold a pixel with alpha >= 1/255 (tight ellipse
                            sigma <= ln(255*opacity), intersected with gsplat's 3-sigma tile rectangle).  Pixels in
                            the dropped tiles would fail gsplat's alpha test anyway, so images and gradients are
@@ -143,6 +151,8 @@ typedef struct D4gsProjOut {
   uint64_t *tile_masks;    /* [S*N] (v305, appended; needed with D4GS_EXACT_TILES only): bit (ty - y0) * 8 + (tx - x0) = tile (tx, ty) of the
                               instance's packed rectangle is binned; 0 = no mask, the whole rectangle is (rectangles wider or taller
                               than 8 tiles, single tiles, flag off) */
+  float *compensations;    /* [S,N] (v305, appended) out with D4GS_ANTIALIASED (required then, NULL otherwise): the antialiasing
+                              compensation of every instance, 0 where radii == 0 */
 } D4gsProjOut;
 
 typedef struct D4gsIsect {
@@ -258,6 +268,7 @@ typedef struct {
   int32_t tiles_x, tiles_y, channels;                            /* tile grid; D + depth channel */
   int64_t blend_bases;                                           /* D4gsProjOut.blend_bases (v305, appended; 0 when G == 0) */
   int64_t tile_masks;                                            /* D4gsProjOut.tile_masks (uint64 elements; needed with D4GS_EXACT_TILES) */
+  int64_t compensations;                                         /* D4gsProjOut.compensations (v305, appended): S*N with D4GS_ANTIALIASED, else 0 */
 } D4gsSizes;
 D4GS_API int d4gs_query_sizes(const D4gsDims *dims, D4gsSizes *sizes);
 
