@@ -134,7 +134,12 @@ static int check_dims(const D4gsDims *d) {
     d4gs_set_error("dims is NULL");
     return D4GS_EINVAL;
   }
-  if (d->N < 0 || d->S <= 0 || d->width <= 0 || d->height <= 0 || d->D <= 0) {
+  // D == 0 is the depth-only render modes "D" / "ED" (the staged entry points): it needs a depth channel to composite
+  if (d->D == 0 && d->depth_mode == D4GS_DEPTH_NONE) {
+    d4gs_set_error("bad dims: D == 0 needs depth_mode D4GS_DEPTH_D or D4GS_DEPTH_ED (the depth-only render modes)");
+    return D4GS_EINVAL;
+  }
+  if (d->N < 0 || d->S <= 0 || d->width <= 0 || d->height <= 0 || d->D < 0) {
     d4gs_set_error("bad dims N=%d S=%d W=%d H=%d D=%d", d->N, d->S, d->width, d->height, d->D);
     return D4GS_EINVAL;
   }
@@ -249,8 +254,8 @@ const char *d4gs_last_error(void) { return g_err; }
 int d4gs_project_fwd(const D4gsDims *dims, const D4gsProjIn *in, const D4gsProjOut *out, void *stream) {
   int rc = check_dims(dims);
   if (rc) return rc;
-  if (!in || !out || !in->means || !in->quats || !in->scales || !in->opacities || !in->colors || !in->viewmat ||
-      !in->Kmat) {
+  if (!in || !out || !in->means || !in->quats || !in->scales || !in->opacities || (dims->D > 0 && !in->colors) || !in->viewmat ||
+      !in->Kmat) {  // (D == 0: no colour table - colors and ctab may be NULL)
     d4gs_set_error("d4gs_project_fwd: NULL required input");
     return D4GS_EINVAL;
   }
@@ -271,7 +276,7 @@ int d4gs_project_fwd(const D4gsDims *dims, const D4gsProjIn *in, const D4gsProjO
 }
 
 static int check_binned(const char *who, const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect *isect) {
-  if (!proj || !isect || !proj->geom || !proj->ctab || !proj->depths || !proj->tile_rects || !proj->tiles_touched ||
+  if (!proj || !isect || !proj->geom || (dims->D > 0 && !proj->ctab) || !proj->depths || !proj->tile_rects || !proj->tiles_touched ||
       !proj->isect_offsets || !proj->tile_counts || !proj->tile_offsets || !proj->n_isect) {
     d4gs_set_error("%s: NULL projection buffer", who);
     return D4GS_EINVAL;
@@ -314,7 +319,8 @@ int d4gs_raster_bwd(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIse
   if (rc) return rc;
   if ((rc = check_binned("d4gs_raster_bwd", dims, proj, isect))) return rc;
   if (!r || !r->render_colors || !r->render_alphas || !r->last_ids || !r->final_T || !g || !g->v_render_colors ||
-      !g->isect_grad || !g->isect_live || !g->v_means2d || !g->v_conics || !g->v_depths || !g->v_opac_act || !g->v_ctab) {
+      !g->isect_grad || !g->isect_live || !g->v_means2d || !g->v_conics || !g->v_depths || !g->v_opac_act ||
+      (dims->D > 0 && !g->v_ctab)) {  // (D == 0: no colour table, v_ctab may be NULL)
     d4gs_set_error("d4gs_raster_bwd: NULL forward state or gradient buffer");
     return D4GS_EINVAL;
   }
@@ -340,10 +346,11 @@ int d4gs_project_bwd(const D4gsDims *dims, const D4gsProjIn *in, const D4gsProjO
                      const D4gsLeafGrads *grads, void *stream) {
   int rc = check_dims(dims);
   if (rc) return rc;
-  if (!in || !proj || !grads || !in->means || !in->quats || !in->scales || !in->opacities || !in->colors || !in->viewmat ||
-      !in->Kmat || !proj->radii || !proj->conics || !proj->ctab || !proj->opac_act || !v_means2d || !v_conics ||
-      !v_depths || !v_opac_act || !v_ctab || !grads->v_means || !grads->v_quats || !grads->v_scales ||
-      !grads->v_opacities || !grads->v_colors || !grads->partials) {
+  const bool col = dims->D > 0;  // (D == 0: no colour table - colors, ctab, v_ctab and v_colors may be NULL)
+  if (!in || !proj || !grads || !in->means || !in->quats || !in->scales || !in->opacities || (col && !in->colors) || !in->viewmat ||
+      !in->Kmat || !proj->radii || !proj->conics || (col && !proj->ctab) || !proj->opac_act || !v_means2d || !v_conics ||
+      !v_depths || !v_opac_act || (col && !v_ctab) || !grads->v_means || !grads->v_quats || !grads->v_scales ||
+      !grads->v_opacities || (col && !grads->v_colors) || !grads->partials) {
     d4gs_set_error("d4gs_project_bwd: NULL required buffer");
     return D4GS_EINVAL;
   }

@@ -75,11 +75,18 @@ FrameBufs carve(const D4gsDims *d, int64_t cap, void *ws) {
   return b;
 }
 
+// D == 0 (the depth-only render modes) is a case of the staged entry points only (include/d4gs.h)
+int frame_refuses_depth_only(const char *who) {
+  d4gs_set_error("%s: D == 0 (depth-only render) is not supported by the one-call frame; use the staged entry points", who);
+  return D4GS_EINVAL;
+}
+
 int check_frame(const char *who, const D4gsDims *d, const D4gsProjIn *in, const D4gsFrameIO *io, void *ws, size_t ws_bytes,
                 int64_t cap, bool forward_only = false) {
   D4gsSizes z;
   int rc = d4gs_query_sizes(d, &z);  // validates dims
   if (rc) return rc;
+  if (d->D == 0) return frame_refuses_depth_only(who);
   if (!in || !io || !ws || !io->renders || !io->alphas || !io->means2d || !io->radii || !io->n_isect ||
       (io->blended && !io->acc) || !in->means || !in->quats || !in->scales || !in->opacities || !in->colors || !in->viewmat ||
       !in->Kmat || (d->G > 0 && (!in->motion_coefs || !in->rots || !in->transls || !in->times)) || d->N == 0) {
@@ -112,12 +119,20 @@ extern "C" {
 size_t d4gs_frame_workspace_bytes(const D4gsDims *dims, int64_t isect_capacity) {
   D4gsSizes z;
   if (d4gs_query_sizes(dims, &z)) return 0;
+  if (dims->D == 0) {
+    frame_refuses_depth_only("d4gs_frame_workspace_bytes");
+    return 0;
+  }
   return carve(dims, isect_capacity, nullptr).bytes;
 }
 
 size_t d4gs_frame_workspace_bytes_fwd(const D4gsDims *dims, int64_t isect_capacity) {
   D4gsSizes z;
   if (d4gs_query_sizes(dims, &z)) return 0;
+  if (dims->D == 0) {
+    frame_refuses_depth_only("d4gs_frame_workspace_bytes_fwd");
+    return 0;
+  }
   return carve(dims, isect_capacity, nullptr).fwd_bytes;
 }
 

@@ -106,6 +106,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // their own (the row[RV] call, and so the existing rows' summation trees, stay as they are).  isect_grad rows grow by two floats,
 // [6 moments | NCH channels | |dL/dx| | |dL/dy|]; in the slab the two sums sit behind everything else (column AB, AB + 1; AB + 2
 // takes wave_sum_store's spare writes).
+// D = 0 (with DEPTH): the depth-only render modes "D" / "ED".  No colour record is staged; the one channel is the depth of the geometry
+// record (g0.w), and a replayed pair's row is the 6 moments + the depth: R = 7 (9 with ABS), reduced by wave_sum_store's packed ladder.
 template <int D, bool DEPTH, bool SEG = false, bool ABS = false>
 __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
 #pragma clang fp contract(off)
@@ -141,7 +143,7 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
   __shared__ float4 sg0[NB];
   __shared__ float4 sg1[NB];
   __shared__ typename std::conditional<W4, uint2, float4>::type sbox[NB];  // W4: 4 x f16, tile-local (the forward's pack_box)
-  __shared__ float4 scol[NB * DV];
+  __shared__ float4 scol[NB * (DV > 0 ? DV : 1)];  // (D = 0: never referenced, so never allocated)
   __shared__ __attribute__((aligned(16))) float sgrad[4 * NB * RP];
   __shared__ int shi[4];
 
@@ -591,7 +593,7 @@ __global__ void __launch_bounds__(SLOTS * 64) k_gather(const GatherArgsT<AA> a) 
   float *mine = stage + wv * GATHER_ROWS * R;
   uint32_t *mylive32 = slive + (SPARSE ? wv * 64 : 0);
   const uint8_t *mylive = reinterpret_cast<const uint8_t *>(mylive32);
-  float vo = 0.f, vc[D];
+  float vo = 0.f, vc[D > 0 ? D : 1];  // (D = 0, the depth-only kernels: no colour gradients, no v_ctab)
 #pragma unroll
   for (int c = 0; c < D; c++) vc[c] = 0.f;
   // densification statistics of this Gaussian, accumulated over the sub-samples in order (k_control_stats' arithmetic)
@@ -867,21 +869,23 @@ int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, const GatherAA &gaa, int64_t n_
 #ifdef D4GS_VARIANTS  // the A/B build only (tests/libd4gs_variants.so): environment-selected reference variants, dense rows
   static const bool wave_per_tile = getenv("D4GS_BWD_WAVE_PER_TILE") != nullptr;  // variant A
   static const bool use_mfma = getenv("D4GS_BWD_MFMA") != nullptr;                // variant C
-  if (!ABS && (wave_per_tile || use_mfma)) {
-    constexpr int R = 6 + D + (DEPTH ? 1 : 0);
-    a.sparse = ga.sparse = 0;
-    if (wave_per_tile) {  // variant A relies on a zeroed buffer
-      hipError_t e = hipMemsetAsync(a.isect_grad, 0, sizeof(float) * (size_t)R * (size_t)(n_isect > 0 ? n_isect : 1), stream);
-      if (e != hipSuccess) {
-        d4gs_set_error("hipMemsetAsync(isect_grad): %s", hipGetErrorString(e));
-        return D4GS_ELAUNCH;
+  if constexpr (D > 0) {  // (no depth-only reference variants: the default kernels serve D = 0)
+    if (!ABS && (wave_per_tile || use_mfma)) {
+      constexpr int R = 6 + D + (DEPTH ? 1 : 0);
+      a.sparse = ga.sparse = 0;
+      if (wave_per_tile) {  // variant A relies on a zeroed buffer
+        hipError_t e = hipMemsetAsync(a.isect_grad, 0, sizeof(float) * (size_t)R * (size_t)(n_isect > 0 ? n_isect : 1), stream);
+        if (e != hipSuccess) {
+          d4gs_set_error("hipMemsetAsync(isect_grad): %s", hipGetErrorString(e));
+          return D4GS_ELAUNCH;
+        }
       }
+      if (n_isect > 0) {
+        if (wave_per_tile) D4GS_LAUNCH("k_raster_bwd", (k_raster_bwd<D, DEPTH>), dim3(blocks), dim3(64), 0, stream, a);
+        else D4GS_LAUNCH("k_raster_bwd_m", (k_raster_bwd_m<D, DEPTH>), dim3(blocks), dim3(256), 0, stream, a);
+      }
+      launched = true;
     }
-    if (n_isect > 0) {
-      if (wave_per_tile) D4GS_LAUNCH("k_raster_bwd", (k_raster_bwd<D, DEPTH>), dim3(blocks), dim3(64), 0, stream, a);
-      else D4GS_LAUNCH("k_raster_bwd_m", (k_raster_bwd_m<D, DEPTH>), dim3(blocks), dim3(256), 0, stream, a);
-    }
-    launched = true;
   }
 #endif
   if (!launched) {
@@ -978,6 +982,10 @@ int d4gs_raster_bwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   case DD:            \
     return dep ? D4GS_LB(DD, true) : D4GS_LB(DD, false);
   switch (dims->D) {
+    case 0:  // depth-only render modes "D" / "ED": no colour table, no v_ctab (the C API admits D = 0 with a depth mode only)
+      if (dep) return D4GS_LB(0, true);
+      d4gs_set_error("D = 0 needs a depth mode (the depth-only composite)");
+      return D4GS_EINVAL;
     D4GS_CASE(1)
     D4GS_CASE(2)
     D4GS_CASE(3)

@@ -100,6 +100,8 @@ __device__ __forceinline__ int d4gs_byte_x16(uint32_t w) {
   return r;
 }
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+// D = 0 (with DEPTH): the depth-only render modes "D" / "ED".  A batch stages the geometry record and the box only - no colour row,
+// no colour accumulators - and the one channel composites the record's depth (g0.w); the narrow kernels' loop and null record.
 template <int D, bool DEPTH, bool SEG = false>
 __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
 #pragma clang fp contract(off)
@@ -131,13 +133,13 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
 #ifndef D4GS_FWD_WIDE4
 #define D4GS_FWD_WIDE4 1  // the matrix-pipe kernel also takes the four-steps-per-read loop and the null record (round 6)
 #endif
-  constexpr bool LIKE_NARROW = DV == 1 || (MF && D4GS_FWD_WIDE4);
+  constexpr bool LIKE_NARROW = DV <= 1 || (MF && D4GS_FWD_WIDE4);  // (DV = 0: the depth-only kernels, no colour record at all)
   constexpr bool NULL0 = D4GS_FWD_NULL0 && LIKE_NARROW && !SEG;
   constexpr int FBE = NULL0 ? FB - 1 : FB;  // splats per batch
   __shared__ float4 sg0[FB];
   __shared__ float4 sg1[FB];
   __shared__ typename BoxT<(DV <= 1)>::type sbox[FB];  // tight box in tile-local pixels
-  __shared__ float4 scol[FB * DV];
+  __shared__ float4 scol[FB * (DV > 0 ? DV : 1)];  // (D = 0: never referenced, so never allocated)
   __shared__ __attribute__((aligned(16))) unsigned char slist[4 * 4 * FB];  // [wave][row][position]
 
   D4GS_TCLK(_t0)
@@ -474,13 +476,15 @@ int launch_fwd(const RasterFwdArgs &a, hipStream_t stream) {
 #ifdef D4GS_VARIANTS  // the A/B build only (tests/libd4gs_variants.so): environment-selected reference variants
   static const bool wave_per_tile = getenv("D4GS_FWD_WAVE_PER_TILE") != nullptr;  // variant A
   static const bool quads = getenv("D4GS_FWD_QUADS") != nullptr;                  // variant B
-  if (wave_per_tile) {
-    D4GS_LAUNCH("k_raster_fwd", (k_raster_fwd<D, DEPTH>), dim3(blocks), dim3(64), 0, stream, a);
-    return d4gs_check_launch("k_raster_fwd");
-  }
-  if (quads) {
-    D4GS_LAUNCH("k_raster_fwd_q", (k_raster_fwd_q<D, DEPTH>), dim3(blocks), dim3(256), 0, stream, a);
-    return d4gs_check_launch("k_raster_fwd_q");
+  if constexpr (D > 0) {  // (the reference variants have no depth-only instantiation: the default kernel below serves it)
+    if (wave_per_tile) {
+      D4GS_LAUNCH("k_raster_fwd", (k_raster_fwd<D, DEPTH>), dim3(blocks), dim3(64), 0, stream, a);
+      return d4gs_check_launch("k_raster_fwd");
+    }
+    if (quads) {
+      D4GS_LAUNCH("k_raster_fwd_q", (k_raster_fwd_q<D, DEPTH>), dim3(blocks), dim3(256), 0, stream, a);
+      return d4gs_check_launch("k_raster_fwd_q");
+    }
   }
 #endif
   if (a.seg_state) {
@@ -549,6 +553,10 @@ int d4gs_raster_fwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   case DD:                                                              \
     return dep ? launch_fwd<DD, true>(aa, stream) : launch_fwd<DD, false>(aa, stream);
     switch (dims->D) {
+      case 0:  // depth-only render modes "D" / "ED": no colour table (the C API admits D = 0 with a depth mode only)
+        if (dep) return launch_fwd<0, true>(aa, stream);
+        d4gs_set_error("D = 0 needs a depth mode (the depth-only composite)");
+        return D4GS_EINVAL;
       D4GS_CASE(1)
       D4GS_CASE(2)
       D4GS_CASE(3)

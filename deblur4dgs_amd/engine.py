@@ -67,6 +67,8 @@ class RenderCfg:
     #                                  render by `resolve_lazy` (D4GS_LAZY_SORT=auto, the default: on when the previous render of the
     #                                  shape measured < 50 % live rows and lists of >= 1000 keys on average)
     near_target: int = 0  # keys the near part of a list is aimed at (0: the library's 1024)
+    depth_only: bool = False  # with D == 0 and a depth mode: gsplat's render modes "D" / "ED" through the depth-only composite kernels (no
+    #                           colour table, one channel).  False: render_instances' older D == 0 route, one zero colour channel on the D = 1 kernels
     exact_tiles: bool | None = None  # D4GS_EXACT_TILES (include/d4gs.h): bin a splat only into the tiles of its tight rectangle that its
     #                                  alpha >= 1/255 ellipse reaches.  Same image and gradients bit for bit, shorter lists; the test costs the
     #                                  projection ~1 instruction per candidate pair and lane, so None (D4GS_EXACT_TILES=auto) turns it on from
@@ -1014,7 +1016,7 @@ def render_instances(cfg: RenderCfg, means, quats, scales, opacities, colors, mo
                      viewmat, Kmat, background):
     """Deform + project + bin + sort + composite all S sub-samples.
     -> render_colors [S,H,W,D'], render_alphas [S,H,W,1], means2d [S,N,2], radii int32 [S,N], state."""
-    drop0 = cfg.D == 0  # e.g. return_color=False with depth only (scene_model.py:221-225): carry one zero channel
+    drop0 = cfg.D == 0 and not cfg.depth_only  # e.g. return_color=False with depth only (scene_model.py:221-225): carry one zero channel
     if drop0:
         colors = torch.zeros(cfg.N, 1, dtype=torch.float32, device=means.device)
         background = None if background is None else torch.zeros(1, dtype=torch.float32, device=means.device)
@@ -1022,6 +1024,10 @@ def render_instances(cfg: RenderCfg, means, quats, scales, opacities, colors, mo
         rc, ra, m2d, radii, st = render_instances(cfg, means, quats, scales, opacities, colors, motion_coefs, rots,
                                                   transls, times, RTs, viewmat, Kmat, background)
         return rc[..., 1:], ra, m2d, radii, st
+    if cfg.D == 0:  # depth only: no colour table - the colours, if any, are neither read nor differentiated (gsplat discards them)
+        if cfg.depth_mode == L.DEPTH_NONE:
+            raise ValueError("RenderCfg.depth_only needs a depth mode (DEPTH_D or DEPTH_ED)")
+        colors = background = None
     resolve_lazy(cfg, means.device)
     st = State(cfg)
     if cfg.N == 0:  # an empty scene (e.g. everything culled): the image is the background, nothing to launch
@@ -1041,6 +1047,9 @@ def render_instances(cfg: RenderCfg, means, quats, scales, opacities, colors, mo
                 torch.zeros(S, 0, dtype=torch.int32, device=dev), st)
     means2d, conics, depths, opac_act, ctab, radii = ProjectFn.apply(
         st, means, quats, scales, opacities, colors, motion_coefs, rots, transls, times, RTs, viewmat, Kmat)
+    if cfg.D == 0:  # depth only (cfg.depth_only): the depth-only kernels, no colour table
+        rc, ra = RasterFn.apply(st, cfg, means2d, conics, depths, opac_act, ctab, background)
+        return rc, ra, means2d, radii, st
     chunks = channel_chunks(cfg.D)
     if len(chunks) == 1 and chunks[0][2] == cfg.D:  # the common case: one kernel width, nothing to slice or pad
         rc, ra = RasterFn.apply(st, cfg, means2d, conics, depths, opac_act, ctab, background)

@@ -2,7 +2,11 @@
 (flow3d/scene_model.py:360-373: packed=False, C=1, render_mode in {"RGB","RGB+ED"}).
 
 Same argument names / meaning / return triple as gsplat 1.1.1:
-    render_colors [C,H,W,D(+1)], render_alphas [C,H,W,1], info
+    render_colors [C,H,W,D(+1)] ([C,H,W,1] in the depth-only modes), render_alphas [C,H,W,1], info
+render_mode: "RGB", "RGB+D", "RGB+ED", and the depth-only "D" / "ED" - the composited depth (ED: divided by max(alpha, 1e-10)), as
+gsplat computes it with colors := depths[:, None] and a zero background.  Those two run the depth-only kernels (no colour table, one
+channel); `colors` is validated as in the other modes but never composited (no SH evaluation, `colors.grad` stays None) and
+`backgrounds` is ignored.
 `info["means2d"]` is an autograd intermediate ([C,N,2], pixel units) on which callers may `.retain_grad()`;
 `info["radii"]` is int32 [C,N], > 0 <=> visible.
 
@@ -26,7 +30,8 @@ from . import engine
 from .engine import RenderCfg, render_instances
 from .sh import sh_colors, spherical_harmonics  # noqa: F401  (re-exported: gsplat.rendering's companion)
 
-_MODES = {"RGB": L.DEPTH_NONE, "RGB+ED": L.DEPTH_ED, "RGB+D": L.DEPTH_D}
+_MODES = {"RGB": L.DEPTH_NONE, "RGB+ED": L.DEPTH_ED, "RGB+D": L.DEPTH_D, "ED": L.DEPTH_ED, "D": L.DEPTH_D}
+_DEPTH_ONLY = ("D", "ED")
 
 
 def rasterization(
@@ -65,7 +70,8 @@ def rasterization(
     if packed or sparse_grad or tile_size != 16:
         raise NotImplementedError("only packed=False, sparse_grad=False and tile_size=16 are implemented")
     if render_mode not in _MODES:
-        raise ValueError(f"render_mode {render_mode!r} not supported (RGB, RGB+ED, RGB+D)")
+        raise ValueError(f"render_mode {render_mode!r} not supported (RGB, RGB+ED, RGB+D, D, ED)")
+    depth_only = render_mode in _DEPTH_ONLY
     N = means.shape[0]
     if sh_degree is not None:
         d = int(sh_degree)
@@ -81,20 +87,25 @@ def rasterization(
             raise ValueError(f"sh_degree {d} needs K >= {(d + 1) ** 2} coefficients, got K = {colors.shape[1]}")
         # gsplat masks the evaluation with radii > 0.  Unmasked here: a Gaussian that mask would drop is in no tile list,
         # so its colour is never read and its v_rgb is 0 - outputs and gradients equal the masked evaluation's, and the
-        # colours need not wait for the projection.
-        colors = sh_colors(means, viewmats[0], colors, d)
+        # colours need not wait for the projection.  (Depth-only modes: nothing reads the colours, nothing is evaluated.)
+        if not depth_only:
+            colors = sh_colors(means, viewmats[0], colors, d)
     assert quats.shape == (N, 4) and scales.shape == (N, 3) and opacities.shape == (N,) and colors.shape[0] == N
-    bg = None if backgrounds is None else backgrounds[0]
+    bg = None if backgrounds is None or depth_only else backgrounds[0]
+    D = colors.shape[-1]
+    if depth_only:  # the depth-only kernels: no colour table, the colours are not composited (gsplat discards them)
+        colors, D = None, 0
     # any channel count: the engine composites it in chunks of <= 16 channels over one projection / one set of sorted
     # tile lists (engine.channel_chunks), like gsplat's `channel_chunk`
     if lazy_sort is None:  # `info["flatten_ids"]` is part of this seam: lazy lists (unsorted behind a tile's last contributor) only on request
         lazy_sort = engine.LAZY_SORT == "1"
     if exact_tiles is None:  # likewise `tiles_per_gauss` / the lists: the per-tile ellipse test only on request (or D4GS_EXACT_TILES=1)
         exact_tiles = engine.EXACT_TILES == "1"
-    cfg = RenderCfg(N=N, G=0, K=0, T=0, S=1, D=colors.shape[-1], width=width, height=height,
+    cfg = RenderCfg(N=N, G=0, K=0, T=0, S=1, D=D, width=width, height=height,
                     depth_mode=_MODES[render_mode], flags=0, near_plane=near_plane, far_plane=far_plane, eps2d=eps2d,
                     radius_clip=radius_clip, exact_cull=exact_cull, lazy_sort=lazy_sort, near_target=near_target,
-                    exact_tiles=exact_tiles, absgrad=bool(absgrad), antialiased=rasterize_mode == "antialiased")
+                    exact_tiles=exact_tiles, absgrad=bool(absgrad), antialiased=rasterize_mode == "antialiased",
+                    depth_only=depth_only)
     rc, ra, means2d, radii, st = render_instances(cfg, means, quats, scales, opacities, colors, None, None, None,
                                                   None, None, viewmats[0], Ks[0], bg)
     tw, th = cfg.tiles

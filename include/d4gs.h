@@ -82,6 +82,12 @@ enum { /* D4gsDims.flags */
 };
 
 enum { D4GS_DEPTH_NONE = 0, D4GS_DEPTH_ED = 1, D4GS_DEPTH_D = 2 }; /* render_mode RGB / RGB+ED / RGB+D */
+/* Depth-only renders (v305): D4gsDims.D == 0 with depth_mode D4GS_DEPTH_D or D4GS_DEPTH_ED is gsplat's render_mode "D" / "ED" - one
+ * channel, the composited depth (ED: divided by max(alpha, 1e-10)), no background.  d4gs_query_sizes (ctab 0, isect_grad_row 7, or 9
+ * with D4GS_ABSGRAD), d4gs_project_fwd (no colour table is written: in->colors and out->ctab may be NULL), d4gs_bin_sort,
+ * d4gs_raster_fwd, d4gs_raster_bwd (v_ctab may be NULL) and d4gs_project_bwd (colors, ctab, v_ctab and v_colors may be NULL) take it.
+ * D == 0 with D4GS_DEPTH_NONE, and D == 0 passed to d4gs_forward / d4gs_backward / d4gs_frame_workspace_bytes(_fwd), are D4GS_EINVAL
+ * (the workspace queries return 0). */
 /* D4gsRasterGrads.row_mode.  DENSE: every row of isect_grad is written (rows behind a tile's last contributor zero-filled);
  * SPARSE: only replayed rows are written and flagged in isect_live (large-footprint / occluded scenes).  Same gradients, bitwise. */
 enum { D4GS_ROWS_AUTO = 0, D4GS_ROWS_DENSE = 1, D4GS_ROWS_SPARSE = 2 };
@@ -92,7 +98,7 @@ typedef struct D4gsDims {
   int32_t K;          /* motion bases */
   int32_t T;          /* frames per basis */
   int32_t S;          /* exposure sub-samples in this call */
-  int32_t D;          /* colour channels supplied by the caller (without the depth channel) */
+  int32_t D;          /* colour channels supplied by the caller (without the depth channel); 0: a depth-only render (see above) */
   int32_t width, height;
   int32_t depth_mode; /* D4GS_DEPTH_* ; channels rendered = D + (depth_mode != 0) */
   int32_t flags;      /* D4GS_RAW_* */
