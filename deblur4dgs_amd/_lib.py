@@ -97,10 +97,16 @@ class Poses(C.Structure):
     _fields_ = [("means", F), ("quats", F), ("transforms", F), ("g_major", C.c_int32)]
 
 
+class AdamRec(C.Structure):
+    _fields_ = [(n, F) for n in ("param", "grad", "exp_avg", "exp_avg_sq", "step")] + [("n", C.c_int64)] + \
+               [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps")]
+
+
 RAW_PARAMS, RAW_COLORS, EXACT_CULL, LAZY_SORT, EXACT_TILES, ABSGRAD, ANTIALIASED = 1, 2, 4, 8, 16, 32, 64
 DEPTH_NONE, DEPTH_ED, DEPTH_D = 0, 1, 2
 ROWS_AUTO, ROWS_DENSE, ROWS_SPARSE = 0, 1, 2
 TILE = 16
+ADAM_CHUNK = 2048  # D4GS_ADAM_CHUNK
 VERSION = 305  # D4GS_VERSION of include/d4gs.h
 GEOM_STRIDE = 8
 
@@ -111,6 +117,7 @@ EXPORTS = (
     "d4gs_blend_shard_winner", "d4gs_blend_shard_bwd", "d4gs_control_stats", "d4gs_control_plan", "d4gs_gather_rows", "d4gs_camera_path_fwd", "d4gs_camera_path_bwd",
     "d4gs_pose_encode", "d4gs_pose_encode_bwd", "d4gs_move_model_fwd", "d4gs_move_model_bwd",
     "d4gs_photometric_blocks", "d4gs_photometric_fwd", "d4gs_photometric_bwd", "d4gs_sh_partials_elems", "d4gs_sh_fwd", "d4gs_sh_bwd", "d4gs_query_sizes", "d4gs_profile_enable", "d4gs_profile_collect", "d4gs_measure_peaks",
+    "d4gs_adam_blocks", "d4gs_adam_step", "d4gs_adam_set_grads", "d4gs_adam_step_cpu",
 )
 
 _lib = None
@@ -183,6 +190,11 @@ def lib() -> C.CDLL:
         L.d4gs_sh_bwd.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.d4gs_blend_fwd.argtypes = [C.c_int32, C.c_int64, C.c_int32, P(C.c_int32), vp, vp, vp, vp, vp]
         L.d4gs_blend_bwd.argtypes = [C.c_int32, C.c_int64, C.c_int32, P(C.c_int32), vp, vp, vp, vp, vp, vp, vp]
+        L.d4gs_adam_blocks.argtypes = [C.c_int64]
+        L.d4gs_adam_blocks.restype = C.c_int64
+        L.d4gs_adam_step.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp]
+        L.d4gs_adam_set_grads.argtypes = [vp, C.c_int32, P(vp), vp]
+        L.d4gs_adam_step_cpu.argtypes = [P(AdamRec), C.c_int32]
         if L.d4gs_version() != VERSION:
             raise RuntimeError(f"libd4gs.so version {L.d4gs_version()} != {VERSION} (stale build?)")
         _lib = L

@@ -38,24 +38,34 @@ def build(n_fg=40_000, n_bg=100_000, K=20, W=512, H=288, dev="cuda:0", seed=0):
 
 
 def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, fused_stats=True, deferred=True,
-          graph=False, **kw):
+          graph=False, hip_adam=False, seed=0, step_events=None, **kw):
     """fused_stats: the densification statistics come out of the rasterizer's backward (attach_control_stats) instead
     of a pass over `_current_xys[i].grad`; deferred: no render waits for its intersection count on the host
     (`deferred_size_check`), the counts are verified once per step; graph: the three renders, the loss and the whole
     backward of a step are captured ONCE in a HIP graph (after two eager warm-up steps) and replayed - the step is then
-    one hipGraphLaunch plus the optimizers (re-captured whenever a control step changes N)."""
+    one hipGraphLaunch plus the optimizers (re-captured whenever a control step changes N); hip_adam: the per-tensor optimizers
+    are handles of one `deblur4dgs_amd.optim.AdamGroup` - one HIP launch steps them all, and with graph=True that launch is
+    captured behind the backward, so the whole step, optimizers included, is the one hipGraphLaunch.  seed: the synthetic
+    scene (its targets: seed + 1); step_events: a list that receives one timing event per step, recorded where the step
+    begins (per-step times without a host sync: scripts/bench_adam.py)."""
     assert not graph or (fused_stats and deferred), "graph capture needs the sync-free step"
-    model, sc = build(W=W, H=H, dev=dev, **kw)
+    model, sc = build(W=W, H=H, dev=dev, seed=seed, **kw)
     model.deferred_size_check = bool(deferred)
     w2c, K = sc["viewmat"][None].to(dev), sc["K"][None].to(dev)
     # targets: renders of a perturbed copy of the scene (so the loss has something to fit)
     with torch.no_grad():
-        tgt_model, _ = build(W=W, H=H, dev=dev, seed=1, **kw)
+        tgt_model, _ = build(W=W, H=H, dev=dev, seed=seed + 1, **kw)
         tgt_dyn = tgt_model.render(3, w2c, K, (W, H), mode="blury")["img"]
         tgt_sta = tgt_model.render(3, w2c, K, (W, H), bg_only=True, mode="blury")["img"]
     # (torch's fused Adam faults the GPU when its gradients live in a CUDA-graph memory pool - scripts/graph_bisect.py;
     # the graph mode therefore uses the plain implementation)
     adam = lambda p, lr: torch.optim.Adam([p], lr=lr, fused=p.is_cuda and not graph)
+    group = None
+    if hip_adam:  # the same optimizers (one torch.optim.Adam subclass per tensor, same keys), stepped together by one kernel
+        from deblur4dgs_amd.optim import AdamGroup
+
+        group = AdamGroup()
+        adam = group.adam
     lrs = {"means": 1.6e-4, "colors": 1e-2, "opacities": 1e-2, "scales": 5e-3, "quats": 5e-3, "motion_coefs": 5e-3}
     # one Adam per tensor, keyed like the reference's Trainer.optimizers (trainer.py:1168-1196): the control steps
     # re-key them when rows are added / removed
@@ -92,6 +102,9 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
         if it == warm:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
+        if step_events is not None:
+            step_events.append(torch.cuda.Event(enable_timing=True))
+            step_events[-1].record()
         if captured is not None:
             # a replayed graph keeps the list capacities of its capture: the counts of the PREVIOUS replay (copied to pinned
             # memory by nodes of the graph itself) are looked at before the next one - an overflowed replay rendered nothing,
@@ -108,8 +121,12 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
             g_, watch = torch.cuda.CUDAGraph(), engine.GraphWatch()
             with watch.capturing(), torch.cuda.graph(g_):
                 loss_static, _ = fwd_bwd()
+                if group is not None:
+                    group.step()  # reads lr and step counts from its device table: valid at every replay
             captured = (g_, loss_static, watch)
         if captured is not None:
+            if group is not None:
+                group.sync()  # an lr a scheduler moved since the last step reaches the device table (no-op otherwise)
             captured[0].replay()  # gradients land in the same .grad tensors every step
             captured[2].replayed()
             loss, side = captured[1], None
@@ -119,8 +136,11 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
             loss, side = fwd_bwd()
             eager_since_capture += 1
         xys2, radii2, wh2 = side if side is not None else (None, None, None)
-        for o in opts():
-            o.step()
+        if group is None:
+            for o in opts():
+                o.step()
+        elif captured is None:  # (a replayed graph has stepped them already)
+            group.step()
         if not fused_stats:
             model._current_xys, model._current_radii, model._current_img_wh = xys2, radii2, wh2
             accumulate_from_model(stats, model, batch_size=1)
@@ -159,5 +179,6 @@ if __name__ == "__main__":
     ap.add_argument("--control-every", type=int, default=0, help="densify + cull every N steps (0: never)")
     ap.add_argument("--round1", action="store_true", help="statistics as a separate pass, host waits for every list size")
     ap.add_argument("--graph", action="store_true", help="replay the step's renders + loss + backward from a HIP graph")
+    ap.add_argument("--hip-adam", action="store_true", help="step every optimizer with one HIP launch (inside the graph with --graph)")
     a = ap.parse_args()
-    train(a.steps, control_every=a.control_every, fused_stats=not a.round1, deferred=not a.round1, graph=a.graph)
+    train(a.steps, control_every=a.control_every, fused_stats=not a.round1, deferred=not a.round1, graph=a.graph, hip_adam=a.hip_adam)

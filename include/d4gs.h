@@ -533,6 +533,47 @@ D4GS_API int d4gs_blend_shard_winner(const D4gsShardBlend *b, const float *rende
 D4GS_API int d4gs_blend_shard_bwd(const D4gsShardBlend *b, const float *v_out, const float *v_acc /* or NULL */, const int32_t *win,
                          float *v_renders /* [S_local,P,C] */, float *v_alphas /* [S_local,P] */, void *stream);
 
+/* Multi-tensor Adam (appended; D4GS_VERSION unchanged): ONE launch updates every tensor of a table that lives in DEVICE memory,
+ * so a launch captured in a HIP graph stays valid when the host refreshes an lr (or any other field) in the table between replays.
+ * torch.optim.Adam with default flags (no amsgrad, no weight decay, no maximize), fp32 tensors, per record with t = step + 1:
+ *   m += (g - m) (1 - beta1);  v = beta2 v + (1 - beta2) g g;  p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * The four scalars are doubles, as torch holds them: 1 - beta1, 1 - beta2 and the two bias corrections are formed in fp64 (on the
+ * device, once per workgroup) and rounded to fp32 once; every per-element operation is one correctly rounded fp32 operation, with
+ * no contraction, in the order torch's single-tensor path applies them.
+ * A record whose `grad` is NULL is skipped: nothing of it is written and its step does not advance (torch skips `grad is None`).
+ * Workgroup b of the launch serves chunk (b - block_prefix[r]) - D4GS_ADAM_CHUNK elements - of the record r with
+ * block_prefix[r] <= b < block_prefix[r + 1]; a record has d4gs_adam_blocks(n) = max(1, ceil(n / D4GS_ADAM_CHUNK)) workgroups,
+ * so block_prefix [n_records + 1] is the running sum of those counts and n_blocks = block_prefix[n_records].  16-byte loads and
+ * stores when the four bases of a record are 16-byte aligned (the n % 4 tail as dwords), dwords otherwise.  No atomics and no
+ * cross-workgroup traffic: bitwise reproducible.  That is also why the step count is kept once per WORKGROUP: block_steps
+ * [n_blocks] (float, like torch's `step`) holds each workgroup's own copy of its record's count - it reads, increments and
+ * writes back only that word, and chunk 0 also stores the new count to `*step` for the host to see.  Whoever builds the table
+ * seeds block_steps[b] with the `*step` of b's record (and seeds it again after changing `*step` from outside). */
+#define D4GS_ADAM_CHUNK 2048
+typedef struct D4gsAdamRec {
+  float *param;              /* [n] */
+  const float *grad;         /* [n] or NULL: the record is skipped */
+  float *exp_avg;            /* [n] m */
+  float *exp_avg_sq;         /* [n] v */
+  float *step;               /* [1] the step count torch keeps in state["step"] (fp32) */
+  int64_t n;
+  double lr, beta1, beta2, eps;
+} D4gsAdamRec;
+D4GS_API int64_t d4gs_adam_blocks(int64_t n);
+/* table [n_records], block_prefix [n_records + 1] and block_steps [n_blocks]: device memory (table 8-byte, the others 4-byte
+ * aligned).  n_records == 0 launches nothing.  D4GS_EINVAL for a NULL or misaligned argument or a negative count; what the
+ * records hold cannot be checked from the host - the kernel itself never touches an element at or beyond `n`. */
+D4GS_API int d4gs_adam_step(const D4gsAdamRec *table, int32_t n_records, const int32_t *block_prefix, int32_t n_blocks,
+                            float *block_steps, void *stream);
+/* table[r].grad = grads[r] for r < n_records, by kernels that carry the pointers as ARGUMENTS (64 per launch): the one way to
+ * point a device table at gradient tensors that were born inside a stream capture - a captured copy from host memory would be
+ * read again at every replay.  grads [host] [n_records]. */
+D4GS_API int d4gs_adam_set_grads(D4gsAdamRec *table, int32_t n_records, const float *const *grads, void *stream);
+/* CPU twin: the same per-element function on HOST pointers (table and everything it points to), one thread, no stream, no block
+ * tables (t = *step + 1).  Never a fallback.  Validates every record: D4GS_EINVAL for a NULL param / exp_avg / exp_avg_sq /
+ * step, a pointer that is not 4-byte aligned, or n < 0. */
+D4GS_API int d4gs_adam_step_cpu(const D4gsAdamRec *table, int32_t n_records);
+
 #ifdef __cplusplus
 }
 #endif
