@@ -118,6 +118,8 @@ EXPORTS = (
     "d4gs_pose_encode", "d4gs_pose_encode_bwd", "d4gs_move_model_fwd", "d4gs_move_model_bwd",
     "d4gs_photometric_blocks", "d4gs_photometric_fwd", "d4gs_photometric_bwd", "d4gs_sh_partials_elems", "d4gs_sh_fwd", "d4gs_sh_bwd", "d4gs_query_sizes", "d4gs_profile_enable", "d4gs_profile_collect", "d4gs_measure_peaks",
     "d4gs_adam_blocks", "d4gs_adam_step", "d4gs_adam_set_grads", "d4gs_adam_step_cpu",
+    "d4gs_trimmed_scratch_words", "d4gs_masked_l1_fwd", "d4gs_masked_l1_bwd", "d4gs_trimmed_l1_fwd", "d4gs_trimmed_l1_bwd",
+    "d4gs_gradient_loss_fwd", "d4gs_gradient_loss_bwd",
 )
 
 _lib = None
@@ -195,6 +197,14 @@ def lib() -> C.CDLL:
         L.d4gs_adam_step.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp]
         L.d4gs_adam_set_grads.argtypes = [vp, C.c_int32, P(vp), vp]
         L.d4gs_adam_step_cpu.argtypes = [P(AdamRec), C.c_int32]
+        L.d4gs_trimmed_scratch_words.argtypes = [C.c_int64, C.c_int32]
+        L.d4gs_trimmed_scratch_words.restype = C.c_int64
+        L.d4gs_masked_l1_fwd.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_float, vp, C.c_int64, vp, vp]
+        L.d4gs_masked_l1_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp, vp]
+        L.d4gs_trimmed_l1_fwd.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_float, vp, C.c_int64, vp, vp]
+        L.d4gs_trimmed_l1_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp]
+        L.d4gs_gradient_loss_fwd.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.c_int64, vp, vp]
+        L.d4gs_gradient_loss_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
         if L.d4gs_version() != VERSION:
             raise RuntimeError(f"libd4gs.so version {L.d4gs_version()} != {VERSION} (stale build?)")
         _lib = L

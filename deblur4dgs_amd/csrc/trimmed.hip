@@ -1,0 +1,450 @@
+// trimmed.hip -- the reference's quantile-trimmed losses (flow3d/loss_utils.py: masked_l1_loss, trimmed_l1_loss,
+// compute_gradient_loss) without a sort, a host read or a data-dependent launch (include/d4gs.h, "Trimmed losses").
+//
+// One value pass per mode writes the elements v >= 0 to scratch (the depth-gradient mode: two terms, one slot per pixel and term,
+// a slot without a valid pair holds TRIM_EMPTY and the valid ones are counted on the device).  Everything after it is the same for
+// every mode and runs once per term (blockIdx.y):
+//   4 x { k_trim_hist: LDS histogram of one 8-bit digit of the keys under the current prefix, merged into 256 global bins with
+//                      integer atomics;  k_trim_narrow: one block scans the bins and extends the prefix }
+// Non-negative floats order like their bit patterns, so after the four digits the prefix IS the order statistic.  torch.quantile
+// interpolates between the order statistics floor(r) and ceil(r): two prefixes are narrowed side by side (they share a histogram
+// until they part, after which the upper one is the minimum of its bin).  k_trim_sum then adds v * m, m and the count over v < t
+// into per-block partials and k_trim_finish adds those in a fixed order in double.  Integer adds commute and every float sum has a
+// fixed order: the same input gives the same bits on every run and every graph replay.
+//
+// LDS atomics on one address serialise, and a depth map puts every key of a wave into one bin of the first digit (often of the
+// first two), so a wave first peels off up to TRIM_PEEL groups of lanes that share a digit - one add of the group's size each - and
+// only the lanes left after that add one by one (keys spread over many bins, where lanes rarely meet).
+#include "common.h"
+
+namespace {
+
+constexpr int TB = 256;                      // threads per block, all kernels
+constexpr int TRIM_ITEMS = 8;                // elements per thread before the grid stops growing
+constexpr int TRIM_MAX_BLOCKS = 1024;        // 4 per CU; beyond that the data passes stride
+constexpr int TRIM_PEEL = 4;
+constexpr uint32_t TRIM_EMPTY = 0xFFFFFFFFu;  // a slot without an element: a NaN pattern, above every key, `v < t` false
+constexpr int TRIM_PASSES = 4;
+// control words per term (uint32): the state, then two 256-bin histograms (lower / upper order statistic)
+enum { C_COUNT = 0, C_PREFIX_LO, C_RANK_LO, C_PREFIX_HI, C_RANK_HI, C_FRAC, C_T, C_PAD, C_HIST, C_WORDS = C_HIST + 512 };
+constexpr int PARTIAL_DOUBLES = 3;  // sum v * m, sum m, count
+
+__host__ __device__ inline int64_t trim_blocks(int64_t n_max) {
+  const int64_t b = (n_max + (int64_t)TB * TRIM_ITEMS - 1) / ((int64_t)TB * TRIM_ITEMS);
+  return b < 1 ? 1 : (b > TRIM_MAX_BLOCKS ? TRIM_MAX_BLOCKS : b);
+}
+// scratch layout in 32-bit words: values [terms * n_max] (padded to even) | control [terms * C_WORDS] | partials (doubles)
+__host__ __device__ inline int64_t trim_ctrl_offset(int64_t n_max, int terms) { return ((int64_t)terms * n_max + 1) & ~(int64_t)1; }
+__host__ __device__ inline int64_t trim_partials_offset(int64_t n_max, int terms) {
+  return trim_ctrl_offset(n_max, terms) + (int64_t)terms * C_WORDS;
+}
+__host__ __device__ inline int64_t trim_scratch_words(int64_t n_max, int terms) {
+  return trim_partials_offset(n_max, terms) + 2 * (int64_t)terms * trim_blocks(n_max) * PARTIAL_DOUBLES;
+}
+
+__global__ void __launch_bounds__(TB) k_trim_init(uint32_t *ctrl, int terms, uint32_t count) {
+  for (int i = threadIdx.x; i < terms * C_WORDS; i += TB) ctrl[i] = (i % C_WORDS) == C_COUNT ? count : 0u;
+}
+
+// v[i] = mean over the last axis of |pred - gt|
+__global__ void __launch_bounds__(TB) k_trim_l1_values(const float *__restrict__ pred, const float *__restrict__ gt, int64_t n, int D,
+                                                       float *__restrict__ values) {
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += stride) {
+    float s = 0.f;
+    for (int d = 0; d < D; d++) s += fabsf(pred[i * D + d] - gt[i * D + d]);
+    values[i] = D == 1 ? s : s / (float)D;
+  }
+}
+
+// the finite differences of one pixel towards its right (x term) and lower (y term) neighbour, and whether each pair is valid
+struct GradPairs {
+  float dx, dy;
+  bool vx, vy;
+};
+__device__ __forceinline__ GradPairs grad_pairs(const float *__restrict__ pred, const float *__restrict__ gt, const float *__restrict__ mask,
+                                                int64_t p, int H, int W) {
+  const int x = (int)(p % W), y = (int)((p / W) % H);
+  GradPairs g;
+  const bool m0 = mask[p] != 0.f;
+  g.vx = m0 && x + 1 < W && mask[p + 1] != 0.f;
+  g.vy = m0 && y + 1 < H && mask[p + W] != 0.f;
+  g.dx = g.vx ? (pred[p + 1] - pred[p]) - (gt[p + 1] - gt[p]) : 0.f;
+  g.dy = g.vy ? (pred[p + W] - pred[p]) - (gt[p + W] - gt[p]) : 0.f;
+  return g;
+}
+
+__global__ void __launch_bounds__(TB) k_trim_grad_values(const float *__restrict__ pred, const float *__restrict__ gt,
+                                                         const float *__restrict__ mask, int64_t P, int H, int W,
+                                                         float *__restrict__ values, uint32_t *ctrl) {
+  __shared__ uint32_t cnt[2];
+  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t cx = 0, cy = 0;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t p = (int64_t)blockIdx.x * TB + threadIdx.x; p < P; p += stride) {
+    const GradPairs g = grad_pairs(pred, gt, mask, p, H, W);
+    values[p] = g.vx ? fabsf(g.dx) : __uint_as_float(TRIM_EMPTY);
+    values[P + p] = g.vy ? fabsf(g.dy) : __uint_as_float(TRIM_EMPTY);
+    cx += g.vx, cy += g.vy;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cx += __shfl_xor(cx, o), cy += __shfl_xor(cy, o);
+  if ((threadIdx.x & 63) == 0) atomicAdd(&cnt[0], cx), atomicAdd(&cnt[1], cy);
+  __syncthreads();
+  if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&ctrl[threadIdx.x * C_WORDS + C_COUNT], cnt[threadIdx.x]);
+}
+
+// one wave adds its lanes' digits to an LDS histogram (header comment); called by all 64 lanes together
+__device__ __forceinline__ void wave_hist_add(uint32_t *h, uint32_t digit, bool active) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(active);
+  for (int round = 0; round < TRIM_PEEL && todo; round++) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const uint32_t d = __shfl(digit, leader);
+    const bool mine = active && digit == d;
+    const unsigned long long same = __ballot(mine);
+    if (lane == leader) atomicAdd(&h[d], (uint32_t)__popcll(same));
+    active = active && !mine;
+    todo &= ~same;
+  }
+  if (active) atomicAdd(&h[digit], 1u);
+}
+
+// pass p counts bits [24 - 8p, 32 - 8p) of the keys whose higher bits equal the prefix of the lower / of the upper order statistic
+__global__ void __launch_bounds__(TB) k_trim_hist(const float *__restrict__ values, int64_t n_max, uint32_t *ctrl_all, int pass) {
+  __shared__ uint32_t h[TB / 64][2][256];
+  const int term = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+  uint32_t *ctrl = ctrl_all + (int64_t)term * C_WORDS;
+  const uint32_t *keys = reinterpret_cast<const uint32_t *>(values) + (int64_t)term * n_max;
+  for (int i = tid; i < (TB / 64) * 2 * 256; i += TB) (&h[0][0][0])[i] = 0;
+  const int shift = 24 - 8 * pass;
+  const uint32_t high = pass == 0 ? 0u : 0xFFFFFFFFu << (shift + 8);
+  const uint32_t pre_lo = ctrl[C_PREFIX_LO], pre_hi = ctrl[C_PREFIX_HI];
+  const bool split = pre_lo != pre_hi;
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t base = (int64_t)blockIdx.x * TB; base < n_max; base += stride) {  // block-uniform trip count: the ballots need whole waves
+    const int64_t i = base + tid;
+    const uint32_t key = i < n_max ? keys[i] : TRIM_EMPTY;
+    const uint32_t digit = (key >> shift) & 255u;
+    const bool live = key != TRIM_EMPTY;
+    wave_hist_add(h[wave][0], digit, live && (key & high) == pre_lo);
+    if (split) wave_hist_add(h[wave][1], digit, live && (key & high) == pre_hi);
+  }
+  __syncthreads();
+  for (int i = tid; i < 512; i += TB) {
+    const int track = i >> 8, bin = i & 255;
+    uint32_t s = 0;
+#pragma unroll
+    for (int w = 0; w < TB / 64; w++) s += h[w][track][bin];
+    if (s) atomicAdd(&ctrl[C_HIST + i], s);
+  }
+}
+
+// torch.lerp's formula in fp32 (ATen/native/Lerp.h)
+__device__ __forceinline__ float trim_lerp(float a, float b, float w) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  return w < 0.5f ? a + w * d : b - d * (1.f - w);
+}
+
+// one block per term: bin of the histogram that holds the wanted rank -> next 8 bits of the prefix.  Before the first pass: the
+// ranks from the live count, r = q (n - 1) in fp32 as torch.quantile evaluates it for fp32 input.  After the last: the threshold.
+__global__ void __launch_bounds__(TB) k_trim_narrow(uint32_t *ctrl_all, int pass, float q) {
+  __shared__ uint32_t scan[2][TB];
+  __shared__ uint32_t st[8];
+  uint32_t *ctrl = ctrl_all + (int64_t)blockIdx.x * C_WORDS;
+  const int tid = threadIdx.x;
+  const uint32_t n = ctrl[C_COUNT];
+  if (tid == 0) {
+    if (pass == 0) {
+      float r = 0.f;
+      uint32_t lo = 0, hi = 0;
+      if (n > 0) {
+        r = q * (float)(n - 1);
+        const float fl = floorf(r), ce = ceilf(r);
+        lo = fl >= (float)(n - 1) ? n - 1 : (uint32_t)fl;  // (float)(n - 1) can round up: stay inside
+        hi = ce >= (float)(n - 1) ? n - 1 : (uint32_t)ce;
+        r = r - fl;
+      }
+      st[C_PREFIX_LO] = 0, st[C_PREFIX_HI] = 0, st[C_RANK_LO] = lo, st[C_RANK_HI] = hi, st[C_FRAC] = __float_as_uint(r);
+    } else {
+      for (int k = C_PREFIX_LO; k <= C_FRAC; k++) st[k] = ctrl[k];
+    }
+  }
+  const uint32_t ha = ctrl[C_HIST + tid], hb_raw = ctrl[C_HIST + 256 + tid];
+  __syncthreads();
+  ctrl[C_HIST + tid] = 0, ctrl[C_HIST + 256 + tid] = 0;  // ready for the next pass (and for the next call)
+  const bool split = st[C_PREFIX_LO] != st[C_PREFIX_HI];
+  const uint32_t hb = split ? hb_raw : ha;
+  const uint32_t rank_lo = st[C_RANK_LO], rank_hi = st[C_RANK_HI];
+  scan[0][tid] = ha, scan[1][tid] = hb;
+  __syncthreads();
+  for (int o = 1; o < TB; o <<= 1) {  // inclusive scans of both histograms
+    const uint32_t a = tid >= o ? scan[0][tid - o] : 0, b = tid >= o ? scan[1][tid - o] : 0;
+    __syncthreads();
+    scan[0][tid] += a, scan[1][tid] += b;
+    __syncthreads();
+  }
+  const int shift = 24 - 8 * pass;
+  const uint32_t ea = scan[0][tid] - ha, eb = scan[1][tid] - hb;  // exclusive
+  if (ha && ea <= rank_lo && rank_lo - ea < ha) st[C_PREFIX_LO] |= (uint32_t)tid << shift, st[C_RANK_LO] = rank_lo - ea;
+  __syncthreads();  // (the two updates touch different words, but C_PREFIX_LO above was read for `split`: keep them apart)
+  if (hb && eb <= rank_hi && rank_hi - eb < hb) st[C_PREFIX_HI] |= (uint32_t)tid << shift, st[C_RANK_HI] = rank_hi - eb;
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = C_PREFIX_LO; k <= C_FRAC; k++) ctrl[k] = st[k];
+    if (pass == TRIM_PASSES - 1) {
+      const float t = n > 0 ? trim_lerp(__uint_as_float(st[C_PREFIX_LO]), __uint_as_float(st[C_PREFIX_HI]), __uint_as_float(st[C_FRAC]))
+                            : __uint_as_float(0x7FC00000u);  // no element: NaN, nothing is below it
+      ctrl[C_T] = __float_as_uint(t);
+    }
+  }
+}
+
+__device__ __forceinline__ bool trim_kept(float v, float t, bool keep_all) { return keep_all ? v == v : v < t; }
+
+__global__ void __launch_bounds__(TB) k_trim_sum(const float *__restrict__ values, const float *__restrict__ weights, int64_t n_max,
+                                                 const uint32_t *__restrict__ ctrl_all, int keep_all, double *__restrict__ partials) {
+  __shared__ double red[3][TB / 64];
+  const int term = blockIdx.y, tid = threadIdx.x;
+  const float t = __uint_as_float(ctrl_all[(int64_t)term * C_WORDS + C_T]);
+  const float *v = values + (int64_t)term * n_max;
+  double s_vm = 0.0, s_m = 0.0, cnt = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + tid; i < n_max; i += stride) {
+    const float vi = v[i];
+    if (trim_kept(vi, t, keep_all)) {
+      const float m = weights ? weights[i] : 1.f;
+      s_vm += (double)(vi * m), s_m += (double)m, cnt += 1.0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s_vm += __shfl_xor(s_vm, o), s_m += __shfl_xor(s_m, o), cnt += __shfl_xor(cnt, o);
+  if ((tid & 63) == 0) red[0][tid >> 6] = s_vm, red[1][tid >> 6] = s_m, red[2][tid >> 6] = cnt;
+  __syncthreads();
+  if (tid < 3) partials[((int64_t)term * gridDim.x + blockIdx.x) * PARTIAL_DOUBLES + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+
+// out[0] = sum of the terms' losses; per term k: out[1 + 2k] = threshold, out[2 + 2k] = 1 / denominator (what the backward scales by)
+// denominators: mode 0 sum of kept m + 1e-8 (normalize=True), mode 1 the kept count (normalize=False, no mask)
+__global__ void __launch_bounds__(TB) k_trim_finish(const double *__restrict__ partials, int n_blocks, int terms, int mode,
+                                                    const uint32_t *__restrict__ ctrl_all, float *out) {
+  __shared__ double r[3][TB];
+  double total = 0.0;
+  for (int term = 0; term < terms; term++) {
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n_blocks; i += TB)
+      for (int k = 0; k < 3; k++) a[k] += partials[((int64_t)term * n_blocks + i) * PARTIAL_DOUBLES + k];
+    for (int k = 0; k < 3; k++) r[k][threadIdx.x] = a[k];
+    __syncthreads();
+    for (int o = TB / 2; o > 0; o >>= 1) {
+      if (threadIdx.x < o)
+        for (int k = 0; k < 3; k++) r[k][threadIdx.x] += r[k][threadIdx.x + o];
+      __syncthreads();
+    }
+    const double den = mode == 0 ? r[1][0] + 1e-8 : r[2][0];
+    total += r[0][0] / den;  // 0 / 0 = NaN: an empty kept set, as torch's mean of nothing
+    if (threadIdx.x == 0) out[1 + 2 * term] = __uint_as_float(ctrl_all[(int64_t)term * C_WORDS + C_T]), out[2 + 2 * term] = (float)(1.0 / den);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)total;
+}
+
+__global__ void __launch_bounds__(TB) k_trim_l1_bwd(const float *__restrict__ pred, const float *__restrict__ gt, const float *__restrict__ mask,
+                                                    const float *__restrict__ values, const float *__restrict__ out,
+                                                    const float *__restrict__ v_loss, int64_t n, int D, int keep_all, float *__restrict__ v_pred) {
+  const float t = out[1], scale = v_loss[0] * out[2] / (float)D;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += stride) {
+    const float c = trim_kept(values[i], t, keep_all) ? scale * (mask ? mask[i] : 1.f) : 0.f;
+    for (int d = 0; d < D; d++) {
+      const float x = pred[i * D + d], y = gt[i * D + d];
+      v_pred[i * D + d] = x > y ? c : (x < y ? -c : 0.f);
+    }
+  }
+}
+
+__device__ __forceinline__ float trim_sign(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+
+// one thread per pixel gathers from the (at most) four pairs it belongs to: no atomics, a fixed order
+__global__ void __launch_bounds__(TB) k_trim_grad_bwd(const float *__restrict__ pred, const float *__restrict__ gt, const float *__restrict__ mask,
+                                                      const float *__restrict__ values, const float *__restrict__ out,
+                                                      const float *__restrict__ v_loss, int64_t P, int H, int W, float *__restrict__ v_pred) {
+  const float tx = out[1], ty = out[3], sx = v_loss[0] * out[2], sy = v_loss[0] * out[4];
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t p = (int64_t)blockIdx.x * TB + threadIdx.x; p < P; p += stride) {
+    const int x = (int)(p % W), y = (int)((p / W) % H);
+    float g = 0.f;
+    const GradPairs own = grad_pairs(pred, gt, mask, p, H, W);  // pairs (p, p + 1) and (p, p + W): p is the subtracted end
+    if (own.vx && values[p] < tx) g -= sx * trim_sign(own.dx);
+    if (x > 0) {
+      const GradPairs l = grad_pairs(pred, gt, mask, p - 1, H, W);
+      if (l.vx && values[p - 1] < tx) g += sx * trim_sign(l.dx);
+    }
+    if (own.vy && values[P + p] < ty) g -= sy * trim_sign(own.dy);
+    if (y > 0) {
+      const GradPairs u = grad_pairs(pred, gt, mask, p - W, H, W);
+      if (u.vy && values[P + p - W] < ty) g += sy * trim_sign(u.dy);
+    }
+    v_pred[p] = g;
+  }
+}
+
+// init, [selection], sum, finish over values already in scratch
+int trim_reduce(float *values, const float *weights, int64_t n_max, int terms, bool keep_all, int mode, float q, uint32_t *ctrl,
+                double *partials, float *out, hipStream_t stream) {
+  const int nb = (int)trim_blocks(n_max);
+  const dim3 grid(nb, terms);
+  if (!keep_all) {
+    for (int pass = 0; pass < TRIM_PASSES; pass++) {
+      D4GS_LAUNCH("k_trim_hist", k_trim_hist, grid, dim3(TB), 0, stream, (const float *)values, n_max, ctrl, pass);
+      if (int rc = d4gs_check_launch("k_trim_hist")) return rc;
+      D4GS_LAUNCH("k_trim_narrow", k_trim_narrow, dim3(terms), dim3(TB), 0, stream, ctrl, pass, q);
+      if (int rc = d4gs_check_launch("k_trim_narrow")) return rc;
+    }
+  }
+  D4GS_LAUNCH("k_trim_sum", k_trim_sum, grid, dim3(TB), 0, stream, (const float *)values, weights, n_max, (const uint32_t *)ctrl,
+              (int)keep_all, partials);
+  if (int rc = d4gs_check_launch("k_trim_sum")) return rc;
+  D4GS_LAUNCH("k_trim_finish", k_trim_finish, dim3(1), dim3(TB), 0, stream, (const double *)partials, nb, terms, mode,
+              (const uint32_t *)ctrl, out);
+  return d4gs_check_launch("k_trim_finish");
+}
+
+bool bad_quantile(float q) { return !(q > 0.f) || !(q <= 3.0e38f); }  // NaN, <= 0, inf
+
+int l1_fwd(const char *who, const float *pred, const float *gt, const float *mask, int64_t n, int32_t D, bool keep_all, int mode,
+           float quantile, void *scratch, int64_t scratch_words, float *out, void *stream) {
+  if (!pred || !gt || !scratch || !out) {
+    d4gs_set_error("%s: NULL argument (pred, gt, scratch and out are required)", who);
+    return D4GS_EINVAL;
+  }
+  if (n < 0 || n > INT32_MAX || D < 1) {
+    d4gs_set_error("%s: bad size n=%lld D=%d (0 <= n <= 2^31 - 1, D >= 1)", who, (long long)n, D);
+    return D4GS_EINVAL;
+  }
+  if (bad_quantile(quantile)) {
+    d4gs_set_error("%s: quantile=%g (finite and > 0)", who, (double)quantile);
+    return D4GS_EINVAL;
+  }
+  if (scratch_words < trim_scratch_words(n, 1) || (uintptr_t)scratch % 8) {
+    d4gs_set_error("%s: scratch of %lld words (8-byte aligned) needed, %lld given at %p", who, (long long)trim_scratch_words(n, 1),
+                   (long long)scratch_words, scratch);
+    return D4GS_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float *values = (float *)scratch;
+  uint32_t *ctrl = (uint32_t *)scratch + trim_ctrl_offset(n, 1);
+  double *partials = (double *)((uint32_t *)scratch + trim_partials_offset(n, 1));
+  D4GS_LAUNCH("k_trim_init", k_trim_init, dim3(1), dim3(TB), 0, s, ctrl, 1, (uint32_t)n);
+  if (int rc = d4gs_check_launch("k_trim_init")) return rc;
+  D4GS_LAUNCH("k_trim_l1_values", k_trim_l1_values, dim3((unsigned)trim_blocks(n)), dim3(TB), 0, s, pred, gt, n, (int)D, values);
+  if (int rc = d4gs_check_launch("k_trim_l1_values")) return rc;
+  return trim_reduce(values, mask, n, 1, keep_all, mode, quantile, ctrl, partials, out, s);
+}
+
+int l1_bwd(const char *who, const float *pred, const float *gt, const float *mask, const float *values, const float *out,
+           const float *v_loss, int64_t n, int32_t D, bool keep_all, float *v_pred, void *stream) {
+  if (!pred || !gt || !values || !out || !v_loss || !v_pred) {
+    d4gs_set_error("%s: NULL argument (only the mask is optional)", who);
+    return D4GS_EINVAL;
+  }
+  if (n < 0 || n > INT32_MAX || D < 1) {
+    d4gs_set_error("%s: bad size n=%lld D=%d (0 <= n <= 2^31 - 1, D >= 1)", who, (long long)n, D);
+    return D4GS_EINVAL;
+  }
+  if (n == 0) return D4GS_OK;
+  D4GS_LAUNCH("k_trim_l1_bwd", k_trim_l1_bwd, dim3((unsigned)trim_blocks(n)), dim3(TB), 0, (hipStream_t)stream, pred, gt, mask, values,
+              out, v_loss, n, (int)D, (int)keep_all, v_pred);
+  return d4gs_check_launch("k_trim_l1_bwd");
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t d4gs_trimmed_scratch_words(int64_t n_max, int32_t terms) {
+  if (n_max < 0 || n_max > INT32_MAX || terms < 1 || terms > 2) return 0;
+  return trim_scratch_words(n_max, terms);
+}
+
+int d4gs_masked_l1_fwd(const float *pred, const float *gt, const float *mask, int64_t n, int32_t D, int32_t normalize, float quantile,
+                       void *scratch, int64_t scratch_words, float *out, void *stream) {
+  if (!mask) {
+    d4gs_set_error("d4gs_masked_l1_fwd: NULL mask (the form without a mask is d4gs_trimmed_l1_fwd)");
+    return D4GS_EINVAL;
+  }
+  return l1_fwd("d4gs_masked_l1_fwd", pred, gt, mask, n, D, quantile >= 1.f, normalize ? 0 : 1, quantile, scratch, scratch_words, out, stream);
+}
+
+int d4gs_masked_l1_bwd(const float *pred, const float *gt, const float *mask, const float *values, const float *out, const float *v_loss,
+                       int64_t n, int32_t D, float quantile, float *v_pred, void *stream) {
+  if (!mask || bad_quantile(quantile)) {
+    d4gs_set_error("d4gs_masked_l1_bwd: NULL mask or quantile=%g (finite and > 0)", (double)quantile);
+    return D4GS_EINVAL;
+  }
+  return l1_bwd("d4gs_masked_l1_bwd", pred, gt, mask, values, out, v_loss, n, D, quantile >= 1.f, v_pred, stream);
+}
+
+int d4gs_trimmed_l1_fwd(const float *pred, const float *gt, int64_t n, int32_t D, float quantile, void *scratch, int64_t scratch_words,
+                        float *out, void *stream) {
+  return l1_fwd("d4gs_trimmed_l1_fwd", pred, gt, nullptr, n, D, false, 1, quantile, scratch, scratch_words, out, stream);
+}
+
+int d4gs_trimmed_l1_bwd(const float *pred, const float *gt, const float *values, const float *out, const float *v_loss, int64_t n,
+                        int32_t D, float *v_pred, void *stream) {
+  return l1_bwd("d4gs_trimmed_l1_bwd", pred, gt, nullptr, values, out, v_loss, n, D, false, v_pred, stream);
+}
+
+int d4gs_gradient_loss_fwd(const float *pred, const float *gt, const float *mask, int32_t B, int32_t H, int32_t W, float quantile,
+                           void *scratch, int64_t scratch_words, float *out, void *stream) {
+  if (!pred || !gt || !mask || !scratch || !out) {
+    d4gs_set_error("d4gs_gradient_loss_fwd: NULL argument");
+    return D4GS_EINVAL;
+  }
+  const int64_t P = (int64_t)B * H * W;
+  if (B < 0 || H < 0 || W < 0 || P > INT32_MAX) {
+    d4gs_set_error("d4gs_gradient_loss_fwd: bad size B=%d H=%d W=%d (each >= 0, B H W <= 2^31 - 1)", B, H, W);
+    return D4GS_EINVAL;
+  }
+  if (bad_quantile(quantile)) {
+    d4gs_set_error("d4gs_gradient_loss_fwd: quantile=%g (finite and > 0)", (double)quantile);
+    return D4GS_EINVAL;
+  }
+  if (scratch_words < trim_scratch_words(P, 2) || (uintptr_t)scratch % 8) {
+    d4gs_set_error("d4gs_gradient_loss_fwd: scratch of %lld words (8-byte aligned) needed, %lld given at %p",
+                   (long long)trim_scratch_words(P, 2), (long long)scratch_words, scratch);
+    return D4GS_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float *values = (float *)scratch;
+  uint32_t *ctrl = (uint32_t *)scratch + trim_ctrl_offset(P, 2);
+  double *partials = (double *)((uint32_t *)scratch + trim_partials_offset(P, 2));
+  D4GS_LAUNCH("k_trim_init", k_trim_init, dim3(1), dim3(TB), 0, s, ctrl, 2, 0u);
+  if (int rc = d4gs_check_launch("k_trim_init")) return rc;
+  D4GS_LAUNCH("k_trim_grad_values", k_trim_grad_values, dim3((unsigned)trim_blocks(P)), dim3(TB), 0, s, pred, gt, mask, P, (int)H, (int)W,
+              values, ctrl);
+  if (int rc = d4gs_check_launch("k_trim_grad_values")) return rc;
+  return trim_reduce(values, nullptr, P, 2, false, 1, quantile, ctrl, partials, out, s);
+}
+
+int d4gs_gradient_loss_bwd(const float *pred, const float *gt, const float *mask, const float *values, const float *out,
+                           const float *v_loss, int32_t B, int32_t H, int32_t W, float *v_pred, void *stream) {
+  if (!pred || !gt || !mask || !values || !out || !v_loss || !v_pred) {
+    d4gs_set_error("d4gs_gradient_loss_bwd: NULL argument");
+    return D4GS_EINVAL;
+  }
+  const int64_t P = (int64_t)B * H * W;
+  if (B < 0 || H < 0 || W < 0 || P > INT32_MAX) {
+    d4gs_set_error("d4gs_gradient_loss_bwd: bad size B=%d H=%d W=%d (each >= 0, B H W <= 2^31 - 1)", B, H, W);
+    return D4GS_EINVAL;
+  }
+  if (P == 0) return D4GS_OK;
+  D4GS_LAUNCH("k_trim_grad_bwd", k_trim_grad_bwd, dim3((unsigned)trim_blocks(P)), dim3(TB), 0, (hipStream_t)stream, pred, gt, mask, values,
+              out, v_loss, P, (int)H, (int)W, v_pred);
+  return d4gs_check_launch("k_trim_grad_bwd");
+}
+
+}  // extern "C"

@@ -1,9 +1,16 @@
-"""The photometric term of the reference's training loss, fused.
+"""The reference's image-sized training losses as HIP kernels: the photometric term and the quantile-trimmed
+masked L1 / depth-gradient losses of flow3d/loss_utils.py.
 
 `photometric_loss(pred, gt, mask)` = 0.8 * L1 + 0.2 * (1 - SSIM) on `pred * mask` vs `gt * mask`, the expression the
 reference evaluates three to four times per step (flow3d/trainer.py:388-392,575-586) with `pytorch_msssim.SSIM` and
 ~85 eager launches per evaluation; here: two kernels forward, one backward (`csrc/photometric.hip`).  Images are
 channel-last [B,H,W,3] as the rasterizer returns them (no permute), the mask is [B,H,W] or [B,H,W,1].
+
+`masked_l1_loss`, `trimmed_l1_loss` and `compute_gradient_loss` carry the names and signatures of flow3d/loss_utils.py, so
+`from deblur4dgs_amd.losses import ...` replaces `from flow3d.loss_utils import ...`.  The reference finds its threshold with
+`torch.quantile` (a full sort) and selects with boolean masks (`nonzero`: the host waits for the device); here the two order
+statistics come from a radix select and nothing is read on the host, so the losses can sit inside a captured HIP graph
+(`csrc/trimmed.hip`).  Gradients flow to `pred` only.
 """
 from __future__ import annotations
 
@@ -56,3 +63,131 @@ def photometric_loss(pred, gt, mask=None, w_l1: float = 0.8, w_ssim: float = 0.2
     (the reference's `imgs` and masks are data)."""
     loss, l1, ssim = PhotometricFn.apply(pred, gt, mask, float(w_l1), float(w_ssim))
     return (loss, l1.detach(), ssim.detach()) if return_terms else loss
+
+
+def _f32(t):
+    return t.detach().float().contiguous()
+
+
+def _check_quantile(quantile, upper_open):
+    q = float(quantile)
+    if not (q > 0.0) or q == float("inf") or (not upper_open and q > 1.0):
+        raise ValueError(f"quantile={quantile}: must be in (0, 1]" + (" (or above 1: nothing is trimmed)" if upper_open else ""))
+    return q
+
+
+def _scratch(n_max, terms, device):
+    words = L.lib().d4gs_trimmed_scratch_words(n_max, terms)
+    if words == 0:
+        raise RuntimeError(f"trimmed losses: {n_max} elements (at most 2^31 - 1)")
+    return torch.empty(words, device=device, dtype=torch.int32), words
+
+
+class _TrimmedL1Fn(torch.autograd.Function):
+    """mask is None: the trimmed mean (always selects); otherwise the masked forms (quantile >= 1: every element kept)."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, mask, normalize, quantile):
+        if not pred.is_cuda:
+            raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+        if pred.shape != gt.shape or pred.dim() < 1:
+            raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have the same shape, at least 1-D")
+        D = pred.shape[-1]
+        if D < 1:
+            raise ValueError("the last axis of pred is empty")
+        n = pred.numel() // D
+        if n == 0:
+            raise ValueError("no elements (torch.quantile of an empty tensor raises too)")
+        p, g = _f32(pred), _f32(gt)
+        m = None
+        if mask is not None:
+            if mask.numel() != n:
+                raise ValueError(f"mask {tuple(mask.shape)} does not match the {tuple(pred.shape[:-1])} elements of pred")
+            m = _f32(mask).reshape(n)
+        lib = L.lib()
+        scratch, words = _scratch(n, 1, p.device)
+        out = torch.empty(8, device=p.device, dtype=torch.float32)
+        stream = C.c_void_p(L.raw_stream(p.device.index))
+        if m is None:
+            L.check(lib.d4gs_trimmed_l1_fwd(_p(p), _p(g), n, D, quantile, _p(scratch), words, _p(out), stream), "d4gs_trimmed_l1_fwd")
+        else:
+            L.check(lib.d4gs_masked_l1_fwd(_p(p), _p(g), _p(m), n, D, int(bool(normalize)), quantile, _p(scratch), words, _p(out), stream),
+                    "d4gs_masked_l1_fwd")
+        ctx.keep = (p, g, m, scratch, out)
+        ctx.args = (n, D, quantile, pred.shape, pred.dtype)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, v_loss):
+        p, g, m, scratch, out = ctx.keep
+        n, D, quantile, shape, dtype = ctx.args
+        v = v_loss.detach().float().reshape(1).contiguous()
+        v_pred = torch.empty_like(p)
+        stream = C.c_void_p(L.raw_stream(p.device.index))
+        lib = L.lib()
+        if m is None:
+            L.check(lib.d4gs_trimmed_l1_bwd(_p(p), _p(g), _p(scratch), _p(out), _p(v), n, D, _p(v_pred), stream), "d4gs_trimmed_l1_bwd")
+        else:
+            L.check(lib.d4gs_masked_l1_bwd(_p(p), _p(g), _p(m), _p(scratch), _p(out), _p(v), n, D, quantile, _p(v_pred), stream),
+                    "d4gs_masked_l1_bwd")
+        return v_pred.reshape(shape).to(dtype), None, None, None, None
+
+
+class _GradientLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, mask, quantile):
+        if not pred.is_cuda:
+            raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+        if pred.dim() == 4 and pred.shape[-1] != 1:
+            raise NotImplementedError(f"compute_gradient_loss: {pred.shape[-1]} channels (one is supported: [B,H,W] or [B,H,W,1])")
+        if pred.dim() not in (3, 4) or pred.shape != gt.shape:
+            raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must both be [B,H,W] or [B,H,W,1]")
+        B, H, W = pred.shape[:3]
+        if B * H * W == 0:
+            raise ValueError("no pixels")
+        if mask.numel() != B * H * W:
+            raise ValueError(f"mask {tuple(mask.shape)} does not match [B,H,W] = {(B, H, W)}")
+        p, g, m = _f32(pred), _f32(gt), _f32(mask).reshape(B, H, W)
+        scratch, words = _scratch(B * H * W, 2, p.device)
+        out = torch.empty(8, device=p.device, dtype=torch.float32)
+        stream = C.c_void_p(L.raw_stream(p.device.index))
+        L.check(L.lib().d4gs_gradient_loss_fwd(_p(p), _p(g), _p(m), B, H, W, quantile, _p(scratch), words, _p(out), stream),
+                "d4gs_gradient_loss_fwd")
+        ctx.keep = (p, g, m, scratch, out)
+        ctx.args = (B, H, W, pred.shape, pred.dtype)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, v_loss):
+        p, g, m, scratch, out = ctx.keep
+        B, H, W, shape, dtype = ctx.args
+        v = v_loss.detach().float().reshape(1).contiguous()
+        v_pred = torch.empty_like(p)
+        stream = C.c_void_p(L.raw_stream(p.device.index))
+        L.check(L.lib().d4gs_gradient_loss_bwd(_p(p), _p(g), _p(m), _p(scratch), _p(out), _p(v), B, H, W, _p(v_pred), stream),
+                "d4gs_gradient_loss_bwd")
+        return v_pred.reshape(shape).to(dtype), None, None, None
+
+
+def masked_l1_loss(pred, gt, mask=None, normalize=True, quantile: float = 1.0):
+    """flow3d/loss_utils.py:26-42.  Elements v = |pred - gt|.mean(-1); with quantile < 1 only those strictly below
+    torch.quantile(v, quantile) - taken over ALL elements, masked-out ones included - are kept.  `mask` (float or bool, shaped
+    like v, with or without a trailing 1) weighs them: sum(v m) / (sum(m) + 1e-8) over the kept ones, or sum(v m) / #kept with
+    normalize=False.  mask=None is `trimmed_l1_loss(pred, gt, quantile)`, as in the reference."""
+    if mask is None:
+        return trimmed_l1_loss(pred, gt, quantile)
+    return _TrimmedL1Fn.apply(pred, gt, mask, bool(normalize), _check_quantile(quantile, upper_open=True))
+
+
+def trimmed_l1_loss(pred, gt, quantile=0.9):
+    """flow3d/loss_utils.py:64-68: the mean of the elements strictly below torch.quantile(v, quantile).  The quantile is always
+    taken (quantile=1: the maximum, whose tie group is dropped); an empty kept set is NaN, as torch's mean of nothing."""
+    return _TrimmedL1Fn.apply(pred, gt, None, False, _check_quantile(quantile, upper_open=False))
+
+
+def compute_gradient_loss(pred, gt, mask, quantile=0.98):
+    """flow3d/loss_utils.py:71-90.  pred, gt [B,H,W] or [B,H,W,1]; mask [B,H,W] or [B,H,W,1], bool or float.  The trimmed mean of
+    |dx pred - dx gt| over horizontally adjacent pixels that are both inside the mask, plus the same vertically.  Deviation: a
+    term without any valid pair is NaN here, where the reference raises (torch.quantile of an empty tensor) - raising would need
+    the count on the host."""
+    return _GradientLossFn.apply(pred, gt, mask, _check_quantile(quantile, upper_open=False))

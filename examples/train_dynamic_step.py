@@ -5,9 +5,13 @@ Mirrors the SHAPE of the reference's `Trainer.train_step` (flow3d/trainer.py:203
 (static `bg_only` blurry frame, dynamic full blurry frame with mask / track / depth channels, static `mid` frame),
 the reference's photometric loss (0.8 L1 + 0.2 (1 - SSIM), fused), one Adam optimizer per parameter tensor, the
 densification statistics of `_prepare_control_step` and (with --control-every) the densify / cull control steps -
-without the reference's data pipeline or its PWC-Net / depth / track losses (out of scope).  It exists to show the seam in a real autograd + optimizer loop:
+without the reference's data pipeline or its PWC-Net / track losses (out of scope).  With --depth-losses the step
+also carries the reference's quantile-trimmed losses (deblur4dgs_amd.losses): the disparity loss and the
+depth-gradient loss on the `mid` render (trainer.py:399-416) and the L1 term of the mask loss on the dynamic render (:626-630).
+It exists to show the seam in a real autograd + optimizer loop:
 
     python examples/train_dynamic_step.py --steps 20
+    python examples/train_dynamic_step.py --graph --hip-adam --depth-losses
 """
 from __future__ import annotations
 
@@ -22,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from deblur4dgs_amd import engine  # noqa: E402
 from deblur4dgs_amd.control import ControlCfg, accumulate_from_model, cull_step, densify_step, spatial_order_step  # noqa: E402
-from deblur4dgs_amd.losses import photometric_loss  # noqa: E402
+from deblur4dgs_amd.losses import compute_gradient_loss, masked_l1_loss, photometric_loss  # noqa: E402
 from deblur4dgs_amd.scene_model import GaussianParams, MotionBases, SceneModel  # noqa: E402
 from deblur4dgs_amd.synth import make_scene  # noqa: E402
 
@@ -38,7 +42,7 @@ def build(n_fg=40_000, n_bg=100_000, K=20, W=512, H=288, dev="cuda:0", seed=0):
 
 
 def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, fused_stats=True, deferred=True,
-          graph=False, hip_adam=False, seed=0, step_events=None, **kw):
+          graph=False, hip_adam=False, seed=0, step_events=None, depth_losses=False, **kw):
     """fused_stats: the densification statistics come out of the rasterizer's backward (attach_control_stats) instead
     of a pass over `_current_xys[i].grad`; deferred: no render waits for its intersection count on the host
     (`deferred_size_check`), the counts are verified once per step; graph: the three renders, the loss and the whole
@@ -47,7 +51,9 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
     are handles of one `deblur4dgs_amd.optim.AdamGroup` - one HIP launch steps them all, and with graph=True that launch is
     captured behind the backward, so the whole step, optimizers included, is the one hipGraphLaunch.  seed: the synthetic
     scene (its targets: seed + 1); step_events: a list that receives one timing event per step, recorded where the step
-    begins (per-step times without a host sync: scripts/bench_adam.py)."""
+    begins (per-step times without a host sync: scripts/bench_adam.py); depth_losses: add the reference's disparity, depth-gradient
+    and mask-L1 losses with its default weights (configs.py: w_depth_reg 0.5, w_depth_grad 1, w_mask 1) - they wait for nothing on
+    the host, so the step still captures."""
     assert not graph or (fused_stats and deferred), "graph capture needs the sync-free step"
     model, sc = build(W=W, H=H, dev=dev, seed=seed, **kw)
     model.deferred_size_check = bool(deferred)
@@ -57,6 +63,14 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
         tgt_model, _ = build(W=W, H=H, dev=dev, seed=seed + 1, **kw)
         tgt_dyn = tgt_model.render(3, w2c, K, (W, H), mode="blury")["img"]
         tgt_sta = tgt_model.render(3, w2c, K, (W, H), bg_only=True, mode="blury")["img"]
+        if depth_losses:  # the perturbed scene also supplies the depth of the `mid` frame and the foreground mask
+            tgt_mid = tgt_model.render(3, w2c, K, (W, H), bg_only=True, return_depth=True, mode="mid")
+            tgt_disp = 1.0 / (tgt_mid["depth"] + 1e-5)
+            tgt_mask = (tgt_model.render(3, w2c, K, (W, H), return_mask=True, mode="blury")["mask"] > 0.5).float()
+            # outside the foreground mask (the reference dilates it first: trainer.py:388,397) and, the scene being synthetic, only
+            # where the target's background covers the pixel: a hole has depth 0, a disparity of 1e5
+            depth_masks = (1.0 - tgt_mask) * (tgt_mid["acc"] > 0.5).float()
+            depth_valid = depth_masks > 0.5
     # (torch's fused Adam faults the GPU when its gradients live in a CUDA-graph memory pool - scripts/graph_bisect.py;
     # the graph mode therefore uses the plain implementation)
     adam = lambda p, lr: torch.optim.Adam([p], lr=lr, fused=p.is_cuda and not graph)
@@ -92,6 +106,11 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
         # the reference's photometric term, 0.8 L1 + 0.2 (1 - SSIM) (trainer.py:388-392,575-586), fused
         loss = photometric_loss(out1["img"], tgt_sta) + photometric_loss(out2["img"], tgt_dyn) + \
             0.1 * photometric_loss(out3["img"], tgt_sta) + 1e-3 * out2["tracks_3d"].square().mean()
+        if depth_losses:
+            pred_disp = 1.0 / (out3["depth"] + 1e-5)
+            loss = loss + 0.5 * masked_l1_loss(pred_disp, tgt_disp, mask=depth_masks, quantile=0.98) + \
+                1.0 * compute_gradient_loss(pred_disp, tgt_disp, mask=depth_valid, quantile=0.95) + \
+                1.0 * masked_l1_loss(out2["mask"], tgt_mask, quantile=0.98)
         loss.backward()
         return loss.detach(), side
 
@@ -180,5 +199,8 @@ if __name__ == "__main__":
     ap.add_argument("--round1", action="store_true", help="statistics as a separate pass, host waits for every list size")
     ap.add_argument("--graph", action="store_true", help="replay the step's renders + loss + backward from a HIP graph")
     ap.add_argument("--hip-adam", action="store_true", help="step every optimizer with one HIP launch (inside the graph with --graph)")
+    ap.add_argument("--depth-losses", action="store_true",
+                    help="add the reference's disparity, depth-gradient and mask-L1 losses (quantile-trimmed, HIP, graph-capturable)")
     a = ap.parse_args()
-    train(a.steps, control_every=a.control_every, fused_stats=not a.round1, deferred=not a.round1, graph=a.graph, hip_adam=a.hip_adam)
+    train(a.steps, control_every=a.control_every, fused_stats=not a.round1, deferred=not a.round1, graph=a.graph, hip_adam=a.hip_adam,
+          depth_losses=a.depth_losses)

@@ -574,6 +574,41 @@ D4GS_API int d4gs_adam_set_grads(D4gsAdamRec *table, int32_t n_records, const fl
  * step, a pointer that is not 4-byte aligned, or n < 0. */
 D4GS_API int d4gs_adam_step_cpu(const D4gsAdamRec *table, int32_t n_records);
 
+/* Trimmed losses (appended; D4GS_VERSION unchanged): the reference's masked_l1_loss, trimmed_l1_loss and compute_gradient_loss
+ * (flow3d/loss_utils.py:26-42,64-68,71-90) without a sort and without a host read, so a step that holds them can be captured in a
+ * HIP graph.  Elements: v_i = mean over the last axis of |pred - gt|, i < n.  Threshold: t = torch.quantile(v, quantile) over all n
+ * elements with linear interpolation, rank r = quantile * (n - 1) evaluated in fp32, t = lerp(v_(floor r), v_(ceil r), frac r); the
+ * two order statistics are found exactly by a most-significant-digit radix select (4 histogram passes of 8 bits over the bit
+ * patterns of v).  An element is kept when v_i < t (strictly: a tie group at t is dropped whole).
+ *   masked (mask [n], any float weights): quantile >= 1 keeps every element and selects nothing;
+ *       normalize != 0: sum_kept v_i m_i / (sum_kept m_i + 1e-8),  normalize == 0: sum_kept v_i m_i / #kept
+ *   trimmed (no mask): sum_kept v_i / #kept; always selects (quantile >= 1 gives t = max v, as torch.quantile(v, 1) does)
+ *   gradient (pred, gt, mask [B,H,W]): x term over |dx pred - dx gt| at horizontally adjacent pixels whose mask values are both
+ *       non-zero, y term the same vertically; each term is `trimmed` over its own elements, whose COUNT is data: it is counted
+ *       on the device and the rank is formed there.  loss = x term + y term.
+ * An empty kept set is 0 / 0 = NaN for the mean forms (also a gradient term without a valid pair, where the reference raises: that
+ * cannot be done without a host wait) and 0 for normalize != 0.  Non-finite inputs are out of scope (no out-of-bounds access).
+ * pred, gt [n, D] (D >= 1) fp32 contiguous; 0 <= n, B H W <= 2^31 - 1.  scratch: d4gs_trimmed_scratch_words(n, 1) 32-bit words
+ * (gradient: (B H W, 2)), 8-byte aligned; the forward leaves the elements in its first n (gradient: 2 B H W) words - the `values`
+ * the backward wants - and writes out [8]: out[0] the loss, out[1] / out[3] the thresholds, out[2] / out[4] 1 / denominator per term.
+ * Backward: v_pred = v_loss[0] * dL/dpred (v_loss: device scalar), sign(pred - gt) / D * m_i / denominator on kept elements and
+ * zero elsewhere; the gradient form gathers per pixel from its at most four pairs (no atomics).  Nothing flows to gt or the mask.
+ * Every sum has a fixed order and the histograms are integer: bitwise reproducible.  D4GS_EINVAL before any GPU call for a NULL
+ * pointer, a negative or too large size, a quantile that is not finite or <= 0, or undersized / misaligned scratch. */
+D4GS_API int64_t d4gs_trimmed_scratch_words(int64_t n_max, int32_t terms); /* terms: 1, or 2 for the gradient form; 0: bad argument */
+D4GS_API int d4gs_masked_l1_fwd(const float *pred, const float *gt, const float *mask, int64_t n, int32_t D, int32_t normalize,
+                                float quantile, void *scratch, int64_t scratch_words, float *out, void *stream);
+D4GS_API int d4gs_masked_l1_bwd(const float *pred, const float *gt, const float *mask, const float *values, const float *out,
+                                const float *v_loss, int64_t n, int32_t D, float quantile, float *v_pred, void *stream);
+D4GS_API int d4gs_trimmed_l1_fwd(const float *pred, const float *gt, int64_t n, int32_t D, float quantile, void *scratch,
+                                 int64_t scratch_words, float *out, void *stream);
+D4GS_API int d4gs_trimmed_l1_bwd(const float *pred, const float *gt, const float *values, const float *out, const float *v_loss,
+                                 int64_t n, int32_t D, float *v_pred, void *stream);
+D4GS_API int d4gs_gradient_loss_fwd(const float *pred, const float *gt, const float *mask, int32_t B, int32_t H, int32_t W,
+                                    float quantile, void *scratch, int64_t scratch_words, float *out, void *stream);
+D4GS_API int d4gs_gradient_loss_bwd(const float *pred, const float *gt, const float *mask, const float *values, const float *out,
+                                    const float *v_loss, int32_t B, int32_t H, int32_t W, float *v_pred, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
