@@ -120,6 +120,8 @@ EXPORTS = (
     "d4gs_adam_blocks", "d4gs_adam_step", "d4gs_adam_set_grads", "d4gs_adam_step_cpu",
     "d4gs_trimmed_scratch_words", "d4gs_masked_l1_fwd", "d4gs_masked_l1_bwd", "d4gs_trimmed_l1_fwd", "d4gs_trimmed_l1_bwd",
     "d4gs_gradient_loss_fwd", "d4gs_gradient_loss_bwd",
+    "d4gs_correlation_fwd", "d4gs_correlation_bwd", "d4gs_backwarp_fwd", "d4gs_backwarp_bwd",
+    "d4gs_aligned_l1_blocks", "d4gs_aligned_l1_fwd", "d4gs_aligned_l1_bwd",
 )
 
 _lib = None
@@ -205,6 +207,15 @@ def lib() -> C.CDLL:
         L.d4gs_trimmed_l1_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp]
         L.d4gs_gradient_loss_fwd.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.c_int64, vp, vp]
         L.d4gs_gradient_loss_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+        i32 = C.c_int32
+        L.d4gs_correlation_fwd.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, vp]
+        L.d4gs_correlation_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, vp]
+        L.d4gs_backwarp_fwd.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+        L.d4gs_backwarp_bwd.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+        L.d4gs_aligned_l1_blocks.argtypes = [i32, i32]
+        L.d4gs_aligned_l1_blocks.restype = C.c_int64
+        L.d4gs_aligned_l1_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+        L.d4gs_aligned_l1_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
         if L.d4gs_version() != VERSION:
             raise RuntimeError(f"libd4gs.so version {L.d4gs_version()} != {VERSION} (stale build?)")
         _lib = L

@@ -5,13 +5,16 @@ Mirrors the SHAPE of the reference's `Trainer.train_step` (flow3d/trainer.py:203
 (static `bg_only` blurry frame, dynamic full blurry frame with mask / track / depth channels, static `mid` frame),
 the reference's photometric loss (0.8 L1 + 0.2 (1 - SSIM), fused), one Adam optimizer per parameter tensor, the
 densification statistics of `_prepare_control_step` and (with --control-every) the densify / cull control steps -
-without the reference's data pipeline or its PWC-Net / track losses (out of scope).  With --depth-losses the step
+without the reference's data pipeline or its track losses (out of scope).  With --depth-losses the step
 also carries the reference's quantile-trimmed losses (deblur4dgs_amd.losses): the disparity loss and the
 depth-gradient loss on the `mid` render (trainer.py:399-416) and the L1 term of the mask loss on the dynamic render (:626-630).
+With --consistency-loss the dynamic group's loss gains the reference's flow-aligned exposure consistency term (trainer.py:599-618,
+weight 2; deblur4dgs_amd.pwcnet) under a seeded random-weight PWC-Net - the pretrained blob is not shipped.
 It exists to show the seam in a real autograd + optimizer loop:
 
     python examples/train_dynamic_step.py --steps 20
     python examples/train_dynamic_step.py --graph --hip-adam --depth-losses
+    python examples/train_dynamic_step.py --graph --hip-adam --consistency-loss
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deblur4dgs_amd import engine  # noqa: E402
 from deblur4dgs_amd.control import ControlCfg, accumulate_from_model, cull_step, densify_step, spatial_order_step  # noqa: E402
 from deblur4dgs_amd.losses import compute_gradient_loss, masked_l1_loss, photometric_loss  # noqa: E402
+from deblur4dgs_amd.pwcnet import PWCNet, exposure_consistency_loss  # noqa: E402
 from deblur4dgs_amd.scene_model import GaussianParams, MotionBases, SceneModel  # noqa: E402
 from deblur4dgs_amd.synth import make_scene  # noqa: E402
 
@@ -42,7 +46,7 @@ def build(n_fg=40_000, n_bg=100_000, K=20, W=512, H=288, dev="cuda:0", seed=0):
 
 
 def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, fused_stats=True, deferred=True,
-          graph=False, hip_adam=False, seed=0, step_events=None, depth_losses=False, **kw):
+          graph=False, hip_adam=False, seed=0, step_events=None, depth_losses=False, consistency_loss=False, **kw):
     """fused_stats: the densification statistics come out of the rasterizer's backward (attach_control_stats) instead
     of a pass over `_current_xys[i].grad`; deferred: no render waits for its intersection count on the host
     (`deferred_size_check`), the counts are verified once per step; graph: the three renders, the loss and the whole
@@ -53,7 +57,8 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
     scene (its targets: seed + 1); step_events: a list that receives one timing event per step, recorded where the step
     begins (per-step times without a host sync: scripts/bench_adam.py); depth_losses: add the reference's disparity, depth-gradient
     and mask-L1 losses with its default weights (configs.py: w_depth_reg 0.5, w_depth_grad 1, w_mask 1) - they wait for nothing on
-    the host, so the step still captures."""
+    the host, so the step still captures; consistency_loss: add 2 x exposure_consistency_loss of the dynamic render's sub-samples
+    (one batched PWC-Net pass of 2 (S - 1) pairs under no_grad, one loss kernel; no host wait either)."""
     assert not graph or (fused_stats and deferred), "graph capture needs the sync-free step"
     model, sc = build(W=W, H=H, dev=dev, seed=seed, **kw)
     model.deferred_size_check = bool(deferred)
@@ -71,6 +76,11 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
             # where the target's background covers the pixel: a hole has depth 0, a disparity of 1e5
             depth_masks = (1.0 - tgt_mask) * (tgt_mid["acc"] > 0.5).float()
             depth_valid = depth_masks > 0.5
+    alignnet = None
+    if consistency_loss:  # a seeded random-weight flow network, frozen: the loss differentiates the images, not the network
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            alignnet = PWCNet(load_pretrained=False).to(dev).eval().requires_grad_(False)
     # (torch's fused Adam faults the GPU when its gradients live in a CUDA-graph memory pool - scripts/graph_bisect.py;
     # the graph mode therefore uses the plain implementation)
     adam = lambda p, lr: torch.optim.Adam([p], lr=lr, fused=p.is_cuda and not graph)
@@ -111,6 +121,8 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
             loss = loss + 0.5 * masked_l1_loss(pred_disp, tgt_disp, mask=depth_masks, quantile=0.98) + \
                 1.0 * compute_gradient_loss(pred_disp, tgt_disp, mask=depth_valid, quantile=0.95) + \
                 1.0 * masked_l1_loss(out2["mask"], tgt_mask, quantile=0.98)
+        if consistency_loss:
+            loss = loss + 2.0 * exposure_consistency_loss(out2["exposure_imgs"], alignnet)
         loss.backward()
         return loss.detach(), side
 
@@ -138,7 +150,14 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
             for p_ in params:
                 p_.grad = None
             g_, watch = torch.cuda.CUDAGraph(), engine.GraphWatch()
-            with watch.capturing(), torch.cuda.graph(g_):
+            cap_stream = torch.cuda.Stream()
+            if alignnet is not None:  # MIOpen / rocBLAS set up per-stream state on first use: not inside the capture
+                cap_stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(cap_stream), torch.no_grad():
+                    probe = torch.zeros(2 * 10, 3, H, W, device=dev)
+                    alignnet(probe, probe)
+                torch.cuda.synchronize()
+            with watch.capturing(), torch.cuda.graph(g_, stream=cap_stream):
                 loss_static, _ = fwd_bwd()
                 if group is not None:
                     group.step()  # reads lr and step counts from its device table: valid at every replay
@@ -201,6 +220,8 @@ if __name__ == "__main__":
     ap.add_argument("--hip-adam", action="store_true", help="step every optimizer with one HIP launch (inside the graph with --graph)")
     ap.add_argument("--depth-losses", action="store_true",
                     help="add the reference's disparity, depth-gradient and mask-L1 losses (quantile-trimmed, HIP, graph-capturable)")
+    ap.add_argument("--consistency-loss", action="store_true",
+                    help="add the reference's flow-aligned exposure consistency loss (HIP cost volume and warp, graph-capturable)")
     a = ap.parse_args()
     train(a.steps, control_every=a.control_every, fused_stats=not a.round1, deferred=not a.round1, graph=a.graph, hip_adam=a.hip_adam,
-          depth_losses=a.depth_losses)
+          depth_losses=a.depth_losses, consistency_loss=a.consistency_loss)

@@ -609,6 +609,44 @@ D4GS_API int d4gs_gradient_loss_fwd(const float *pred, const float *gt, const fl
 D4GS_API int d4gs_gradient_loss_bwd(const float *pred, const float *gt, const float *mask, const float *values, const float *out,
                                     const float *v_loss, int32_t B, int32_t H, int32_t W, float *v_pred, void *stream);
 
+/* Flow-aligned exposure consistency (appended; D4GS_VERSION unchanged): the pieces of the reference's AlignedLoss (flow3d/loss_utils.py,
+ * flow3d/models/pwcnet.py) that are not convolutions.  Every tensor is fp32, contiguous, NCHW.
+ *
+ * Cost volume: out[b, (dy+4)*9 + (dx+4), y, x] = lrelu((1/C) * sum_c first[b,c,y,x] * second[b,c,y+dy,x+dx]), dx, dy in -4..4, second
+ * zero outside the image; first, second [B,C,H,W], out [B,81,H,W].  lrelu(v) = v > 0 ? v : negative_slope * v is the leaky ReLU the
+ * network always applies to the volume (negative_slope = 1: none).  The channel sum runs in a fixed order.
+ * Backward: with g = v_out where the saved `out` is positive and negative_slope * v_out elsewhere (`out` may be NULL when the slope
+ * is 1), both gradients are gathers without atomics, each optional (NULL: not computed):
+ *   v_first[b,c,y,x]  = (1/C) * sum_k g[b,k,y,x]       * second[b,c,y+dy,x+dx]
+ *   v_second[b,c,y,x] = (1/C) * sum_k g[b,k,y-dy,x-dx] * first[b,c,y-dy,x-dx]
+ * Forward and backward are bitwise reproducible.  D4GS_EINVAL before any GPU call for a NULL required pointer or a dimension < 1
+ * (also B > 65535, H > 524280 or more than 2^40 elements). */
+D4GS_API int d4gs_correlation_fwd(const float *first, const float *second, int32_t B, int32_t C, int32_t H, int32_t W,
+                                  float negative_slope, float *out, void *stream);
+D4GS_API int d4gs_correlation_bwd(const float *first, const float *second, const float *out, const float *v_out, int32_t B, int32_t C,
+                                  int32_t H, int32_t W, float negative_slope, float *v_first, float *v_second, void *stream);
+/* Backward warp (pwcnet.py get_backwarp): input [B,C,H,W], flow [B,2,H,W] (x first, in pixels).  Pixel (x, y) samples the input
+ * bilinearly, zeros outside, at (x + fx W / (W - 1), y + fy H / (H - 1)) - the factor is what the reference's normalisation by
+ * (W - 1) / 2 leaves on its align_corners=False grid; H < 2 or W < 2 is D4GS_EINVAL.  coverage = the sum of the in-bounds bilinear
+ * weights, mask [B,1,H,W] = coverage > 0.999 ? 1 : 0, out [B,C,H,W] = sample * mask.  Backward: v_input (zeroed here, then
+ * scattered into with float atomics: not bitwise reproducible) = the adjoint of the sampling under the mask; nothing flows to the
+ * flow or through the mask. */
+D4GS_API int d4gs_backwarp_fwd(const float *input, const float *flow, int32_t B, int32_t C, int32_t H, int32_t W, float *out, float *mask,
+                               void *stream);
+D4GS_API int d4gs_backwarp_bwd(const float *flow, const float *v_out, int32_t B, int32_t C, int32_t H, int32_t W, float *v_input,
+                               void *stream);
+/* Aligned L1 (AlignedLoss.forward without the flow network) for P pairs at once, with the same sampling:
+ *   losses[p] = mean over 3 H W of | warp(pred_p, flow_p) m_p mask_p - target_p m_p mask_p |
+ * pred, target [P,3,H,W], flow [P,2,H,W], m_p the coverage mask, mask [P,H,W] or NULL (ones).  partials: d4gs_aligned_l1_blocks(H, W)
+ * doubles per pair, 8-byte aligned; block partials are accumulated in double and added in a fixed order (the forward is bitwise
+ * reproducible).  Backward: v_loss [P] (device), v_pred [P,3,H,W] (zeroed here, then scattered into with float atomics) and, when
+ * not NULL, v_target [P,3,H,W] (written directly); sign(0) = 0.  Nothing flows to the flow or the masks. */
+D4GS_API int64_t d4gs_aligned_l1_blocks(int32_t H, int32_t W); /* 0: bad argument */
+D4GS_API int d4gs_aligned_l1_fwd(const float *pred, const float *flow, const float *target, const float *mask, int32_t P, int32_t H,
+                                 int32_t W, double *partials, float *losses, void *stream);
+D4GS_API int d4gs_aligned_l1_bwd(const float *pred, const float *flow, const float *target, const float *mask, const float *v_loss,
+                                 int32_t P, int32_t H, int32_t W, float *v_pred, float *v_target, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
