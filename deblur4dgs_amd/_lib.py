@@ -116,13 +116,18 @@ EXPORTS = (
     "d4gs_points_fwd", "d4gs_points_bwd", "d4gs_poses_fwd", "d4gs_poses_bwd", "d4gs_forward", "d4gs_backward", "d4gs_forward_cpu", "d4gs_backward_cpu", "d4gs_frame_workspace_bytes", "d4gs_frame_workspace_bytes_fwd", "d4gs_blend_shard_partial_fwd", "d4gs_blend_shard_finish_fwd",
     "d4gs_blend_shard_winner", "d4gs_blend_shard_bwd", "d4gs_control_stats", "d4gs_control_plan", "d4gs_gather_rows", "d4gs_camera_path_fwd", "d4gs_camera_path_bwd",
     "d4gs_pose_encode", "d4gs_pose_encode_bwd", "d4gs_move_model_fwd", "d4gs_move_model_bwd",
-    "d4gs_photometric_blocks", "d4gs_photometric_fwd", "d4gs_photometric_bwd", "d4gs_sh_partials_elems", "d4gs_sh_fwd", "d4gs_sh_bwd", "d4gs_query_sizes", "d4gs_profile_enable", "d4gs_profile_collect", "d4gs_measure_peaks",
+    "d4gs_photometric_blocks", "d4gs_photometric_maps_elems", "d4gs_photometric_fwd", "d4gs_photometric_bwd", "d4gs_sh_partials_elems", "d4gs_sh_fwd", "d4gs_sh_bwd", "d4gs_query_sizes", "d4gs_profile_enable", "d4gs_profile_collect", "d4gs_measure_peaks",
     "d4gs_adam_blocks", "d4gs_adam_step", "d4gs_adam_set_grads", "d4gs_adam_step_cpu",
     "d4gs_trimmed_scratch_words", "d4gs_masked_l1_fwd", "d4gs_masked_l1_bwd", "d4gs_trimmed_l1_fwd", "d4gs_trimmed_l1_bwd",
     "d4gs_gradient_loss_fwd", "d4gs_gradient_loss_bwd",
     "d4gs_correlation_fwd", "d4gs_correlation_bwd", "d4gs_backwarp_fwd", "d4gs_backwarp_bwd",
     "d4gs_aligned_l1_blocks", "d4gs_aligned_l1_fwd", "d4gs_aligned_l1_bwd",
 )
+
+# Appended to ABI 305 after A/B libraries of older trees were built.  The product library must have them (as every export; build()
+# checks it too); a library named by D4GS_LIB_PATH is held only to the entry points its run calls, so a raster A/B library
+# that predates one of these still loads, and calling the missing entry point through it raises.
+APPENDED = ("d4gs_photometric_maps_elems",)
 
 _lib = None
 
@@ -138,7 +143,8 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401  -- torch's bundled HIP runtime must be the one both sides use: load it first
         L = C.CDLL(LIB_PATH)
         for name in EXPORTS:
-            getattr(L, name)  # AttributeError if the symbol is missing
+            if not (name in APPENDED and os.environ.get("D4GS_LIB_PATH")):
+                getattr(L, name)  # AttributeError if the symbol is missing
         L.d4gs_last_error.restype = C.c_char_p
         L.d4gs_scan_ws_elems.restype = C.c_size_t
         L.d4gs_scan_ws_elems.argtypes = [C.c_int64]
@@ -184,6 +190,9 @@ def lib() -> C.CDLL:
         L.d4gs_query_sizes.argtypes = [P(Dims), P(Sizes)]
         L.d4gs_photometric_blocks.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         L.d4gs_photometric_blocks.restype = C.c_int64
+        if hasattr(L, "d4gs_photometric_maps_elems"):
+            L.d4gs_photometric_maps_elems.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+            L.d4gs_photometric_maps_elems.restype = C.c_int64
         L.d4gs_photometric_fwd.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp,
                                            vp, vp]
         L.d4gs_photometric_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,

@@ -4,110 +4,150 @@
 //     0.8 * F.l1_loss(pred * m, gt * m) + 0.2 * (1 - SSIM(pred * m, gt * m)),   SSIM = pytorch_msssim.SSIM(1.0, channel=3)
 // (pytorch-msssim 1.0.0: 11-tap sigma-1.5 Gaussian, separable, no padding; see oracle/photometric.py).  In eager
 // PyTorch one evaluation is ~25 launches forward and ~60 backward, three to four times per step; here it is one
-// tile kernel forward (loss partials + the three derivative maps dS/dmu1, dS/dE[x^2], dS/dE[xy]), a one-block ordered
-// sum, and one tile kernel backward (transposed separable filter of the maps + the L1 sign term).  Images are read
-// channel-last [B,H,W,C] exactly as the rasterizer writes them; the mask [B,H,W] multiplies both images.
+// tile kernel forward (loss partials + five maps per output pixel and channel), a one-block ordered sum, and one tile
+// kernel backward (transposed separable filter of the maps + the L1 sign term).  Images are read channel-last
+// [B,H,W,C] exactly as the rasterizer writes them; the mask [B,H,W] multiplies both images.
+//
+// Numerics.  On flat, bright or converged images the variances are ~1e-6 beside means ~1 and are
+// divided by C2 = 9e-4, so nothing here is ever formed from raw fp32 moments:
+//   * every 16x16 tile has a per-channel offset (ox, oy): the masked pred / gt value at its centre pixel, recomputed from
+//     the inputs wherever it is needed (identical bits in both passes, nothing stored);
+//   * the forward stages u = pred*m - ox, v = gt*m - oy (product and difference in double, rounded once to fp32) and
+//     takes the five window moments of (u, v) in double; s1 = E[uu] - E[u]^2 etc. and the whole per-pixel SSIM
+//     algebra stay in double, the luminance term as 1 - (mu1 - mu2)^2 / (mu1^2 + mu2^2 + C1);
+//   * maps hold, per output pixel p and channel, the fixed-sigma derivatives
+//         a = dL/dmu1 * CS,   b = L * dCS/ds1 = -S / B2,   e = L * (dCS/ds12 + 2 dCS/ds1) = 2 L (1 - CS) / B2
+//     and the means relative to the forward tile's offsets as E[u] - E[v] and E[v] (full relative precision in fp32;
+//     the difference is stored because it multiplies b, which is ~1e3 on flat regions, while E[v] multiplies e ~ 0);
+//   * dS(p)/dx(q) = w(p - q) [ a + 2 b ((x(q) - mu1(p)) - (y(q) - mu2(p))) + e (y(q) - mu2(p)) ]: the backward rewrites
+//     the means about ITS tile's offset while staging, filters t = a - 2 b (m1 - m2) - e m2, b and e, and combines
+//     Ft + 2 ((x - ox) - (y - oy)) Fb + (y - oy) Fe, the filter sums in double (where a tile holds a step between two flat
+//     levels, t and 2 (x - y) b are each ~40 and cancel).  When pred == gt bitwise, a, e and t are exactly 0 and so is
+//     the SSIM gradient;
+//   * the block partials are sums of 1 - S (not S), so a loss of 1e-4 keeps its relative precision.
 #include "common.h"
 
 namespace {
 
 constexpr int PW = 11, PT = 16, PH = PT + PW - 1;  // window, tile, tile + halo (26)
 constexpr int PC = 3;                                      // channels (the reference's SSIM is built for 3)
-__constant__ float c_win[PW] = {0.00102838f, 0.00759876f, 0.03600077f, 0.10936069f, 0.21300554f, 0.26601172f,
-                                0.21300554f, 0.10936069f, 0.03600077f, 0.00759876f, 0.00102838f};
-constexpr float SSIM_C1 = 1e-4f, SSIM_C2 = 9e-4f;
+constexpr int PM = 5;                                      // map floats per output pixel and channel: a, b, e, E[u] - E[v], E[v]
+// exp(-k^2 / 4.5) / sum, k = -5..5, in double (bitwise the oracle's window)
+__constant__ double c_wind[PW] = {0.00102838008447911, 0.007598758135239185, 0.03600077212843083, 0.10936068950970002,
+                                  0.2130055377112537,  0.26601172486179436,  0.2130055377112537,  0.10936068950970002,
+                                  0.03600077212843083, 0.007598758135239185, 0.00102838008447911};
+constexpr double SSIM_C1 = 1e-4, SSIM_C2 = 9e-4;
+
+// the offset of 16x16 tile (ty, tx) of image b: the masked value at its centre pixel (clamped into the image)
+__device__ __forceinline__ float tile_offset(const float *img, const float *mask, int b, int H, int W, int ty, int tx, int c) {
+  const int y = min(ty * PT + PT / 2, H - 1), x = min(tx * PT + PT / 2, W - 1);
+  const size_t p = ((size_t)b * H + y) * W + x;
+  return (float)((double)img[p * PC + c] * (double)(mask ? mask[p] : 1.f));
+}
 
 struct PhotoArgs {
   const float *pred, *gt, *mask;  // [B,H,W,C], [B,H,W,C], [B,H,W] or null
   int B, H, W, Ho, Wo, tiles_x, tiles_y;
-  float *maps;      // [B,Ho,Wo,C,3]
-  float *partials;  // [n_blocks,2]  {sum of ssim_map, sum of |x - y|}
+  float *maps;      // [B,Ho,Wo,C,PM]
+  float *partials;  // [n_blocks,2]  {sum of 1 - ssim_map, sum of |x - y|}
 };
 
 __global__ void __launch_bounds__(256) k_photo_fwd(const PhotoArgs a) {
-  __shared__ float sx[PH * PH * PC], sy[PH * PH * PC];
-  __shared__ float hbuf[5 * PH * PT * PC];  // horizontally filtered x, y, xx, yy, xy
-  __shared__ float red[2 * 4];
+  __shared__ float su[PH * PH * PC], sv[PH * PH * PC];  // pred*m - ox, gt*m - oy
+  __shared__ double hbuf[5 * PH * PT];                  // one channel: horizontally filtered u, v, uu, vv, uv
+  __shared__ double red[4];
+  __shared__ float redl[4];
   const int tid = threadIdx.x;
   const int b = blockIdx.z, ty0 = blockIdx.y * PT, tx0 = blockIdx.x * PT;
-  // stage the 26x26 input patch (masked).  Tiles cover the INPUT grid, so every input pixel's |x - y| is owned by
-  // exactly one block (its 16x16 top-left cells); output pixels exist only for oy < H - 10, ox < W - 10.
+  float offx[PC], offy[PC];
+#pragma unroll
+  for (int c = 0; c < PC; c++) {
+    offx[c] = tile_offset(a.pred, a.mask, b, a.H, a.W, blockIdx.y, blockIdx.x, c);
+    offy[c] = tile_offset(a.gt, a.mask, b, a.H, a.W, blockIdx.y, blockIdx.x, c);
+  }
+  // stage the 26x26 input patch (masked, centred).  Tiles cover the INPUT grid, so every input pixel's |x - y| is owned
+  // by exactly one block (its 16x16 top-left cells); output pixels exist only for oy < H - 10, ox < W - 10.  Cells
+  // outside the image are only ever read by windows of output pixels that do not exist.
   float l1 = 0.f;
-  const int own_h = PT, own_w = PT;
   for (int i = tid; i < PH * PH; i += 256) {
     const int ly = i / PH, lx = i - ly * PH;
     const int y = ty0 + ly, x = tx0 + lx;
-    float m = 0.f;
-    float px[PC] = {0.f, 0.f, 0.f}, gx[PC] = {0.f, 0.f, 0.f};
+    float u[PC] = {0.f, 0.f, 0.f}, v[PC] = {0.f, 0.f, 0.f};
     if (y < a.H && x < a.W) {
       const size_t p = ((size_t)b * a.H + y) * a.W + x;
-      m = a.mask ? a.mask[p] : 1.f;
+      const float m = a.mask ? a.mask[p] : 1.f;
 #pragma unroll
-      for (int c = 0; c < PC; c++) px[c] = a.pred[p * PC + c] * m, gx[c] = a.gt[p * PC + c] * m;
-      if (ly < own_h && lx < own_w) {
-#pragma unroll
-        for (int c = 0; c < PC; c++) l1 += fabsf(px[c] - gx[c]);
+      for (int c = 0; c < PC; c++) {
+        const float pv = a.pred[p * PC + c], gv = a.gt[p * PC + c];
+        u[c] = (float)((double)pv * (double)m - (double)offx[c]);
+        v[c] = (float)((double)gv * (double)m - (double)offy[c]);
+        if (ly < PT && lx < PT) l1 += fabsf(pv - gv) * fabsf(m);
       }
     }
 #pragma unroll
-    for (int c = 0; c < PC; c++) sx[i * PC + c] = px[c], sy[i * PC + c] = gx[c];
+    for (int c = 0; c < PC; c++) su[i * PC + c] = u[c], sv[i * PC + c] = v[c];
   }
-  __syncthreads();
-  // horizontal pass: 26 rows x 16 columns x 3 channels
-  for (int i = tid; i < PH * PT * PC; i += 256) {
-    const int c = i % PC, lx = (i / PC) % PT, ly = i / (PC * PT);
-    float hx = 0.f, hy = 0.f, hxx = 0.f, hyy = 0.f, hxy = 0.f;
-#pragma unroll
-    for (int k = 0; k < PW; k++) {
-      const float w = c_win[k], xv = sx[(ly * PH + lx + k) * PC + c], yv = sy[(ly * PH + lx + k) * PC + c];
-      hx += w * xv, hy += w * yv, hxx += w * xv * xv, hyy += w * yv * yv, hxy += w * xv * yv;
-    }
-    hbuf[0 * PH * PT * PC + i] = hx, hbuf[1 * PH * PT * PC + i] = hy, hbuf[2 * PH * PT * PC + i] = hxx;
-    hbuf[3 * PH * PT * PC + i] = hyy, hbuf[4 * PH * PT * PC + i] = hxy;
-  }
-  __syncthreads();
-  // vertical pass + SSIM map + derivative maps: one thread per output pixel, looping channels
   const int ly = tid / PT, lx = tid % PT;
   const int oy = ty0 + ly, ox = tx0 + lx;
-  float ssum = 0.f;
-  if (oy < a.Ho && ox < a.Wo) {
+  const bool live = oy < a.Ho && ox < a.Wo;
+  double osum = 0.0;  // sum of 1 - S
 #pragma unroll
-    for (int c = 0; c < PC; c++) {
-      float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+  for (int c = 0; c < PC; c++) {
+    __syncthreads();  // staging done (c == 0) / the previous channel's vertical pass done with hbuf
+    // horizontal pass: 26 rows x 16 columns
+    for (int i = tid; i < PH * PT; i += 256) {
+      const int hy = i / PT, hx = i - hy * PT;
+      double h[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int k = 0; k < PW; k++) {
-        const float w = c_win[k];
-        const int i = ((ly + k) * PT + lx) * PC + c;
-        mu1 += w * hbuf[i], mu2 += w * hbuf[PH * PT * PC + i], e11 += w * hbuf[2 * PH * PT * PC + i];
-        e22 += w * hbuf[3 * PH * PT * PC + i], e12 += w * hbuf[4 * PH * PT * PC + i];
+        const double w = c_wind[k], uv = su[(hy * PH + hx + k) * PC + c], vv = sv[(hy * PH + hx + k) * PC + c];
+        h[0] += w * uv, h[1] += w * vv, h[2] += w * (uv * uv), h[3] += w * (vv * vv), h[4] += w * (uv * vv);
       }
-      const float s1 = e11 - mu1 * mu1, s2 = e22 - mu2 * mu2, s12 = e12 - mu1 * mu2;
-      const float A1 = 2.f * mu1 * mu2 + SSIM_C1, A2 = 2.f * s12 + SSIM_C2;
-      const float B1 = mu1 * mu1 + mu2 * mu2 + SSIM_C1, B2 = s1 + s2 + SSIM_C2;
-      const float iB = 1.f / (B1 * B2);
-      const float S = A1 * A2 * iB;
-      ssum += S;
-      // derivatives w.r.t. mu1, E[x^2], E[xy] (sigma's expanded: s1 = e11 - mu1^2, s12 = e12 - mu1 mu2)
-      float *mp = a.maps + ((((size_t)b * a.Ho + oy) * a.Wo + ox) * PC + c) * 3;
-      mp[0] = 2.f * mu2 * (A2 - A1) * iB - S * 2.f * mu1 * (B2 - B1) * iB;
-      mp[1] = -S / B2;
-      mp[2] = 2.f * A1 * iB;
+#pragma unroll
+      for (int j = 0; j < 5; j++) hbuf[j * PH * PT + i] = h[j];
+    }
+    __syncthreads();
+    // vertical pass + SSIM map + derivative maps: one thread per output pixel
+    if (live) {
+      double eu = 0.0, ev = 0.0, euu = 0.0, evv = 0.0, euv = 0.0;
+#pragma unroll
+      for (int k = 0; k < PW; k++) {
+        const double w = c_wind[k];
+        const int i = (ly + k) * PT + lx;
+        eu += w * hbuf[i], ev += w * hbuf[PH * PT + i], euu += w * hbuf[2 * PH * PT + i];
+        evv += w * hbuf[3 * PH * PT + i], euv += w * hbuf[4 * PH * PT + i];
+      }
+      const double mu1 = (double)offx[c] + eu, mu2 = (double)offy[c] + ev;
+      const double d = ((double)offx[c] - (double)offy[c]) + (eu - ev);  // mu1 - mu2
+      const double s1 = euu - eu * eu, s2 = evv - ev * ev, s12 = euv - eu * ev;
+      const double iB1 = 1.0 / (mu1 * mu1 + mu2 * mu2 + SSIM_C1), iB2 = 1.0 / (s1 + s2 + SSIM_C2);
+      const double L = 1.0 - d * d * iB1;
+      const double ocs = (s1 + s2 - 2.0 * s12) * iB2;  // 1 - CS
+      const double S = L * (1.0 - ocs);
+      osum += (d * d * iB1 + ocs) - d * d * iB1 * ocs;  // 1 - S
+      float *mp = a.maps + ((((size_t)b * a.Ho + oy) * a.Wo + ox) * PC + c) * PM;
+      mp[0] = (float)(-2.0 * d * (mu2 * (mu1 + mu2) + SSIM_C1) * iB1 * iB1 * (1.0 - ocs));
+      mp[1] = (float)(-S * iB2);
+      mp[2] = (float)(2.0 * L * ocs * iB2);
+      mp[3] = (float)(eu - ev);
+      mp[4] = (float)ev;
     }
   }
   // block sums in a fixed order: lanes (shuffle tree), then the 4 waves
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ssum += __shfl_xor(ssum, o), l1 += __shfl_xor(l1, o);
-  if ((tid & 63) == 0) red[tid >> 6] = ssum, red[4 + (tid >> 6)] = l1;
+  for (int o = 32; o > 0; o >>= 1) osum += __shfl_xor(osum, o), l1 += __shfl_xor(l1, o);
+  if ((tid & 63) == 0) red[tid >> 6] = osum, redl[tid >> 6] = l1;
   __syncthreads();
   if (tid == 0) {
     const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    a.partials[blk * 2] = (red[0] + red[1]) + (red[2] + red[3]);
-    a.partials[blk * 2 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+    a.partials[blk * 2] = (float)((red[0] + red[1]) + (red[2] + red[3]));
+    a.partials[blk * 2 + 1] = (redl[0] + redl[1]) + (redl[2] + redl[3]);
   }
 }
 
-// loss[0] = w_l1 * l1 + w_ssim * (1 - ssim), loss[1] = l1, loss[2] = ssim; one block, ordered
-__global__ void __launch_bounds__(256) k_photo_finish(const float *partials, int n_blocks, float inv_nssim, float inv_nl1,
+// loss[0] = w_l1 * l1 + w_ssim * (1 - ssim), loss[1] = l1, loss[2] = ssim; one block, ordered.  The partials carry
+// 1 - ssim, and the loss is formed from it in double, so a small 1 - ssim is not rounded through an ssim near 1.
+__global__ void __launch_bounds__(256) k_photo_finish(const float *partials, int n_blocks, double inv_nssim, double inv_nl1,
                                                       float w_l1, float w_ssim, float *loss) {
   __shared__ double rs[256], rl[256];
   double s = 0.0, l = 0.0;
@@ -119,8 +159,8 @@ __global__ void __launch_bounds__(256) k_photo_finish(const float *partials, int
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const float ssim = (float)(rs[0] * inv_nssim), l1 = (float)(rl[0] * inv_nl1);
-    loss[0] = w_l1 * l1 + w_ssim * (1.f - ssim), loss[1] = l1, loss[2] = ssim;
+    const double dssim = rs[0] * inv_nssim, l1 = rl[0] * inv_nl1;
+    loss[0] = (float)((double)w_l1 * l1 + (double)w_ssim * dssim), loss[1] = (float)l1, loss[2] = (float)(1.0 - dssim);
   }
 }
 
@@ -131,48 +171,78 @@ struct PhotoBwdArgs {
   float *v_pred;
 };
 
-// dL/dpred(q) = m(q) * v * [ k_l1 sign(x - y) + k_ssim * sum_p w(p - q) (Da(p) + 2 x(q) D11(p) + y(q) D12(p)) ]
+// dL/dpred(q) = m(q) * v * [ k_l1 sign(x - y) + k_ssim * sum_p w(p - q) dS(p)/dx(q) ]   (see the head of this file)
 __global__ void __launch_bounds__(256) k_photo_bwd(const PhotoBwdArgs a) {
-  __shared__ float sm[PH * PH * PC * 3];  // maps patch: output pixels q - 10 .. q (zero outside the valid region)
-  __shared__ float hb[PH * PT * PC * 3];
+  __shared__ float sm[PH * PH * PC * 3];  // {t, b, e} of output pixels q - 10 .. q (zero outside the valid region)
+  __shared__ double hb[PH * PT * 3];  // one channel at a time; double: t and b are large where they cancel (flat regions)
+  __shared__ float so[2 * 2 * PC * 2];  // offsets of the forward tiles (by - 1 .. by) x (bx - 1 .. bx): [dy][dx][c][pred, gt]
   const int tid = threadIdx.x;
   const int b = blockIdx.z, ty0 = blockIdx.y * PT, tx0 = blockIdx.x * PT;
+  if (tid < 2 * 2 * PC * 2) {
+    const int k = tid & 1, c = (tid >> 1) % PC, t = tid / (2 * PC);
+    const int ty = max((int)blockIdx.y - 1 + (t >> 1), 0), tx = max((int)blockIdx.x - 1 + (t & 1), 0);
+    so[tid] = tile_offset(k ? a.gt : a.pred, a.mask, b, a.H, a.W, ty, tx, c);
+  }
+  __syncthreads();
   for (int i = tid; i < PH * PH; i += 256) {
     const int ly = i / PH, lx = i - ly * PH;
     const int oy = ty0 + ly - (PW - 1), ox = tx0 + lx - (PW - 1);
     const bool in = oy >= 0 && ox >= 0 && oy < a.Ho && ox < a.Wo;
-    const float *mp = a.maps + (((size_t)b * a.Ho + (in ? oy : 0)) * a.Wo + (in ? ox : 0)) * PC * 3;
+    if (in) {
+      const float *mp = a.maps + (((size_t)b * a.Ho + oy) * a.Wo + ox) * PC * PM;
+      const int t = ((oy / PT) - ((int)blockIdx.y - 1)) * 2 + ((ox / PT) - ((int)blockIdx.x - 1));  // the tile that wrote p
 #pragma unroll
-    for (int j = 0; j < PC * 3; j++) sm[i * PC * 3 + j] = in ? mp[j] : 0.f;
-  }
-  __syncthreads();
-  // horizontal (transposed): input column x gathers output columns x - 10 .. x with weight w[x - ox]
-  for (int i = tid; i < PH * PT * PC * 3; i += 256) {
-    const int j = i % (PC * 3), lx = (i / (PC * 3)) % PT, ly = i / (PC * 3 * PT);
-    float acc = 0.f;
+      for (int c = 0; c < PC; c++) {
+        const float ma = mp[c * PM], mb = mp[c * PM + 1], me = mp[c * PM + 2];
+        // about this block's offsets: mu1 - mu2 (from the stored difference, so that it keeps its precision where the forward
+        // tile's offset is far from the local level) and mu2: (forward tile's offset - ours) + stored mean
+        const double ox1 = so[(t * PC + c) * 2], oy1 = so[(t * PC + c) * 2 + 1];
+        const double ox0 = so[(3 * PC + c) * 2], oy0 = so[(3 * PC + c) * 2 + 1];
+        const double m12 = ((ox1 - oy1) - (ox0 - oy0)) + (double)mp[c * PM + 3];
+        const double m2 = (oy1 - oy0) + (double)mp[c * PM + 4];
+        sm[(i * PC + c) * 3] = (float)((double)ma - 2.0 * (double)mb * m12 - (double)me * m2);
+        sm[(i * PC + c) * 3 + 1] = mb, sm[(i * PC + c) * 3 + 2] = me;
+      }
+    } else {
 #pragma unroll
-    for (int k = 0; k < PW; k++) acc += c_win[PW - 1 - k] * sm[(ly * PH + lx + k) * PC * 3 + j];
-    hb[i] = acc;
+      for (int j = 0; j < PC * 3; j++) sm[i * PC * 3 + j] = 0.f;
+    }
   }
   __syncthreads();
   const int ly = tid / PT, lx = tid % PT;
   const int y = ty0 + ly, x = tx0 + lx;
-  if (y >= a.H || x >= a.W) return;
-  const size_t p = ((size_t)b * a.H + y) * a.W + x;
+  const bool live = y < a.H && x < a.W;
+  const size_t p = ((size_t)b * a.H + (live ? y : 0)) * a.W + (live ? x : 0);
   const float m = a.mask ? a.mask[p] : 1.f;
   const float v = a.v_loss[0];
 #pragma unroll
   for (int c = 0; c < PC; c++) {
-    float da = 0.f, d11 = 0.f, d12 = 0.f;
+    // horizontal (transposed): input column x gathers output columns x - 10 .. x with weight w[x - ox]
+    for (int i = tid; i < PH * PT * 3; i += 256) {
+      const int j = i % 3, hx = (i / 3) % PT, hy = i / (3 * PT);
+      double acc = 0.0;
 #pragma unroll
-    for (int k = 0; k < PW; k++) {
-      const float w = c_win[PW - 1 - k];
-      const float *h = hb + (((ly + k) * PT + lx) * PC + c) * 3;
-      da += w * h[0], d11 += w * h[1], d12 += w * h[2];
+      for (int k = 0; k < PW; k++) acc += c_wind[PW - 1 - k] * (double)sm[((hy * PH + hx + k) * PC + c) * 3 + j];
+      hb[i] = acc;
     }
-    const float xv = a.pred[p * PC + c] * m, yv = a.gt[p * PC + c] * m;
-    const float sgn = xv > yv ? 1.f : (xv < yv ? -1.f : 0.f);
-    a.v_pred[p * PC + c] = m * v * (a.k_l1 * sgn + a.k_ssim * (da + 2.f * xv * d11 + yv * d12));
+    __syncthreads();
+    if (live) {
+      double ft = 0.0, fb = 0.0, fe = 0.0;
+#pragma unroll
+      for (int k = 0; k < PW; k++) {
+        const double w = c_wind[PW - 1 - k];
+        const double *h = hb + ((ly + k) * PT + lx) * 3;
+        ft += w * h[0], fb += w * h[1], fe += w * h[2];
+      }
+      const float pv = a.pred[p * PC + c], gv = a.gt[p * PC + c];
+      const double dx = (double)pv * (double)m - (double)so[(3 * PC + c) * 2];
+      const double dy = (double)gv * (double)m - (double)so[(3 * PC + c) * 2 + 1];
+      const float dl = (pv - gv) * m;  // sign(x - y) with x = pred m, y = gt m
+      const float sgn = dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f);
+      const float gs = (float)(ft + 2.0 * (dx - dy) * fb + dy * fe);
+      a.v_pred[p * PC + c] = m * v * (a.k_l1 * sgn + a.k_ssim * gs);
+    }
+    __syncthreads();  // hb is rewritten for the next channel
   }
 }
 
@@ -193,7 +263,7 @@ int d4gs_photometric_fwd_impl(const float *pred, const float *gt, const float *m
   if (rc) return rc;
   const int nb = a.tiles_x * a.tiles_y * B;
   ProfScope ps("k_photo_finish", stream);
-  k_photo_finish<<<1, 256, 0, stream>>>(partials, nb, 1.f / ((float)B * PC * a.Ho * a.Wo), 1.f / ((float)B * PC * H * W), w_l1,
+  k_photo_finish<<<1, 256, 0, stream>>>(partials, nb, 1.0 / ((double)B * PC * a.Ho * a.Wo), 1.0 / ((double)B * PC * H * W), w_l1,
                                         w_ssim, loss);
   return d4gs_check_launch("k_photo_finish");
 }
@@ -214,4 +284,8 @@ int d4gs_photometric_bwd_impl(const float *pred, const float *gt, const float *m
 
 extern "C" int64_t d4gs_photometric_blocks(int32_t B, int32_t H, int32_t W) {
   return (int64_t)B * ((W + PT - 1) / PT) * ((H + PT - 1) / PT);
+}
+
+extern "C" int64_t d4gs_photometric_maps_elems(int32_t B, int32_t H, int32_t W) {
+  return H < PW || W < PW ? 0 : (int64_t)B * (H - (PW - 1)) * (W - (PW - 1)) * PC * PM;
 }

@@ -35,8 +35,10 @@ class PhotometricFn(torch.autograd.Function):
         g = gt.detach().float().contiguous()
         m = None if mask is None else mask.detach().float().reshape(B, H, W).contiguous()
         lib = L.lib()
+        if not hasattr(lib, "d4gs_photometric_maps_elems"):  # only an override library can lack it (_lib.APPENDED)
+            raise RuntimeError(f"{L.LIB_PATH} predates d4gs_photometric_maps_elems: its photometric kernels use another maps layout")
         nb = lib.d4gs_photometric_blocks(B, H, W)
-        maps = torch.empty(B, H - 10, W - 10, 3, 3, device=p.device, dtype=torch.float32)
+        maps = torch.empty(lib.d4gs_photometric_maps_elems(B, H, W), device=p.device, dtype=torch.float32)
         scratch = torch.empty(2 * nb + 3, device=p.device, dtype=torch.float32)
         stream = C.c_void_p(L.raw_stream(p.device.index))
         L.check(lib.d4gs_photometric_fwd(_p(p), _p(g), _p(m), B, H, W, Cc, w_l1, w_ssim, _p(maps), _p(scratch),

@@ -417,9 +417,11 @@ D4GS_API int d4gs_move_model_bwd(const D4gsMoveModelParams *p, const D4gsMoveMod
  *   loss = w_l1 * mean|pred*m - gt*m| + w_ssim * (1 - SSIM(pred*m, gt*m)),
  * SSIM = pytorch_msssim.SSIM(data_range=1, size_average=True, channel=3) [11-tap sigma-1.5 window, no padding].
  * pred, gt [B,H,W,3] channel-last; mask [B,H,W] or NULL.  Forward: loss[3] = {loss, l1, ssim} (device), plus what the
- * backward needs: maps [B,H-10,W-10,3,3], partials [d4gs_photometric_blocks(B,H,W), 2] scratch.  Backward:
- * v_pred [B,H,W,3] = dL/dpred * v_loss[0] (v_loss is a device scalar). */
+ * backward needs: maps [d4gs_photometric_maps_elems(B,H,W)] floats (five per output pixel and channel, [B,H-10,W-10,3,5]: it was
+ * three before the variances were taken about a local offset; callers size it with the query, never by hand) and partials
+ * [d4gs_photometric_blocks(B,H,W), 2] scratch.  Backward: v_pred [B,H,W,3] = dL/dpred * v_loss[0] (v_loss is a device scalar). */
 D4GS_API int64_t d4gs_photometric_blocks(int32_t B, int32_t H, int32_t W);
+D4GS_API int64_t d4gs_photometric_maps_elems(int32_t B, int32_t H, int32_t W); /* 0 if H or W < 11 */
 D4GS_API int d4gs_photometric_fwd(const float *pred, const float *gt, const float *mask, int32_t B, int32_t H, int32_t W, int32_t C,
                          float w_l1, float w_ssim, float *maps, float *partials, float *loss, void *stream);
 D4GS_API int d4gs_photometric_bwd(const float *pred, const float *gt, const float *mask, const float *maps, const float *v_loss,
