@@ -1,13 +1,17 @@
-"""Autograd plumbing around libd4gs.so: two `torch.autograd.Function`s that own allocation and enqueue the
+"""Autograd plumbing around libd4gs.so: four `torch.autograd.Function`s that own allocation and enqueue the
 HIP kernels on torch's current stream.
 
   ProjectFn   leaf params (+ bases, times, camera deltas, viewmat)  ->  means2d, conics, depths  [S,N,...],
               activated opacities / colour table.   fwd: d4gs_project_fwd     bwd: d4gs_project_bwd
   RasterFn    those per-instance tensors                            ->  render_colors [S,H,W,D'], alphas
               fwd: d4gs_bin_sort + d4gs_raster_fwd                   bwd: d4gs_raster_bwd
+  FrameFn     the leaves -> blended frame, accumulation, renders, alphas: the whole staged chain (and the blend) as ONE
+              node over one C call each way.   fwd: d4gs_forward     bwd: d4gs_backward
+  PosesFn     the leaves at B times -> deformed means / quats / transforms.   fwd: d4gs_poses_fwd   bwd: d4gs_poses_bwd
 
-`means2d` is a real autograd intermediate between the two, so `means2d.retain_grad()` / `.grad` behave exactly as
-with gsplat's `info["means2d"]` (reference flow3d/scene_model.py:456-461, flow3d/trainer.py:975).
+`means2d` is a real autograd intermediate between ProjectFn and RasterFn, so `means2d.retain_grad()` / `.grad` behave
+exactly as with gsplat's `info["means2d"]` (reference flow3d/scene_model.py:456-461, flow3d/trainer.py:975); FrameFn
+deposits that gradient in a side channel (`State.xys_sink`).  `_sized_launch` is the list-size protocol all renders share.
 
 PyTorch here is plumbing (device memory, streams, autograd graph); all arithmetic happens in the HIP library.
 There is no eager / CPU fallback: tensors must live on a ROCm device.
@@ -17,8 +21,10 @@ from __future__ import annotations
 import os
 
 import collections
+import contextlib
 import ctypes as C
 import threading
+import warnings
 from dataclasses import dataclass, field, replace
 
 import torch
@@ -168,9 +174,42 @@ def _sort_class(max_tile: int) -> int:
     return 0
 
 
+def _warm_capacity(n: int) -> int:
+    """The list capacity a render launches with once an earlier render of its shape measured n intersections."""
+    return n + n // 4 + 4096
+
+
+def _measured_count(cap: int) -> float:
+    return (cap - 4096) / 1.25  # (what a _warm_capacity was derived from)
+
+
+def _lazy_keys(cap: int, lists: int, scale: float = 1.0) -> float:
+    """scale x the keys per tile list as the lazy-sort decisions see them: the 4096 of `_warm_capacity` is deliberately LEFT IN the
+    capacity - LAZY_AUTO_KEYS and the near_target factor were tuned with this arithmetic, and taking it out would change which
+    scenes sort lazily (a change of behaviour, to be made with measurements)."""
+    return scale * cap / 1.25 / lists
+
+
+_Counts = collections.namedtuple("_Counts", "n max_tile sampled live")  # D4gsProjOut.n_isect: intersections, longest tile list, live-row sample
+
+
+def _read_counts(host_n) -> _Counts:
+    return _Counts(*host_n.tolist())
+
+
+def _fits(n: int, max_tile: int, cap: int, hint: int) -> bool:
+    """Did a render that counted (n, max_tile) fit lists of capacity `cap` sorted in class `hint` (0: every class was launched)?
+    One that did not composited nothing: its kernels skipped their work."""
+    return n <= cap and not (hint > 0 and max_tile > hint)
+
+
 def _size_key(dev, S, N, W, H):
     shift = max(N.bit_length() - 2, 0)
     return (dev.index, S, W, H, (N >> shift) << shift)
+
+
+def _shape_key(dev, cfg):
+    return _size_key(dev, cfg.S, cfg.N, cfg.width, cfg.height)
 
 
 def _list_key(dev, cfg):
@@ -178,7 +217,7 @@ def _list_key(dev, cfg):
     RESOLVED exact-tiles flag.  Lists binned with D4GS_EXACT_TILES are 15-40 % shorter than the rectangles' (and may fall in a
     smaller sort class), so a capacity measured under one flag says nothing about the other (a shared key let an
     `auto` on -> off flip launch a deferred render at the stale, too small capacity).  The live fraction stays per shape."""
-    return _size_key(dev, cfg.S, cfg.N, cfg.width, cfg.height) + (bool(cfg.exact_tiles and cfg.exact_cull),)
+    return _shape_key(dev, cfg) + (bool(cfg.exact_tiles and cfg.exact_cull),)
 
 
 def _guess_drop(key):
@@ -244,15 +283,14 @@ _XT_ON: dict = {}  # size key -> bool: the shape's current choice (hysteresis: t
 
 def resolve_lazy(cfg, dev):
     """Fix cfg.lazy_sort / cfg.near_target / cfg.exact_tiles for one render (once: forward and backward must agree on D4gsDims.flags)."""
+    key = _shape_key(dev, cfg)
+    with _SIZE_LOCK:
+        live, was = _LIVE_FRAC.get(key), _XT_ON.get(key, False)
     if cfg.exact_tiles is None:
         cfg.exact_tiles = EXACT_TILES == "1"
-        if EXACT_TILES == "auto":  # the list capacity of the shape is 1.25 x the previous render's count (+ 4096)
-            key = _size_key(dev, cfg.S, cfg.N, cfg.width, cfg.height)
-            with _SIZE_LOCK:
-                was = _XT_ON.get(key, False)
-                live = _LIVE_FRAC.get(key)
+        if EXACT_TILES == "auto":
             guess = _guess_get(key + (was,))  # the count measured under the flag the shape's last render ran with
-            per_inst = ((guess[0] - 4096) / 1.25 / (cfg.S * max(cfg.N, 1))) if guess else 0.0
+            per_inst = _measured_count(guess[0]) / (cfg.S * max(cfg.N, 1)) if guess else 0.0
             # on from 3.5 per instance, off again below 2.1 (the test itself shortens the lists it is decided from)
             on = per_inst >= (0.6 * EXACT_TILES_FROM if was else EXACT_TILES_FROM)
             # ... but never for few-tile launches (their depth-segmented backward places its hand-offs by list length: shorter
@@ -272,24 +310,17 @@ def resolve_lazy(cfg, dev):
                     _XT_ON.clear()
                 _XT_ON[key] = on
             cfg.exact_tiles = on
+    guess = _guess_get(_list_key(dev, cfg))  # (the lists' key carries the exact-tiles flag: known only now)
+    tw, th = cfg.tiles
+    lists = max(cfg.S * tw * th, 1)
     if cfg.lazy_sort is None:
         cfg.lazy_sort = LAZY_SORT == "1"
         if LAZY_SORT == "auto":
-            key = _size_key(dev, cfg.S, cfg.N, cfg.width, cfg.height)
-            with _SIZE_LOCK:
-                f = _LIVE_FRAC.get(key)
-            guess = _guess_get(_list_key(dev, cfg))
-            tw, th = cfg.tiles
-            avg = (guess[0] / 1.25 / max(cfg.S * tw * th, 1)) if guess else 0.0
-            cfg.lazy_sort = f is not None and f < LAZY_AUTO_LIVE and avg >= LAZY_AUTO_KEYS
-    if cfg.lazy_sort and cfg.near_target <= 0:
-        key = _size_key(dev, cfg.S, cfg.N, cfg.width, cfg.height)
-        with _SIZE_LOCK:
-            f = _LIVE_FRAC.get(key)
-        guess = _guess_get(_list_key(dev, cfg))
-        tw, th = cfg.tiles
-        if f is not None and guess:  # about 2.5 x the entries a tile consumed on the previous render of the shape
-            cfg.near_target = max(256, int(2.5 * f * guess[0] / 1.25 / max(cfg.S * tw * th, 1)))
+            avg = _lazy_keys(guess[0], lists) if guess else 0.0
+            cfg.lazy_sort = live is not None and live < LAZY_AUTO_LIVE and avg >= LAZY_AUTO_KEYS
+    if cfg.lazy_sort and cfg.near_target <= 0 and live is not None and guess:
+        # about 2.5 x the entries a tile consumed on the previous render of the shape
+        cfg.near_target = max(256, int(_lazy_keys(guess[0], lists, 2.5 * live)))
     return cfg
 
 
@@ -307,7 +338,7 @@ def row_mode_for(cfg, dev):
     if BWD_ROWS != "auto":
         return {"dense": L.ROWS_DENSE, "sparse": L.ROWS_SPARSE}[BWD_ROWS]
     with _SIZE_LOCK:
-        f = _LIVE_FRAC.get(_size_key(dev, cfg.S, cfg.N, cfg.width, cfg.height))
+        f = _LIVE_FRAC.get(_shape_key(dev, cfg))
     if f is None:
         return L.ROWS_AUTO
     return L.ROWS_SPARSE if f < LIVE_SPARSE_BELOW else L.ROWS_DENSE
@@ -337,25 +368,25 @@ def _deferred_poll(key, block: bool = False, keep_last: int = 0):
     last, bad = None, None
     for host_n, ev, cap, hint in ready:
         ev.synchronize()
-        n, max_tile, sampled, live = host_n.tolist()
-        if n <= cap and not (hint > 0 and max_tile > hint):  # (an overflowed render composited nothing)
-            _live_put(key, live, sampled)
+        last = _read_counts(host_n)
+        if _fits(last.n, last.max_tile, cap, hint):
+            _live_put(key, last.live, last.sampled)
+        elif bad is None:
+            bad = (last, cap, hint)
         with _SIZE_LOCK:  # the copy has landed and been read: the pinned pair can carry the next count
             if len(_PINNED_FREE) < 64:
                 _PINNED_FREE.append(host_n)
-        last = (n, max_tile)
-        if (n > cap or (hint > 0 and max_tile > hint)) and bad is None:
-            bad = (n, max_tile, cap, hint)
-    if last is not None:
-        _guess_put(key, (last[0] + last[0] // 4 + 4096, _sort_class(last[1])))
+    if last is None:
+        return None
+    _guess_put(key, (_warm_capacity(last.n), _sort_class(last.max_tile)))  # the newest count sizes the next render ...
     if bad is not None:
-        if bad[0] + bad[0] // 4 + 4096 > (last[0] + last[0] // 4 + 4096):
-            _guess_put(key, (bad[0] + bad[0] // 4 + 4096, _sort_class(max(bad[1], last[1]))))
-        n, max_tile, cap, hint = bad
-        raise RuntimeError(f"deblur4dgs_amd: a render with deferred_size_check needed {n} intersections (longest tile "
-                           f"list {max_tile}) but its lists were sized for {cap} (class {hint}): that render's output "
+        c, cap, hint = bad
+        if _warm_capacity(c.n) > _warm_capacity(last.n):  # ... unless the overflowed one needed more
+            _guess_put(key, (_warm_capacity(c.n), _sort_class(max(c.max_tile, last.max_tile))))
+        raise RuntimeError(f"deblur4dgs_amd: a render with deferred_size_check needed {c.n} intersections (longest tile "
+                           f"list {c.max_tile}) but its lists were sized for {cap} (class {hint}): that render's output "
                            "was INVALID (its kernels skipped the work).  Re-run the step; the size guess is updated.")
-    return last
+    return last.n, last.max_tile
 
 
 _WATCH_TLS = threading.local()  # .watch: the GraphWatch whose capture is in progress ON THIS THREAD (GraphWatch.capturing());
@@ -387,19 +418,14 @@ class GraphWatch:
             raise RuntimeError("GraphWatch: more renders in the captured step than max_renders")
         return self._pool.pop()
 
+    @contextlib.contextmanager
     def capturing(self):
-        import contextlib
-
-        @contextlib.contextmanager
-        def cm():
-            assert _graph_watch() is None, "nested GraphWatch captures"
-            _WATCH_TLS.watch = self
-            try:
-                yield self
-            finally:
-                _WATCH_TLS.watch = None
-
-        return cm()
+        assert _graph_watch() is None, "nested GraphWatch captures"
+        _WATCH_TLS.watch = self
+        try:
+            yield self
+        finally:
+            _WATCH_TLS.watch = None
 
     def replayed(self):
         self.event = torch.cuda.Event()
@@ -412,16 +438,16 @@ class GraphWatch:
         self.event = None
         bad = None
         for key, host_n, cap, hint in self.recs:
-            n, max_tile, sampled, live = host_n.tolist()
-            if n > cap or (hint > 0 and max_tile > hint):
-                _guess_put(key, (n + n // 4 + 4096, _sort_class(max_tile)))
-                bad = bad or (n, max_tile, cap, hint)
+            c = _read_counts(host_n)
+            if _fits(c.n, c.max_tile, cap, hint):
+                _live_put(key, c.live, c.sampled)
             else:
-                _live_put(key, live, sampled)
+                _guess_put(key, (_warm_capacity(c.n), _sort_class(c.max_tile)))
+                bad = bad or (c, cap, hint)
         if bad is not None:
-            n, max_tile, cap, hint = bad
-            raise RuntimeError(f"deblur4dgs_amd: a render replayed from a HIP graph needed {n} intersections (longest tile list "
-                               f"{max_tile}) but the graph was captured with lists for {cap} (class {hint}): that replay's output "
+            c, cap, hint = bad
+            raise RuntimeError(f"deblur4dgs_amd: a render replayed from a HIP graph needed {c.n} intersections (longest tile list "
+                               f"{c.max_tile}) but the graph was captured with lists for {cap} (class {hint}): that replay's output "
                                "was INVALID (its kernels skipped the work).  Re-capture the step; the size guess is updated.")
 
 
@@ -452,6 +478,20 @@ def _pinned_counts(dev):
         return _PINNED[k]
 
 
+def _pinned_take():
+    """A pinned int64[4] for the counts of one deferred render: recycled once read (pin_memory() costs ~0.1 ms)."""
+    with _SIZE_LOCK:
+        if _PINNED_FREE:
+            return _PINNED_FREE.pop()
+    return torch.empty(4, dtype=torch.int64).pin_memory()
+
+
+def _copy_counts(n_isect, host_n, dev):
+    # a KERNEL stores the counts: a device-to-host copy would be a DMA-engine trip the backward's kernels wait for.  Captured, it is a
+    # graph node writing memory pinned BEFORE the capture (no allocation, no host-allocator bookkeeping on a capturing stream)
+    L.check(L.lib().d4gs_copy_counts(L.ptr(n_isect), host_n.data_ptr(), raw_stream(dev.index)), "copy_counts")
+
+
 def _need_gpu(t: torch.Tensor):
     if not t.is_cuda:
         raise RuntimeError("deblur4dgs_amd runs on an MI355X (ROCm) device only; got a CPU tensor (no CPU fallback)")
@@ -461,14 +501,49 @@ def _f32c(t):
     return None if t is None else t.detach().to(torch.float32).contiguous()
 
 
-def _proj_structs(st: State):
-    pin = L.fill(L.ProjIn(), **st.proj_in)
-    pout = L.fill(L.ProjOut(), **st.proj_out)
-    return pin, pout
-
-
 _PROJ_IN = ("means", "quats", "scales", "opacities", "colors", "motion_coefs", "rots", "transls", "times", "RTs", "viewmat",
             "Kmat")
+_LEAVES = _PROJ_IN[:-1]  # what a render differentiates, in the order its autograd functions take and return them
+
+
+def _proj_in(*leaves) -> dict:
+    """D4gsProjIn's tensors from the twelve leaf arguments of a render.  The backward re-reads them.  `_f32c` hands out detached ALIASES
+    of f32-contiguous leaves, which share the leaf's version counter: routing them through save_for_backward makes an in-place update
+    between forward and backward (optimizer.step, a control step) raise, as stock autograd / gsplat would, instead of silently
+    differentiating modified parameters.  (Writes through `.data` bypass version counters everywhere.)"""
+    assert len(leaves) == len(_PROJ_IN)
+    return dict(zip(_PROJ_IN, map(_f32c, leaves)))
+
+
+def _needs(*leaves) -> list:
+    return [t is not None and t.requires_grad for t in leaves]
+
+
+def _only_needed(grads, needs) -> list:
+    return [g if need else None for g, need in zip(grads, needs)]
+
+
+def _leaf_grads(cfg: RenderCfg, dims, pi: dict, dev, with_partials: bool) -> dict:
+    """D4gsLeafGrads' buffers: cfg.grad_arena's tensor of the name where it has the shape and dtype and is contiguous, a fresh one
+    otherwise; `with_partials`: plus d4gs_project_bwd's scratch (d4gs_backward carves its own from the workspace)."""
+    f32 = dict(dtype=torch.float32, device=dev)
+    arena = cfg.grad_arena or {}
+    dyn = cfg.G > 0
+
+    def buf(name, *shape):
+        t = arena.get(name)
+        if t is not None and t.shape == torch.Size(shape) and t.dtype == torch.float32 and t.is_contiguous():
+            return t.view(shape)  # a fresh alias: autograd takes it over as the leaf's .grad without a copy
+        return torch.empty(*shape, **f32)
+
+    return dict(
+        v_means=buf("means", cfg.N, 3), v_quats=buf("quats", cfg.N, 4), v_scales=buf("scales", cfg.N, 3),
+        v_opacities=buf("opacities", cfg.N), v_colors=buf("colors", cfg.N, cfg.D),
+        v_motion_coefs=buf("motion_coefs", cfg.G, cfg.K) if dyn else None,
+        v_rots=buf("rots", cfg.K, cfg.T, 6) if dyn else None, v_transls=buf("transls", cfg.K, cfg.T, 3) if dyn else None,
+        v_times=buf("times", cfg.S) if dyn else None, v_RTs=buf("RTs", cfg.S, 3, 4) if pi["RTs"] is not None else None,
+        v_viewmat=buf("viewmat", 4, 4),
+        partials=torch.empty(L.lib().d4gs_bwd_partials_elems(C.byref(dims)), **f32) if with_partials else None)
 
 
 class ProjectFn(torch.autograd.Function):
@@ -482,10 +557,7 @@ class ProjectFn(torch.autograd.Function):
         tw, th = cfg.tiles
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
-        st.proj_in = dict(means=_f32c(means), quats=_f32c(quats), scales=_f32c(scales), opacities=_f32c(opacities),
-                          colors=_f32c(colors), motion_coefs=_f32c(motion_coefs), rots=_f32c(rots),
-                          transls=_f32c(transls), times=_f32c(times), RTs=_f32c(RTs), viewmat=_f32c(viewmat),
-                          Kmat=_f32c(Kmat))
+        st.proj_in = _proj_in(means, quats, scales, opacities, colors, motion_coefs, rots, transls, times, RTs, viewmat, Kmat)
         lib = L.lib()
         st.proj_out = dict(
             means2d=torch.empty(S, N, 2, **f32), depths=torch.empty(S, N, **f32), conics=torch.empty(S, N, 3, **f32),
@@ -501,16 +573,11 @@ class ProjectFn(torch.autograd.Function):
             compensations=torch.empty(S, N, **f32) if cfg.antialiased else None,
         )
         dims = cfg.dims()
-        pin, pout = _proj_structs(st)
+        pin, pout = L.fill(L.ProjIn(), **st.proj_in), L.fill(L.ProjOut(), **st.proj_out)
         L.check(lib.d4gs_project_fwd(C.byref(dims), C.byref(pin), C.byref(pout), _stream()), "d4gs_project_fwd")
         ctx.st = st
-        # The backward re-reads the leaves.  `_f32c` hands out detached ALIASES of f32-contiguous leaves, which share the
-        # leaf's version counter: routing them through save_for_backward makes an in-place update between forward and
-        # backward (optimizer.step, a control step) raise, as stock autograd / gsplat would, instead of silently
-        # differentiating modified parameters.  (Writes through `.data` bypass version counters everywhere.)
-        ctx.save_for_backward(*[st.proj_in[k] for k in _PROJ_IN])
-        ctx.needs = [t is not None and t.requires_grad for t in
-                     (means, quats, scales, opacities, colors, motion_coefs, rots, transls, times, RTs, viewmat)]
+        ctx.save_for_backward(*st.proj_in.values())  # version-checked (see _proj_in)
+        ctx.needs = _needs(means, quats, scales, opacities, colors, motion_coefs, rots, transls, times, RTs, viewmat)
         o = st.proj_out
         # return ALIASES of the buffers: autograd attaches grad_fn (-> ctx -> st) to the returned objects, and st must
         # not hold those objects or every call leaks a reference cycle until the cyclic GC runs
@@ -524,34 +591,13 @@ class ProjectFn(torch.autograd.Function):
         cfg = st.cfg
         o = st.proj_out
         dev = o["means2d"].device
-        f32 = dict(dtype=torch.float32, device=dev)
         z = lambda g, ref: torch.zeros_like(ref) if g is None else g.to(torch.float32).contiguous()
         v_means2d, v_conics, v_depths = z(v_means2d, o["means2d"]), z(v_conics, o["conics"]), z(v_depths, o["depths"])
         v_opac_act, v_ctab = z(v_opac_act, o["opac_act"]), z(v_ctab, o["ctab"])
         lib = L.lib()
         dims = cfg.dims()
         pi = dict(zip(_PROJ_IN, ctx.saved_tensors))  # raises if a leaf was modified in place since the forward
-        dyn = cfg.G > 0
-        arena = cfg.grad_arena or {}
-
-        def buf(name, *shape):
-            t = arena.get(name)
-            if t is not None and t.shape == torch.Size(shape) and t.dtype == torch.float32 and t.is_contiguous():
-                return t.view(shape)  # a fresh alias: autograd takes it over as the leaf's .grad without a copy
-            return torch.empty(*shape, **f32)
-
-        g = dict(
-            v_means=buf("means", cfg.N, 3), v_quats=buf("quats", cfg.N, 4),
-            v_scales=buf("scales", cfg.N, 3), v_opacities=buf("opacities", cfg.N),
-            v_colors=buf("colors", cfg.N, cfg.D),
-            v_motion_coefs=buf("motion_coefs", cfg.G, cfg.K) if dyn else None,
-            v_rots=buf("rots", cfg.K, cfg.T, 6) if dyn else None,
-            v_transls=buf("transls", cfg.K, cfg.T, 3) if dyn else None,
-            v_times=buf("times", cfg.S) if dyn else None,
-            v_RTs=buf("RTs", cfg.S, 3, 4) if pi["RTs"] is not None else None,
-            v_viewmat=buf("viewmat", 4, 4),
-            partials=torch.empty(lib.d4gs_bwd_partials_elems(C.byref(dims)), **f32),
-        )
+        g = _leaf_grads(cfg, dims, pi, dev, with_partials=True)
         pin = L.fill(L.ProjIn(), **pi)
         pout = L.fill(L.ProjOut(), **st.proj_out)
         lg = L.fill(L.LeafGrads(), **g)
@@ -559,10 +605,7 @@ class ProjectFn(torch.autograd.Function):
         L.check(lib.d4gs_project_bwd(C.byref(dims), C.byref(pin), C.byref(pout), vp(v_means2d), vp(v_conics),
                                      vp(v_depths), vp(v_opac_act), vp(v_ctab), C.byref(lg), _stream()),
                 "d4gs_project_bwd")
-        outs = [g["v_means"], g["v_quats"], g["v_scales"], g["v_opacities"], g["v_colors"], g["v_motion_coefs"],
-                g["v_rots"], g["v_transls"], g["v_times"], g["v_RTs"], g["v_viewmat"]]
-        outs = [x if need else None for x, need in zip(outs, ctx.needs)]
-        return (None, *outs, None)
+        return (None, *_only_needed([g["v_" + k] for k in _LEAVES], ctx.needs), None)
 
 
 def _check_stats(cs: dict, N: int) -> dict:
@@ -573,6 +616,19 @@ def _check_stats(cs: dict, N: int) -> dict:
     if int(cs["batch_size"]) <= 0:
         raise ValueError("control_stats: batch_size must be positive")
     return cs
+
+
+def _fill_stats(grads, cfg: RenderCfg):
+    """Point the stats_* fields of a D4gsRasterGrads / D4gsFrameGrads at cfg.control_stats, if any (fused statistics: the
+    backward's gather epilogue owns v_means2d and reads radii)."""
+    if cfg.control_stats is None:
+        return
+    cs = _check_stats(cfg.control_stats, cfg.N)
+    if cs.get("absgrad", False) and not cfg.absgrad:
+        raise ValueError("control_stats['absgrad'] needs RenderCfg.absgrad")
+    grads.stats_grad_norm_acc, grads.stats_vis_count = L.ptr(cs["xys_grad_norm_acc"]), L.ptr(cs["vis_count"])
+    grads.stats_max_radii, grads.stats_batch_size = L.ptr(cs["max_radii"]), int(cs["batch_size"])
+    grads.stats_update_max_radii, grads.stats_absgrad = (int(bool(cs.get(k, False))) for k in ("update_max_radii", "absgrad"))
 
 
 def _sized_launch(cfg: "RenderCfg", dev, n_isect_dev, launch, count_needs_launch: bool = False, fused_counts: bool = False):
@@ -591,52 +647,34 @@ def _sized_launch(cfg: "RenderCfg", dev, n_isect_dev, launch, count_needs_launch
         guess = _guess_get(key)
         if guess is not None:
             # deferred check: launch at the guessed capacity, never wait.  The count travels to pinned memory behind
-            # the launches and is looked at by a later call (not under stream capture: a graph replays this shape).
+            # the launches and is looked at by a later call - or, under stream capture, after every replay by the GraphWatch.
             watch = _graph_watch()
-            host_n = None
-            if fused_counts:  # the pinned buffer is chosen BEFORE the launch: the frame's last kernel stores the counts there
-                if capturing and watch is not None:
-                    host_n = watch.take()
-                elif not capturing:
-                    with _SIZE_LOCK:  # pinned pairs are recycled once their count has been read (pin_memory() costs ~0.1 ms)
-                        host_n = _PINNED_FREE.pop() if _PINNED_FREE else None
-                    if host_n is None:
-                        host_n = torch.empty(4, dtype=torch.int64).pin_memory()
-                launch(*guess, 0 if host_n is None else host_n.data_ptr())
+            if not capturing:
+                host_n = _pinned_take()
+            elif watch is not None:
+                host_n = watch.take()  # every replay leaves its counts in this record's buffer
             else:
-                launch(*guess)
-            stored = host_n is not None
-            if capturing and watch is None:
+                host_n = None
                 global _WARNED_UNWATCHED
                 if not _WARNED_UNWATCHED:
                     _WARNED_UNWATCHED = True
-                    import warnings
-
                     warnings.warn("deblur4dgs_amd: a render is being captured in a HIP graph outside `GraphWatch.capturing()`: its "
                                   "replays keep the captured list capacities and skip their work silently if the scene outgrows them "
                                   "(stale images, zero raster gradients).  Capture inside `with engine.GraphWatch().capturing():` and "
                                   "call watch.replayed() / watch.check() around graph.replay().", RuntimeWarning, stacklevel=3)
-            if capturing and watch is not None:
-                # the copy of the counts becomes a node of the graph: every replay leaves them in this record's pinned buffer
-                # (a raw hipMemcpyAsync into memory pinned BEFORE the capture: neither an allocation nor torch's host-allocator
-                # bookkeeping may happen on a capturing stream)
-                if not stored:
-                    host_n = watch.take()
-                    L.check(L.lib().d4gs_copy_counts(L.ptr(n_isect_dev()), host_n.data_ptr(), raw_stream(dev.index)), "copy_counts")
-                watch.recs.append((key, host_n, guess[0], guess[1]))
+            if fused_counts:  # the frame's last kernel stores the counts itself
+                launch(*guess, 0 if host_n is None else host_n.data_ptr())
+            else:
+                launch(*guess)
+                if host_n is not None:
+                    _copy_counts(n_isect_dev(), host_n, dev)
             if not capturing:
-                if not stored:
-                    with _SIZE_LOCK:  # pinned pairs are recycled once their count has been read (pin_memory() costs ~0.1 ms)
-                        host_n = _PINNED_FREE.pop() if _PINNED_FREE else None
-                    if host_n is None:
-                        host_n = torch.empty(4, dtype=torch.int64).pin_memory()
-                    # (a kernel stores the counts into the pinned buffer: a device-to-host copy here is a DMA-engine trip the
-                    # backward's kernels would wait for)
-                    L.check(L.lib().d4gs_copy_counts(L.ptr(n_isect_dev()), host_n.data_ptr(), raw_stream(dev.index)), "copy_counts")
                 ev = torch.cuda.Event()
                 ev.record()
                 with _SIZE_LOCK:
-                    _DEFERRED.setdefault(key, []).append((host_n, ev, guess[0], guess[1]))
+                    _DEFERRED.setdefault(key, []).append((host_n, ev, *guess))
+            elif watch is not None:
+                watch.recs.append((key, host_n, *guess))
             _SIZE_STATS["calls"] += 1
             return guess
     if torch.cuda.is_current_stream_capturing():  # what follows WAITS for the counts on the host: impossible under capture
@@ -656,16 +694,16 @@ def _sized_launch(cfg: "RenderCfg", dev, n_isect_dev, launch, count_needs_launch
     ev = torch.cuda.Event()
     ev.record()
     ev.synchronize()
-    n, max_tile, sampled, live = host_n.tolist()
-    if guess is not None and n <= guess[0] and not (guess[1] > 0 and max_tile > guess[1]):
-        _live_put(key, live, sampled)  # (the launch in front of this readback composited the frame)
-    if guess is None or n > guess[0] or (guess[1] > 0 and max_tile > guess[1]):
+    c = _read_counts(host_n)
+    if guess is not None and _fits(c.n, c.max_tile, *guess):
+        _live_put(key, c.live, c.sampled)  # (the launch in front of this readback composited the frame)
+    else:
         if guess is not None:
             _SIZE_STATS["relaunched"] += 1
-        launch(n, max_tile)
+        launch(c.n, c.max_tile)
     _SIZE_STATS["calls"] += 1
-    _guess_put(key, (n + n // 4 + 4096, _sort_class(max_tile)))
-    return n, max_tile
+    _guess_put(key, (_warm_capacity(c.n), _sort_class(c.max_tile)))
+    return c.n, c.max_tile
 
 
 _SEG_ELEMS: dict = {}
@@ -770,12 +808,7 @@ class RasterFn(torch.autograd.Function):
         ras = L.fill(L.Raster(), **rst)
         rg = L.fill(L.RasterGrads(), **g)
         rg.row_mode = row_mode_for(cfg, dev)
-        if cfg.control_stats is not None:  # fused statistics: the gather epilogue owns v_means2d and reads radii
-            cs = _check_stats(cfg.control_stats, N)
-            rg.stats_grad_norm_acc, rg.stats_vis_count = L.ptr(cs["xys_grad_norm_acc"]), L.ptr(cs["vis_count"])
-            rg.stats_max_radii = L.ptr(cs["max_radii"])
-            rg.stats_batch_size, rg.stats_update_max_radii = int(cs["batch_size"]), int(bool(cs.get("update_max_radii", False)))
-            rg.stats_absgrad = _stats_absgrad(cfg, cs)
+        _fill_stats(rg, cfg)
         L.check(lib.d4gs_raster_bwd(C.byref(dims), C.byref(pout), C.byref(isect), C.byref(ras), C.byref(rg), _stream()),
                 "d4gs_raster_bwd")
         if cfg.absgrad:
@@ -803,10 +836,7 @@ class FrameFn(torch.autograd.Function):
         S, N, H, W, NCH = cfg.S, cfg.N, cfg.height, cfg.width, cfg.NCH
         f32 = dict(dtype=torch.float32, device=dev)
         lib = L.lib()
-        st.proj_in = dict(means=_f32c(means), quats=_f32c(quats), scales=_f32c(scales), opacities=_f32c(opacities),
-                          colors=_f32c(colors), motion_coefs=_f32c(motion_coefs), rots=_f32c(rots),
-                          transls=_f32c(transls), times=_f32c(times), RTs=_f32c(RTs), viewmat=_f32c(viewmat),
-                          Kmat=_f32c(Kmat))
+        st.proj_in = _proj_in(means, quats, scales, opacities, colors, motion_coefs, rots, transls, times, RTs, viewmat, Kmat)
         blended = blend_policy is not None
         io = dict(blended=torch.empty(H, W, NCH, **f32) if blended else None, acc=torch.empty(H, W, **f32) if blended else None,
                   renders=torch.empty(S, H, W, NCH, **f32), alphas=torch.empty(S, H, W, **f32),
@@ -839,9 +869,8 @@ class FrameFn(torch.autograd.Function):
         st.frame_io, st.policy = io, pol
         ctx.st = st
         ctx.set_materialize_grads(False)  # an output the loss does not use must arrive as None, not as a zero-filled stack
-        ctx.save_for_backward(*[st.proj_in[k] for k in _PROJ_IN])  # version-checked, like ProjectFn
-        ctx.needs = [t is not None and t.requires_grad for t in
-                     (means, quats, scales, opacities, colors, motion_coefs, rots, transls, times, RTs, viewmat)]
+        ctx.save_for_backward(*st.proj_in.values())  # version-checked (see _proj_in)
+        ctx.needs = _needs(means, quats, scales, opacities, colors, motion_coefs, rots, transls, times, RTs, viewmat)
         ra = (io["renders"].view(S, H, W, NCH), io["alphas"].view(S, H, W))
         if blended:
             return (io["blended"].view(H, W, NCH), io["acc"].view(H, W), *ra)
@@ -856,8 +885,6 @@ class FrameFn(torch.autograd.Function):
         lib = L.lib()
         dims = cfg.dims()
         pi = dict(zip(_PROJ_IN, ctx.saved_tensors))
-        dyn = cfg.G > 0
-        arena = cfg.grad_arena or {}
         blended = io["blended"] is not None
         c32 = lambda t: None if t is None else t.to(torch.float32).contiguous()
         v_blended, v_acc, v_renders, v_alphas = c32(v_blended), c32(v_acc), c32(v_renders), c32(v_alphas)
@@ -866,31 +893,14 @@ class FrameFn(torch.autograd.Function):
         if blended and v_blended is None and v_acc is None and v_renders is None and v_alphas is None:
             v_blended = torch.zeros_like(io["blended"])
 
-        def buf(name, *shape):
-            t = arena.get(name)
-            if t is not None and t.shape == torch.Size(shape) and t.dtype == torch.float32 and t.is_contiguous():
-                return t.view(shape)
-            return torch.empty(*shape, **f32)
-
-        g = dict(
-            v_means=buf("means", cfg.N, 3), v_quats=buf("quats", cfg.N, 4), v_scales=buf("scales", cfg.N, 3),
-            v_opacities=buf("opacities", cfg.N), v_colors=buf("colors", cfg.N, cfg.D),
-            v_motion_coefs=buf("motion_coefs", cfg.G, cfg.K) if dyn else None,
-            v_rots=buf("rots", cfg.K, cfg.T, 6) if dyn else None, v_transls=buf("transls", cfg.K, cfg.T, 3) if dyn else None,
-            v_times=buf("times", cfg.S) if dyn else None, v_RTs=buf("RTs", cfg.S, 3, 4) if pi["RTs"] is not None else None,
-            v_viewmat=buf("viewmat", 4, 4), partials=None)
+        g = _leaf_grads(cfg, dims, pi, dev, with_partials=False)
         v_m2d = torch.empty(cfg.S, cfg.N, 2, **f32)
         v_abs = torch.empty(cfg.S, cfg.N, 2, **f32) if cfg.absgrad else None
         fg = L.FrameGrads()
         fg.v_blended, fg.v_acc, fg.v_renders, fg.v_alphas = L.ptr(v_blended), L.ptr(v_acc), L.ptr(v_renders), L.ptr(v_alphas)
         fg.v_means2d, fg.v_means2d_abs = L.ptr(v_m2d), L.ptr(v_abs)
         fg.row_mode = row_mode_for(cfg, dev)
-        if cfg.control_stats is not None:
-            cs = _check_stats(cfg.control_stats, cfg.N)
-            fg.stats_grad_norm_acc, fg.stats_vis_count = L.ptr(cs["xys_grad_norm_acc"]), L.ptr(cs["vis_count"])
-            fg.stats_max_radii = L.ptr(cs["max_radii"])
-            fg.stats_batch_size, fg.stats_update_max_radii = int(cs["batch_size"]), int(bool(cs.get("update_max_radii", False)))
-            fg.stats_absgrad = _stats_absgrad(cfg, cs)
+        _fill_stats(fg, cfg)
         fio = L.fill(L.FrameIO(), **io)
         fio.near_target = cfg.near_target
         if blended:
@@ -904,16 +914,7 @@ class FrameFn(torch.autograd.Function):
                 x.grad = v_m2d[s:s + 1]
                 if v_abs is not None:
                     x.absgrad = v_abs[s:s + 1]
-        outs = [g["v_means"], g["v_quats"], g["v_scales"], g["v_opacities"], g["v_colors"], g["v_motion_coefs"],
-                g["v_rots"], g["v_transls"], g["v_times"], g["v_RTs"], g["v_viewmat"]]
-        outs = [x if need else None for x, need in zip(outs, ctx.needs)]
-        return (None, None, *outs, None, None)
-
-
-def _stats_absgrad(cfg: RenderCfg, cs: dict) -> int:
-    if cs.get("absgrad", False) and not cfg.absgrad:
-        raise ValueError("control_stats['absgrad'] needs RenderCfg.absgrad")
-    return int(bool(cs.get("absgrad", False)))
+        return (None, None, *_only_needed([g["v_" + k] for k in _LEAVES], ctx.needs), None, None)
 
 
 def frame_supported(cfg: RenderCfg) -> bool:
@@ -958,7 +959,7 @@ class PosesFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)  # unused outputs arrive as None (no zero-filled [N,B,...] gradients to stream)
         ctx.keys = [k for k, v in pin.items() if v is not None]
         ctx.save_for_backward(*[pin[k] for k in ctx.keys])  # version-checked, like ProjectFn
-        ctx.needs = [t is not None and t.requires_grad for t in (means, quats, motion_coefs, rots, transls, ts, w2cs34)]
+        ctx.needs = _needs(means, quats, motion_coefs, rots, transls, ts, w2cs34)
         if want_t and out["transforms"] is None:
             out["transforms"] = torch.zeros(shp(0, 3, 4), **f32)
         return out["means"], out["quats"], out["transforms"]
@@ -994,7 +995,7 @@ class PosesFn(torch.autograd.Function):
                                    C.byref(L.fill(L.LeafGrads(), **g)), _stream()), "d4gs_poses_bwd")
         del vin
         outs = [g["v_means"], g["v_quats"], g["v_motion_coefs"], g["v_rots"], g["v_transls"], g["v_times"], g["v_RTs"]]
-        return (*(x if need else None for x, need in zip(outs, ctx.needs)), None, None, None)
+        return (*_only_needed(outs, ctx.needs), None, None, None)
 
 
 def poses(means, quats, motion_coefs, rots, transls, ts, want=(True, True, False), raw_coefs=True):

@@ -146,3 +146,133 @@ def test_exact_tiles_auto_keeps_one_size_guess_per_flag_and_counts_again_after_o
             engine._guess_drop(k)
         engine._XT_ON.pop(base, None)
         engine._LIVE_FRAC.pop(base, None)
+
+
+# ---- the list-size protocol, rule by rule.  Expected capacities and sort classes come from tests/ladder.py (its own statements of
+# the rules), count buffers are ordinary host int64[4] tensors and go back to a throwaway pool, no GPU is touched.
+
+class _Ev:
+    """What the protocol uses of a torch.cuda.Event (as in test_deferred_records_queue_up_and_are_all_verified)."""
+
+    def __init__(self, done=True):
+        self.done = done
+
+    def query(self):
+        return self.done
+
+    def synchronize(self):
+        self.done = True
+
+
+def _counts(n, max_tile, live=0, sampled=50):
+    return torch.tensor([n, max_tile, sampled, live], dtype=torch.int64)  # D4gsProjOut.n_isect
+
+
+@pytest.fixture
+def size_state(monkeypatch):
+    """A throwaway pinned pool; the keys a test registers here leave no guess, live fraction or record behind."""
+    monkeypatch.setattr(engine, "_PINNED_FREE", [])
+    keys = []
+    yield keys
+    for k in keys:
+        engine._guess_drop(k)
+        engine._LIVE_FRAC.pop(k[:5], None)
+        engine._DEFERRED.pop(k, None)
+        engine._XT_ON.pop(k[:5], None)
+
+
+@pytest.mark.parametrize("n", [0, 1, 3, 4, 5, 4095, 4096, 4097, 10**6 + 3])
+def test_stored_capacity_is_the_ladders_warm_capacity(n, size_state):
+    from tests import ladder
+
+    key = ("cap", 0, n, 3, 4, False)
+    size_state.append(key)
+    engine._DEFERRED[key] = [(_counts(n, 10), _Ev(), n, 0)]
+    assert engine._deferred_poll(key) == (n, 10)
+    assert engine._guess_get(key) == (ladder.warm_capacity(n), ladder.sort_class(10))
+
+
+def test_deferred_poll_overflowed_record_is_not_the_newest(size_state):
+    from tests import ladder
+
+    key = ("unit", 2, 2, 3, 4, False)
+    size_state.append(key)
+    b1, b2 = _counts(900, 3000, live=50), _counts(100, 10, live=20)
+    engine._DEFERRED[key] = [(b1, _Ev(), 200, 2048), (b2, _Ev(), 200, 2048)]
+    with pytest.raises(RuntimeError, match="needed 900 intersections"):
+        engine._deferred_poll(key)
+    assert key not in engine._DEFERRED
+    # the newest record sets the guess, the overflowed one raises it: its capacity, the class of the longer of the two longest lists
+    assert engine._guess_get(key) == (ladder.warm_capacity(900), ladder.sort_class(3000))
+    assert engine._LIVE_FRAC[key[:5]] == 20 / 50  # the second record's only: the overflowed render composited nothing
+    assert len(engine._PINNED_FREE) == 2 and engine._PINNED_FREE[0] is b1 and engine._PINNED_FREE[1] is b2
+
+
+def test_deferred_poll_longest_list_overflow_alone(size_state):
+    from tests import ladder
+
+    key = ("unit", 3, 2, 3, 4, False)
+    size_state.append(key)
+    engine._DEFERRED[key] = [(_counts(100, 3000, live=40), _Ev(), 200, 2048)]
+    with pytest.raises(RuntimeError, match=r"needed 100 intersections \(longest tile list 3000\).*sized for 200 \(class 2048\)"):
+        engine._deferred_poll(key)
+    assert key[:5] not in engine._LIVE_FRAC
+    assert engine._guess_get(key) == (ladder.warm_capacity(100), ladder.sort_class(3000))
+    engine._DEFERRED[key] = [(_counts(100, 3000, live=40), _Ev(), 200, 0)]  # hint 0 = class unknown: every class was launched
+    assert engine._deferred_poll(key) == (100, 3000)
+    assert engine._LIVE_FRAC[key[:5]] == 40 / 50
+
+
+def test_graph_watch_check_updates_overflowed_guesses_only(size_state):
+    from tests import ladder
+
+    fits, by_count, by_list = (("unit", 4, i, 3, 4, False) for i in range(3))
+    size_state.extend((fits, by_count, by_list))
+    for k in (fits, by_count, by_list):
+        engine._guess_put(k, (1234, 2048))
+    watch = object.__new__(engine.GraphWatch)  # (__init__ pins memory)
+    watch.recs = [(fits, _counts(150, 100, live=30), 200, 2048), (by_count, _counts(700, 100, live=50), 200, 2048),
+                  (by_list, _counts(120, 2500, live=50), 200, 2048)]
+    watch.event = _Ev(False)
+    with pytest.raises(RuntimeError, match=r"needed 700 intersections \(longest tile list 100\).*captured with lists for 200 \(class 2048\)"):
+        watch.check()
+    assert engine._guess_get(fits) == (1234, 2048)
+    assert engine._guess_get(by_count) == (ladder.warm_capacity(700), ladder.sort_class(100))
+    assert engine._guess_get(by_list) == (ladder.warm_capacity(120), ladder.sort_class(2500))
+    assert engine._LIVE_FRAC[fits[:5]] == 30 / 50
+    assert by_count[:5] not in engine._LIVE_FRAC and by_list[:5] not in engine._LIVE_FRAC
+    assert watch.event is None
+    watch.check()  # nothing replayed since: a no-op
+
+
+def test_lazy_sort_auto_decides_from_the_capacity_with_its_constant_left_in(monkeypatch, size_state):
+    """LAZY_AUTO_KEYS and the near_target factor were tuned on `capacity / 1.25` per tile list - the 4096 of the capacity rule is
+    NOT taken out first.  The guesses sit so close to the line that taking it out would flip the decision."""
+    import math
+
+    dev = torch.device("cuda", 0)
+    monkeypatch.setattr(engine, "LAZY_SORT", "auto")
+    monkeypatch.setattr(engine, "EXACT_TILES", "0")
+    S, N, W, H = 2, 1000, 64, 48
+    mk = lambda: engine.RenderCfg(N=N, G=0, K=0, T=0, S=S, D=3, width=W, height=H)
+    tw, th = mk().tiles
+    lists = S * tw * th
+    base = engine._size_key(dev, S, N, W, H)
+    size_state.append(base + (False,))
+    size_state.append(base + (True,))
+    on_from = math.ceil(engine.LAZY_AUTO_KEYS * 1.25 * lists)
+    assert on_from / 1.25 / lists >= engine.LAZY_AUTO_KEYS > (on_from - 1) / 1.25 / lists
+    assert (on_from + 4000 - 4096) / 1.25 / lists < engine.LAZY_AUTO_KEYS  # without the constant both "on" guesses would be off
+    low, high = engine.LAZY_AUTO_LIVE / 2, (1 + engine.LAZY_AUTO_LIVE) / 2
+    for cap, f, want in ((on_from, low, True), (on_from + 4000, low, True), (on_from - 1, low, False), (on_from, high, False),
+                         (10 * on_from + 7, 0.3 * engine.LAZY_AUTO_LIVE, True)):
+        engine._guess_put(base + (False,), (cap, 2048))
+        engine._live_put(base, int(f * 10000), 10000)
+        f = engine._LIVE_FRAC[base]
+        cfg = engine.resolve_lazy(mk(), dev)
+        assert cfg.exact_tiles is False
+        assert (f < engine.LAZY_AUTO_LIVE and cap / 1.25 / lists >= engine.LAZY_AUTO_KEYS) == want, (cap, f)  # (the cases are what they claim)
+        assert cfg.lazy_sort is want, (cap, f)
+        assert cfg.near_target == (max(256, int(2.5 * f * cap / 1.25 / lists)) if want else 0), (cap, f)
+    engine._guess_drop(base + (False,))  # nothing measured: off, whatever the live fraction
+    assert engine.resolve_lazy(mk(), dev).lazy_sort is False

@@ -169,3 +169,48 @@ def test_a_replayed_graph_reports_lists_that_outgrew_their_capture():
         watch.check()
     key = watch.recs[0][0]
     assert engine._guess_get(key)[0] > watch.recs[0][2]  # the next eager / captured step is sized for the new count
+
+
+def test_one_call_render_captured_under_a_graph_watch_equals_the_eager_render_bitwise():
+    """The one-call node (engine.FrameFn: its last kernel stores the list counts into the pinned buffer itself) through the deferred
+    size check, eagerly and captured inside GraphWatch.capturing() - the tests above take the staged chain.  The count record of
+    each render must arrive where its reader looks (engine._DEFERRED eagerly, watch.recs under capture), and images and leaf
+    gradients must equal the synchronous render's bit for bit."""
+    from deblur4dgs_amd import engine
+
+    dev = torch.device("cuda:0")
+    N, G, K_, S, W, H = 400, 250, 3, 2, 64, 48
+    sc = make_scene(N, G, K_, S, W, H, seed=23)
+    K = sc["K"].to(dev)
+    w = torch.randn(H, W, 4, generator=torch.Generator().manual_seed(3)).to(dev)
+    engine.check_deferred()
+    eager = _leaves(sc, dev)
+    r_e = _step(eager, K, W, H, w, fused=True)  # synchronous: exact sizes
+    assert r_e["state"].frame_io  # the one-call path
+    static = _leaves(sc, dev)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            for v in static.values():
+                v.grad = None
+            r_d = _step(static, K, W, H, w, deferred_size_check=True, fused=True)
+    torch.cuda.current_stream().wait_stream(side)
+    key = engine._list_key(dev, r_d["state"].cfg)
+    assert len(engine._DEFERRED.get(key, ())) >= 1  # (earlier records of the shape may have been read by the render after them)
+    engine.check_deferred()
+    assert key not in engine._DEFERRED
+    assert torch.equal(r_d["blended"], r_e["blended"]) and all(torch.equal(static[k].grad, eager[k].grad) for k in NAMES)
+    for v in static.values():
+        v.grad = None
+    graph, watch = torch.cuda.CUDAGraph(), engine.GraphWatch()
+    with watch.capturing(), torch.cuda.graph(graph):
+        r_g = _step(static, K, W, H, w, deferred_size_check=True, fused=True)
+    assert len(watch.recs) == 1 and watch.recs[0][0] == key and key not in engine._DEFERRED
+    graph.replay()
+    watch.replayed()
+    watch.check()  # fits: silent
+    assert 0 < int(watch.recs[0][1][0]) <= watch.recs[0][2]
+    assert torch.equal(r_g["blended"], r_e["blended"])
+    for k in NAMES:
+        assert torch.equal(static[k].grad, eager[k].grad), k
