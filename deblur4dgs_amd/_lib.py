@@ -119,7 +119,7 @@ EXPORTS = (
     "d4gs_photometric_blocks", "d4gs_photometric_maps_elems", "d4gs_photometric_fwd", "d4gs_photometric_bwd", "d4gs_sh_partials_elems", "d4gs_sh_fwd", "d4gs_sh_bwd", "d4gs_query_sizes", "d4gs_profile_enable", "d4gs_profile_collect", "d4gs_measure_peaks",
     "d4gs_adam_blocks", "d4gs_adam_step", "d4gs_adam_set_grads", "d4gs_adam_step_cpu",
     "d4gs_trimmed_scratch_words", "d4gs_masked_l1_fwd", "d4gs_masked_l1_bwd", "d4gs_trimmed_l1_fwd", "d4gs_trimmed_l1_bwd",
-    "d4gs_gradient_loss_fwd", "d4gs_gradient_loss_bwd",
+    "d4gs_gradient_loss_fwd", "d4gs_gradient_loss_bwd", "d4gs_track_losses_fwd", "d4gs_track_losses_bwd",
     "d4gs_correlation_fwd", "d4gs_correlation_bwd", "d4gs_backwarp_fwd", "d4gs_backwarp_bwd",
     "d4gs_aligned_l1_blocks", "d4gs_aligned_l1_fwd", "d4gs_aligned_l1_bwd",
 )
@@ -216,6 +216,8 @@ def lib() -> C.CDLL:
         L.d4gs_trimmed_l1_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp]
         L.d4gs_gradient_loss_fwd.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.c_int64, vp, vp]
         L.d4gs_gradient_loss_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+        L.d4gs_track_losses_fwd.argtypes = [vp] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_float, vp, C.c_int64, vp, vp]
+        L.d4gs_track_losses_bwd.argtypes = [vp] * 11 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_float, vp, vp]
         i32 = C.c_int32
         L.d4gs_correlation_fwd.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, vp]
         L.d4gs_correlation_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, vp]

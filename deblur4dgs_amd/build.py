@@ -23,8 +23,8 @@ LINK = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-scr
 VARIANTS_LIB = os.path.join(HERE, "..", "tests", "libd4gs_variants.so")
 VARIANT_SOURCES = ("raster_fwd.hip", "raster_bwd.hip")
 # -fvisibility=hidden: only the D4GS_API entry points of include/d4gs.h are exported (tests/test_c_abi.py checks `nm -D`).  No
-# -munsafe-fp-atomics: the gradient reductions are deterministic gathers; the one scatter (warp.hip, the backward warp's image gradient)
-# uses plain atomicAdd, which is a single global_atomic_add_f32 on gfx950 without the flag.
+# -munsafe-fp-atomics: the gradient reductions are deterministic gathers; the two scatters (warp.hip, the backward warp's image gradient;
+# trimmed.hip, the track losses' point gradient) use plain atomicAdd, which is a single global_atomic_add_f32 on gfx950 without the flag.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # per-file extras.  project_bwd: the SLP vectorizer turns the adjoint chain into v_pk_* math, which is not faster on gfx950 (4.5
 # cycles for two operations against 2.5 for one) and parks ~40 duplicated operands in VGPR pairs: 256 + 30 registers instead of 128

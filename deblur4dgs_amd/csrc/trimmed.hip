@@ -1,9 +1,11 @@
 // trimmed.hip -- the reference's quantile-trimmed losses (flow3d/loss_utils.py: masked_l1_loss, trimmed_l1_loss,
-// compute_gradient_loss) without a sort, a host read or a data-dependent launch (include/d4gs.h, "Trimmed losses").
+// compute_gradient_loss) without a sort, a host read or a data-dependent launch (include/d4gs.h, "Trimmed losses"),
+// and the trainer's 2-D track / mapped-depth pair built on them (flow3d/trainer.py:633-667,681-689).
 //
 // One value pass per mode writes the elements v >= 0 to scratch (the depth-gradient mode: two terms, one slot per pixel and term,
-// a slot without a valid pair holds TRIM_EMPTY and the valid ones are counted on the device).  Everything after it is the same for
-// every mode and runs once per term (blockIdx.y):
+// a slot without a valid pair holds TRIM_EMPTY and the valid ones are counted on the device; the track mode: two terms, one slot per
+// (target frame, query) and term, live where the query is visible).  Everything after it is the same for every mode and runs once
+// per term (blockIdx.y); the terms that select come first, the others (term >= sel_terms) skip the selection and keep every live slot:
 //   4 x { k_trim_hist: LDS histogram of one 8-bit digit of the keys under the current prefix, merged into 256 global bins with
 //                      integer atomics;  k_trim_narrow: one block scans the bins and extends the prefix }
 // Non-negative floats order like their bit patterns, so after the four digits the prefix IS the order statistic.  torch.quantile
@@ -206,9 +208,10 @@ __global__ void __launch_bounds__(TB) k_trim_narrow(uint32_t *ctrl_all, int pass
 __device__ __forceinline__ bool trim_kept(float v, float t, bool keep_all) { return keep_all ? v == v : v < t; }
 
 __global__ void __launch_bounds__(TB) k_trim_sum(const float *__restrict__ values, const float *__restrict__ weights, int64_t n_max,
-                                                 const uint32_t *__restrict__ ctrl_all, int keep_all, double *__restrict__ partials) {
+                                                 const uint32_t *__restrict__ ctrl_all, int sel_terms, double *__restrict__ partials) {
   __shared__ double red[3][TB / 64];
   const int term = blockIdx.y, tid = threadIdx.x;
+  const bool keep_all = term >= sel_terms;
   const float t = __uint_as_float(ctrl_all[(int64_t)term * C_WORDS + C_T]);
   const float *v = values + (int64_t)term * n_max;
   double s_vm = 0.0, s_m = 0.0, cnt = 0.0;
@@ -227,8 +230,10 @@ __global__ void __launch_bounds__(TB) k_trim_sum(const float *__restrict__ value
   if (tid < 3) partials[((int64_t)term * gridDim.x + blockIdx.x) * PARTIAL_DOUBLES + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
 }
 
-// out[0] = sum of the terms' losses; per term k: out[1 + 2k] = threshold, out[2 + 2k] = 1 / denominator (what the backward scales by)
-// denominators: mode 0 sum of kept m + 1e-8 (normalize=True), mode 1 the kept count (normalize=False, no mask)
+// out[0] = sum of the terms' losses; per term k: out[1 + 2k] = threshold, out[2 + 2k] = 1 / denominator (what the backward scales by),
+// out[5 + k] = the term's own loss
+// denominators: mode 0 sum of kept m + 1e-8 (normalize=True), mode 1 the kept count (normalize=False, no mask), mode 2 as mode 0 but
+// a term that selected among no live slot at all (its threshold is NaN) is NaN, as the mean forms are
 __global__ void __launch_bounds__(TB) k_trim_finish(const double *__restrict__ partials, int n_blocks, int terms, int mode,
                                                     const uint32_t *__restrict__ ctrl_all, float *out) {
   __shared__ double r[3][TB];
@@ -244,9 +249,12 @@ __global__ void __launch_bounds__(TB) k_trim_finish(const double *__restrict__ p
         for (int k = 0; k < 3; k++) r[k][threadIdx.x] += r[k][threadIdx.x + o];
       __syncthreads();
     }
-    const double den = mode == 0 ? r[1][0] + 1e-8 : r[2][0];
-    total += r[0][0] / den;  // 0 / 0 = NaN: an empty kept set, as torch's mean of nothing
-    if (threadIdx.x == 0) out[1 + 2 * term] = __uint_as_float(ctrl_all[(int64_t)term * C_WORDS + C_T]), out[2 + 2 * term] = (float)(1.0 / den);
+    const double den = mode == 1 ? r[2][0] : r[1][0] + 1e-8;
+    const float t = __uint_as_float(ctrl_all[(int64_t)term * C_WORDS + C_T]);
+    double loss = r[0][0] / den;  // 0 / 0 = NaN: an empty kept set, as torch's mean of nothing
+    if (mode == 2 && t != t) loss = (double)t;
+    total += loss;
+    if (threadIdx.x == 0) out[1 + 2 * term] = t, out[2 + 2 * term] = (float)(1.0 / den), out[5 + term] = (float)loss;
     __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = (float)total;
@@ -292,21 +300,107 @@ __global__ void __launch_bounds__(TB) k_trim_grad_bwd(const float *__restrict__ 
   }
 }
 
-// init, [selection], sum, finish over values already in scratch
-int trim_reduce(float *values, const float *weights, int64_t n_max, int terms, bool keep_all, int mode, float q, uint32_t *ctrl,
+// ---- the 2-D track loss and the mapped-depth loss (trainer.py:633-667,681-689) over elements e = (row r = b N + n, query p) ----
+// One query of one target frame: the point the dynamic render composited at the query's pixel, in the target camera's frame, and
+// its projection by the row's intrinsics.
+struct TrackPoint {
+  const float *K;    // the row's 3 x 3 intrinsics
+  int64_t at;        // offset of the point's three floats in tracks_3d [pixels, N, 3]
+  float pz, z, x, y; // (K X)_z, max(pz, 1e-6), (K X)_xy / z
+};
+// false: not a live element (not visible, or a pixel / row outside the tables' range - no address is formed from such an index)
+__device__ __forceinline__ bool track_point(const float *__restrict__ tracks, const int32_t *__restrict__ pix, const int32_t *__restrict__ rows,
+                                            const uint8_t *__restrict__ visible, const float *__restrict__ Ks, int64_t e, int64_t n_pixels,
+                                            int N, int n_rows, TrackPoint &t) {
+  if (!visible[e]) return false;
+  const int32_t p = pix[e], r = rows[e];
+  if (p < 0 || (int64_t)p >= n_pixels || r < 0 || r >= n_rows) return false;
+  t.K = Ks + (int64_t)r * 9;
+  t.at = ((int64_t)p * N + r % N) * 3;
+  const float X = tracks[t.at], Y = tracks[t.at + 1], Z = tracks[t.at + 2];
+  const float px = t.K[0] * X + t.K[1] * Y + t.K[2] * Z, py = t.K[3] * X + t.K[4] * Y + t.K[5] * Z;
+  t.pz = t.K[6] * X + t.K[7] * Y + t.K[8] * Z;
+  t.z = fmaxf(t.pz, 1e-6f);
+  t.x = px / t.z, t.y = py / t.z;
+  return true;
+}
+__device__ __forceinline__ float track_disparity(float depth) { return 1.f / (depth + 1e-5f); }
+
+// term 0: mean over (x, y) of |projected - target|; term 1: |1 / (z + 1e-5) - 1 / (target depth + 1e-5)|; both share the live count
+__global__ void __launch_bounds__(TB) k_track_values(const float *__restrict__ tracks, const int32_t *__restrict__ pix,
+                                                     const int32_t *__restrict__ rows, const uint8_t *__restrict__ visible,
+                                                     const float *__restrict__ target_2d, const float *__restrict__ target_depth,
+                                                     const float *__restrict__ Ks, int64_t n_pixels, int N, int n_rows, int64_t n,
+                                                     float *__restrict__ values, uint32_t *ctrl) {
+  __shared__ uint32_t cnt;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  uint32_t c = 0;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t e = (int64_t)blockIdx.x * TB + threadIdx.x; e < n; e += stride) {
+    TrackPoint t;
+    const bool live = track_point(tracks, pix, rows, visible, Ks, e, n_pixels, N, n_rows, t);
+    float v0 = __uint_as_float(TRIM_EMPTY), v1 = v0;
+    if (live) {
+      v0 = 0.5f * (fabsf(t.x - target_2d[2 * e]) + fabsf(t.y - target_2d[2 * e + 1]));
+      v1 = fabsf(track_disparity(t.z) - track_disparity(target_depth[e]));
+    }
+    values[e] = v0, values[n + e] = v1;
+    c += live;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&cnt, c);
+  __syncthreads();
+  if (threadIdx.x < 2 && cnt) atomicAdd(&ctrl[threadIdx.x * C_WORDS + C_COUNT], cnt);
+}
+
+// (a kernel, not a memset node: csrc/warp.hip, k_warp_zero)
+__global__ void __launch_bounds__(TB) k_track_zero(float *__restrict__ p, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += stride) p[i] = 0.f;
+}
+
+// one thread per live element adds K^T dL/d(K X) to its point.  torch.clamp(min) passes the gradient where its input is >= the
+// bound: pz > 1e-6f here, fp32's 1e-6 lying just below the real one.  Below it x and y still divide by the clamped 1e-6.
+__global__ void __launch_bounds__(TB) k_track_bwd(const float *__restrict__ tracks, const int32_t *__restrict__ pix,
+                                                  const int32_t *__restrict__ rows, const uint8_t *__restrict__ visible,
+                                                  const float *__restrict__ weights, const float *__restrict__ target_2d,
+                                                  const float *__restrict__ target_depth, const float *__restrict__ Ks,
+                                                  const float *__restrict__ values, const float *__restrict__ out,
+                                                  const float *__restrict__ v_losses, int64_t n_pixels, int N, int n_rows, int64_t n,
+                                                  int keep_all, float *v_tracks) {
+  const float t0 = out[1], s0 = v_losses[0] * out[2], s1 = v_losses[1] * out[4];
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t e = (int64_t)blockIdx.x * TB + threadIdx.x; e < n; e += stride) {
+    TrackPoint t;
+    if (!track_point(tracks, pix, rows, visible, Ks, e, n_pixels, N, n_rows, t)) continue;
+    const float w = weights[e];
+    const float c0 = trim_kept(values[e], t0, keep_all) ? 0.5f * s0 * w : 0.f;
+    const float gx = c0 * trim_sign(t.x - target_2d[2 * e]), gy = c0 * trim_sign(t.y - target_2d[2 * e + 1]);
+    const float a = track_disparity(t.z);
+    const float gz = -(gx * t.x + gy * t.y) / t.z - s1 * w * trim_sign(a - track_disparity(target_depth[e])) * a * a;
+    const float dx = gx / t.z, dy = gy / t.z, dz = t.pz > 1e-6f ? gz : 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; j++) atomicAdd(&v_tracks[t.at + j], t.K[j] * dx + t.K[3 + j] * dy + t.K[6 + j] * dz);
+  }
+}
+
+// [selection of the first sel_terms terms at quantile q], sum, finish over values already in scratch (control words initialised)
+int trim_reduce(float *values, const float *weights, int64_t n_max, int terms, int sel_terms, int mode, float q, uint32_t *ctrl,
                 double *partials, float *out, hipStream_t stream) {
   const int nb = (int)trim_blocks(n_max);
   const dim3 grid(nb, terms);
-  if (!keep_all) {
+  if (sel_terms > 0) {
     for (int pass = 0; pass < TRIM_PASSES; pass++) {
-      D4GS_LAUNCH("k_trim_hist", k_trim_hist, grid, dim3(TB), 0, stream, (const float *)values, n_max, ctrl, pass);
+      D4GS_LAUNCH("k_trim_hist", k_trim_hist, dim3(nb, sel_terms), dim3(TB), 0, stream, (const float *)values, n_max, ctrl, pass);
       if (int rc = d4gs_check_launch("k_trim_hist")) return rc;
-      D4GS_LAUNCH("k_trim_narrow", k_trim_narrow, dim3(terms), dim3(TB), 0, stream, ctrl, pass, q);
+      D4GS_LAUNCH("k_trim_narrow", k_trim_narrow, dim3(sel_terms), dim3(TB), 0, stream, ctrl, pass, q);
       if (int rc = d4gs_check_launch("k_trim_narrow")) return rc;
     }
   }
   D4GS_LAUNCH("k_trim_sum", k_trim_sum, grid, dim3(TB), 0, stream, (const float *)values, weights, n_max, (const uint32_t *)ctrl,
-              (int)keep_all, partials);
+              sel_terms, partials);
   if (int rc = d4gs_check_launch("k_trim_sum")) return rc;
   D4GS_LAUNCH("k_trim_finish", k_trim_finish, dim3(1), dim3(TB), 0, stream, (const double *)partials, nb, terms, mode,
               (const uint32_t *)ctrl, out);
@@ -342,7 +436,7 @@ int l1_fwd(const char *who, const float *pred, const float *gt, const float *mas
   if (int rc = d4gs_check_launch("k_trim_init")) return rc;
   D4GS_LAUNCH("k_trim_l1_values", k_trim_l1_values, dim3((unsigned)trim_blocks(n)), dim3(TB), 0, s, pred, gt, n, (int)D, values);
   if (int rc = d4gs_check_launch("k_trim_l1_values")) return rc;
-  return trim_reduce(values, mask, n, 1, keep_all, mode, quantile, ctrl, partials, out, s);
+  return trim_reduce(values, mask, n, 1, keep_all ? 0 : 1, mode, quantile, ctrl, partials, out, s);
 }
 
 int l1_bwd(const char *who, const float *pred, const float *gt, const float *mask, const float *values, const float *out,
@@ -359,6 +453,26 @@ int l1_bwd(const char *who, const float *pred, const float *gt, const float *mas
   D4GS_LAUNCH("k_trim_l1_bwd", k_trim_l1_bwd, dim3((unsigned)trim_blocks(n)), dim3(TB), 0, (hipStream_t)stream, pred, gt, mask, values,
               out, v_loss, n, (int)D, (int)keep_all, v_pred);
   return d4gs_check_launch("k_trim_l1_bwd");
+}
+
+int track_check(const char *who, const void *const *ptrs, int n_ptrs, int64_t n_pixels, int32_t N, int32_t n_rows, int64_t n_elements,
+                float quantile) {
+  for (int i = 0; i < n_ptrs; i++)
+    if (!ptrs[i]) {
+      d4gs_set_error("%s: NULL argument (every pointer is required)", who);
+      return D4GS_EINVAL;
+    }
+  if (N < 1 || n_rows < 1 || n_rows % N || n_elements < 1 || n_elements > INT32_MAX || n_pixels < 1 || n_pixels > INT32_MAX ||
+      n_pixels > ((int64_t)1 << 40) / N) {
+    d4gs_set_error("%s: bad size n_pixels=%lld N=%d n_rows=%d n_elements=%lld (N >= 1, n_rows a positive multiple of N, 1 <= n_pixels, "
+                   "n_elements <= 2^31 - 1, n_pixels N <= 2^40)", who, (long long)n_pixels, N, n_rows, (long long)n_elements);
+    return D4GS_EINVAL;
+  }
+  if (bad_quantile(quantile)) {
+    d4gs_set_error("%s: quantile=%g (finite and > 0)", who, (double)quantile);
+    return D4GS_EINVAL;
+  }
+  return D4GS_OK;
 }
 
 }  // namespace
@@ -427,7 +541,7 @@ int d4gs_gradient_loss_fwd(const float *pred, const float *gt, const float *mask
   D4GS_LAUNCH("k_trim_grad_values", k_trim_grad_values, dim3((unsigned)trim_blocks(P)), dim3(TB), 0, s, pred, gt, mask, P, (int)H, (int)W,
               values, ctrl);
   if (int rc = d4gs_check_launch("k_trim_grad_values")) return rc;
-  return trim_reduce(values, nullptr, P, 2, false, 1, quantile, ctrl, partials, out, s);
+  return trim_reduce(values, nullptr, P, 2, 2, 1, quantile, ctrl, partials, out, s);
 }
 
 int d4gs_gradient_loss_bwd(const float *pred, const float *gt, const float *mask, const float *values, const float *out,
@@ -445,6 +559,46 @@ int d4gs_gradient_loss_bwd(const float *pred, const float *gt, const float *mask
   D4GS_LAUNCH("k_trim_grad_bwd", k_trim_grad_bwd, dim3((unsigned)trim_blocks(P)), dim3(TB), 0, (hipStream_t)stream, pred, gt, mask, values,
               out, v_loss, P, (int)H, (int)W, v_pred);
   return d4gs_check_launch("k_trim_grad_bwd");
+}
+
+int d4gs_track_losses_fwd(const float *tracks_3d, const int32_t *pix, const int32_t *rows, const uint8_t *visible, const float *weights,
+                          const float *target_2d, const float *target_depth, const float *Ks, int64_t n_pixels, int32_t N, int32_t n_rows,
+                          int64_t n_elements, float quantile, void *scratch, int64_t scratch_words, float *out, void *stream) {
+  const void *ptrs[] = {tracks_3d, pix, rows, visible, weights, target_2d, target_depth, Ks, scratch, out};
+  if (int rc = track_check("d4gs_track_losses_fwd", ptrs, 10, n_pixels, N, n_rows, n_elements, quantile)) return rc;
+  const int64_t n = n_elements;
+  if (scratch_words < trim_scratch_words(n, 2) || (uintptr_t)scratch % 8) {
+    d4gs_set_error("d4gs_track_losses_fwd: scratch of %lld words (8-byte aligned) needed, %lld given at %p",
+                   (long long)trim_scratch_words(n, 2), (long long)scratch_words, scratch);
+    return D4GS_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float *values = (float *)scratch;
+  uint32_t *ctrl = (uint32_t *)scratch + trim_ctrl_offset(n, 2);
+  double *partials = (double *)((uint32_t *)scratch + trim_partials_offset(n, 2));
+  D4GS_LAUNCH("k_trim_init", k_trim_init, dim3(1), dim3(TB), 0, s, ctrl, 2, 0u);
+  if (int rc = d4gs_check_launch("k_trim_init")) return rc;
+  D4GS_LAUNCH("k_track_values", k_track_values, dim3((unsigned)trim_blocks(n)), dim3(TB), 0, s, tracks_3d, pix, rows, visible, target_2d,
+              target_depth, Ks, n_pixels, (int)N, (int)n_rows, n, values, ctrl);
+  if (int rc = d4gs_check_launch("k_track_values")) return rc;
+  // the depth term (the reference's default quantile, 1) never selects; the 2-D term does unless its quantile says the same
+  return trim_reduce(values, weights, n, 2, quantile >= 1.f ? 0 : 1, 2, quantile, ctrl, partials, out, s);
+}
+
+int d4gs_track_losses_bwd(const float *tracks_3d, const int32_t *pix, const int32_t *rows, const uint8_t *visible, const float *weights,
+                          const float *target_2d, const float *target_depth, const float *Ks, const float *values, const float *out,
+                          const float *v_losses, int64_t n_pixels, int32_t N, int32_t n_rows, int64_t n_elements, float quantile,
+                          float *v_tracks_3d, void *stream) {
+  const void *ptrs[] = {tracks_3d, pix, rows, visible, weights, target_2d, target_depth, Ks, values, out, v_losses, v_tracks_3d};
+  if (int rc = track_check("d4gs_track_losses_bwd", ptrs, 12, n_pixels, N, n_rows, n_elements, quantile)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n_floats = n_pixels * N * 3;
+  D4GS_LAUNCH("k_track_zero", k_track_zero, dim3((unsigned)trim_blocks(n_floats)), dim3(TB), 0, s, v_tracks_3d, n_floats);
+  if (int rc = d4gs_check_launch("k_track_zero")) return rc;
+  D4GS_LAUNCH("k_track_bwd", k_track_bwd, dim3((unsigned)trim_blocks(n_elements)), dim3(TB), 0, s, tracks_3d, pix, rows, visible, weights,
+              target_2d, target_depth, Ks, values, out, v_losses, n_pixels, (int)N, (int)n_rows, n_elements, (int)(quantile >= 1.f),
+              v_tracks_3d);
+  return d4gs_check_launch("k_track_bwd");
 }
 
 }  // extern "C"

@@ -11,6 +11,10 @@ channel-last [B,H,W,3] as the rasterizer returns them (no permute), the mask is 
 `torch.quantile` (a full sort) and selects with boolean masks (`nonzero`: the host waits for the device); here the two order
 statistics come from a radix select and nothing is read on the host, so the losses can sit inside a captured HIP graph
 (`csrc/trimmed.hip`).  Gradients flow to `pred` only.
+
+`track_losses` is the 2-D track loss and the mapped (track) depth loss of `Trainer.compute_dynamic_losses`
+(flow3d/trainer.py:633-667,681-689) on the same machinery: one value pass gathers the rendered track points at the query pixels
+and projects them, the selection runs for the 2-D term only, one kernel scatters the gradient back.
 """
 from __future__ import annotations
 
@@ -193,3 +197,115 @@ def compute_gradient_loss(pred, gt, mask, quantile=0.98):
     term without any valid pair is NaN here, where the reference raises (torch.quantile of an empty tensor) - raising would need
     the count on the host."""
     return _GradientLossFn.apply(pred, gt, mask, _check_quantile(quantile, upper_open=False))
+
+
+class _TrackLossesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tracks_3d, pix, rows, vis, weights, tgt_2d, tgt_depth, Ks, quantile):
+        n_pixels, N = tracks_3d.numel() // (3 * tracks_3d.shape[-2]), tracks_3d.shape[-2]
+        t = _f32(tracks_3d)
+        n = pix.numel()
+        scratch, words = _scratch(n, 2, t.device)
+        out = torch.empty(8, device=t.device, dtype=torch.float32)
+        stream = C.c_void_p(L.raw_stream(t.device.index))
+        L.check(L.lib().d4gs_track_losses_fwd(_p(t), _p(pix), _p(rows), _p(vis), _p(weights), _p(tgt_2d), _p(tgt_depth), _p(Ks), n_pixels, N,
+                                              Ks.shape[0], n, quantile, _p(scratch), words, _p(out), stream), "d4gs_track_losses_fwd")
+        ctx.keep = (t, pix, rows, vis, weights, tgt_2d, tgt_depth, Ks, scratch, out)
+        ctx.args = (n_pixels, N, n, quantile, tracks_3d.shape, tracks_3d.dtype)
+        return out[5].clone(), out[6].clone()
+
+    @staticmethod
+    def backward(ctx, v_2d, v_depth):
+        t, pix, rows, vis, weights, tgt_2d, tgt_depth, Ks, scratch, out = ctx.keep
+        n_pixels, N, n, quantile, shape, dtype = ctx.args
+        v = torch.stack([v_2d.detach().float().reshape(()), v_depth.detach().float().reshape(())])
+        v_tracks = torch.empty_like(t)  # zeroed by the entry point, on the stream
+        stream = C.c_void_p(L.raw_stream(t.device.index))
+        L.check(L.lib().d4gs_track_losses_bwd(_p(t), _p(pix), _p(rows), _p(vis), _p(weights), _p(tgt_2d), _p(tgt_depth), _p(Ks), _p(scratch),
+                                              _p(out), _p(v), n_pixels, N, Ks.shape[0], n, quantile, _p(v_tracks), stream),
+                "d4gs_track_losses_bwd")
+        return (v_tracks.reshape(shape).to(dtype),) + (None,) * 8
+
+
+def _per_batch(x, B, name):
+    if torch.is_tensor(x):
+        x = [x]
+    if len(x) != B:
+        raise ValueError(f"{name}: {len(x)} batch entries for tracks_3d of batch {B}")
+    return list(x)
+
+
+def track_losses(tracks_3d, query_tracks_2d, target_Ks, target_tracks_2d, target_visibles, track_weights, target_track_depths,
+                 quantile: float = 0.98):
+    """-> (track_2d_loss, mapped_depth_loss) of flow3d/trainer.py:633-667,681-689.
+
+    tracks_3d [B,H,W,N,3]: the dynamic render's track points in the N target cameras' frames (`SceneModel.render`, B = 1 there).
+    The batch entries of the reference, each a list of B tensors (or one tensor for B = 1): query_tracks_2d [P_b,2] (x, y),
+    target_Ks [N,3,3], target_tracks_2d [N,P_b,2], target_visibles [N,P_b] bool, target_track_depths [N,P_b]; P_b may differ
+    between entries.  An element is (b, n, p) in that order, sum_b N P_b of them.  track_weights: one weight per element, shaped
+    [n], [n,1] or [n,M]; a trailing axis is summed, which is what the reference's masked_l1_loss makes of its [P_all, B N] product
+    `confidences[..., None] * w_interval`.
+
+    Per visible element: X = tracks_3d[b, int(y_p), int(x_p), n], P = K[b,n] X, z = max(P_z, 1e-6), xy = P_xy / z;
+      track_2d_loss     = masked_l1_loss(xy, target 2-D, weights, quantile=quantile) over the visible elements - WITHOUT the
+                          reference's `/ max(H, W)`: the caller divides, as the trainer does
+      mapped_depth_loss = masked_l1_loss(1 / (z + 1e-5), 1 / (target depth + 1e-5), weights) over the same (quantile 1: all kept)
+    Differentiable w.r.t. tracks_3d only.  Nothing is read on the host: the element tables are built with torch ops, the visible
+    count is formed on the device, so the call can sit inside a captured HIP graph.
+
+    Deviations from the reference:
+      pairing - the reference pairs the i-th pixel of the queries' image mask in raster order with the i-th query; here query p
+        is paired with its own pixel.  The two agree exactly when a frame's queries are distinct and in raster order; otherwise
+        the reference raises or mispairs.
+      no visible element - the 2-D term is NaN (with quantile >= 1: 0) and the depth term 0, where the reference raises
+        (torch.quantile of nothing); raising would need the count on the host.  Same as compute_gradient_loss.
+      a query outside the image - its elements are treated as not visible (the reference's indexing faults or wraps); no address
+        is formed from such a pixel.
+    The gradient is scattered with float atomicAdd onto a zeroed image because queries of one row may share a pixel.  With distinct
+    pixels per row every address receives exactly one add onto zero, so the result is bitwise reproducible."""
+    q = _check_quantile(quantile, upper_open=True)
+    if not torch.is_tensor(tracks_3d) or tracks_3d.dim() != 5 or tracks_3d.shape[-1] != 3:
+        raise ValueError("tracks_3d must be a [B,H,W,N,3] tensor")
+    if not tracks_3d.is_cuda:
+        raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+    B, H, W, N, _ = tracks_3d.shape
+    if B * H * W * N == 0:
+        raise ValueError(f"tracks_3d {tuple(tracks_3d.shape)} is empty")
+    queries, Ks = _per_batch(query_tracks_2d, B, "query_tracks_2d"), _per_batch(target_Ks, B, "target_Ks")
+    tgt2d, visibles = _per_batch(target_tracks_2d, B, "target_tracks_2d"), _per_batch(target_visibles, B, "target_visibles")
+    depths = _per_batch(target_track_depths, B, "target_track_depths")
+    dev = tracks_3d.device
+    pix, rows = [], []
+    for b in range(B):
+        if queries[b].dim() != 2 or queries[b].shape[1] != 2:
+            raise ValueError(f"query_tracks_2d[{b}] {tuple(queries[b].shape)} must be [P,2]")
+        P = queries[b].shape[0]
+        for name, x, want in (("target_Ks", Ks[b], (N, 3, 3)), ("target_tracks_2d", tgt2d[b], (N, P, 2)),
+                              ("target_visibles", visibles[b], (N, P)), ("target_track_depths", depths[b], (N, P))):
+            if tuple(x.shape) != want:
+                raise ValueError(f"{name}[{b}] {tuple(x.shape)} must be {want} (N = {N} target frames, {P} queries)")
+        for x in (queries[b], Ks[b], tgt2d[b], visibles[b], depths[b]):
+            if not x.is_cuda:
+                raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+        xy = queries[b].detach().to(torch.int64)  # truncated, as the reference's query_pixels
+        x, y = xy[:, 0], xy[:, 1]
+        inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+        flat = torch.where(inside, (b * H + y) * W + x, torch.full_like(x, -1)).to(torch.int32)
+        pix.append(flat[None].expand(N, P).reshape(-1))
+        rows.append((b * N + torch.arange(N, device=dev, dtype=torch.int32))[:, None].expand(N, P).reshape(-1))
+    pix, rows = torch.cat(pix).contiguous(), torch.cat(rows).contiguous()
+    n = pix.numel()
+    if n == 0:
+        raise ValueError("no query tracks")
+    w = track_weights
+    if not torch.is_tensor(w) or w.dim() not in (1, 2) or w.shape[0] != n:
+        raise ValueError(f"track_weights {tuple(w.shape) if torch.is_tensor(w) else type(w)} must be [{n}], [{n},1] or [{n},M]: one row per "
+                         "(batch entry, target frame, query)")
+    if not w.is_cuda:
+        raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+    w = _f32(w)
+    if w.dim() == 2:
+        w = w.sum(-1)
+    vis = torch.cat([v.detach().reshape(-1) != 0 for v in visibles]).to(torch.uint8).contiguous()
+    return _TrackLossesFn.apply(tracks_3d, pix, rows, vis, w.contiguous(), _f32(torch.cat([t.reshape(-1, 2) for t in tgt2d])),
+                                _f32(torch.cat([d.reshape(-1) for d in depths])), _f32(torch.cat(Ks).reshape(-1, 9)), q)

@@ -5,16 +5,21 @@ Mirrors the SHAPE of the reference's `Trainer.train_step` (flow3d/trainer.py:203
 (static `bg_only` blurry frame, dynamic full blurry frame with mask / track / depth channels, static `mid` frame),
 the reference's photometric loss (0.8 L1 + 0.2 (1 - SSIM), fused), one Adam optimizer per parameter tensor, the
 densification statistics of `_prepare_control_step` and (with --control-every) the densify / cull control steps -
-without the reference's data pipeline or its track losses (out of scope).  With --depth-losses the step
+without the reference's data pipeline (out of scope).  With --depth-losses the step
 also carries the reference's quantile-trimmed losses (deblur4dgs_amd.losses): the disparity loss and the
 depth-gradient loss on the `mid` render (trainer.py:399-416) and the L1 term of the mask loss on the dynamic render (:626-630).
 With --consistency-loss the dynamic group's loss gains the reference's flow-aligned exposure consistency term (trainer.py:599-618,
 weight 2; deblur4dgs_amd.pwcnet) under a seeded random-weight PWC-Net - the pretrained blob is not shipped.
+With --track-losses the 2-D track loss and the mapped-depth loss (trainer.py:633-667,681-689; deblur4dgs_amd.losses.track_losses,
+DESIGN.md section 17) on synthetic query tracks replace the stand-in that otherwise gives the twelve track channels a gradient;
+`--track-losses torch` evaluates the same two terms the way the reference writes them, in eager torch (a timing comparator: it
+waits for the device and cannot be captured).
 It exists to show the seam in a real autograd + optimizer loop:
 
     python examples/train_dynamic_step.py --steps 20
     python examples/train_dynamic_step.py --graph --hip-adam --depth-losses
     python examples/train_dynamic_step.py --graph --hip-adam --consistency-loss
+    python examples/train_dynamic_step.py --graph --hip-adam --track-losses
 """
 from __future__ import annotations
 
@@ -29,7 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from deblur4dgs_amd import engine  # noqa: E402
 from deblur4dgs_amd.control import ControlCfg, accumulate_from_model, cull_step, densify_step, spatial_order_step  # noqa: E402
-from deblur4dgs_amd.losses import compute_gradient_loss, masked_l1_loss, photometric_loss  # noqa: E402
+from deblur4dgs_amd.losses import compute_gradient_loss, masked_l1_loss, photometric_loss, track_losses as hip_track_losses  # noqa: E402
 from deblur4dgs_amd.pwcnet import PWCNet, exposure_consistency_loss  # noqa: E402
 from deblur4dgs_amd.scene_model import GaussianParams, MotionBases, SceneModel  # noqa: E402
 from deblur4dgs_amd.synth import make_scene  # noqa: E402
@@ -45,8 +50,53 @@ def build(n_fg=40_000, n_bg=100_000, K=20, W=512, H=288, dev="cuda:0", seed=0):
     return model.to(dev), sc
 
 
+def make_tracks(tgt_tracks_3d, target_Ks, target_ts, t, n_tracks, seed):
+    """Synthetic track supervision for the dynamic frame, in the reference's batch layout: `n_tracks` distinct query pixels in raster
+    order, and per target frame the 2-D position and depth the target scene's own track points project to (plus a pixel of noise),
+    a visibility and a confidence from the seed.  -> the arguments of track_losses after tracks_3d."""
+    _, H, W, N, _ = tgt_tracks_3d.shape
+    dev = tgt_tracks_3d.device
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.sort(torch.randperm(H * W, generator=g)[:n_tracks]).values.to(dev)
+    query = torch.stack([idx % W, idx // W], -1).float()
+    P = query.shape[0]
+    proj = torch.einsum("nij,pnj->npi", target_Ks, tgt_tracks_3d[0].reshape(H * W, N, 3)[idx])
+    depth = proj[..., 2].clamp(min=1e-6)
+    r = lambda *s: torch.rand(*s, generator=g).to(dev)
+    target_2d = proj[..., :2] / depth[..., None] + 2.0 * (r(N, P, 2) - 0.5)
+    visibles = (r(N, P) < 0.7) & (proj[..., 2] > 0.01)  # (a hole of the synthetic target has no point to track)
+    confidences = r(N * P)
+    num_frames = 7  # the example's clip: the frame at t = 3 and targets around it
+    w_interval = torch.exp(-2.0 * (t - target_ts).abs() / num_frames)
+    return query, target_Ks, target_2d, visibles, confidences[:, None] * w_interval, depth * (1.0 + 0.1 * (r(N, P) - 0.5))
+
+
+def torch_track_losses(tracks_3d, query, target_Ks, target_2d, visibles, weights, target_depths, quantile=0.98):
+    """The same two terms in eager torch over the whole image, the reference's way: project every pixel of every target image, pick
+    the query pixels with a boolean image mask and the visible ones with a second (each a `nonzero`: the host waits for the device)
+    and take the threshold with torch.quantile (a full sort).  A timing comparator for track_losses; it cannot be captured."""
+    _, H, W, N, _ = tracks_3d.shape
+    proj = torch.einsum("nij,npj->npi", target_Ks, tracks_3d[0].permute(2, 0, 1, 3).reshape(N, H * W, 3))
+    depth = proj[..., 2:].clamp(min=1e-6)
+    xy = proj[..., :2] / depth
+    image_mask = torch.zeros(H, W, device=tracks_3d.device)
+    qi = query.to(torch.int64)
+    image_mask[qi[:, 1], qi[:, 0]] = 1.0
+    at_queries = image_mask.reshape(1, H * W).expand(N, H * W) > 0.5
+    vis = visibles.reshape(-1)
+    w = weights[vis].sum(-1)
+
+    def normalised(v, keep):
+        return (v * w)[keep].sum() / (w[keep].sum() + 1e-8)
+
+    v2d = (xy[at_queries][vis] - target_2d.reshape(-1, 2)[vis]).abs().mean(-1)
+    vdepth = (1 / (depth[at_queries][vis] + 1e-5) - 1 / (target_depths.reshape(-1)[vis, None] + 1e-5)).abs()[:, 0]
+    return normalised(v2d, v2d < torch.quantile(v2d, quantile)), normalised(vdepth, torch.ones_like(vis[vis]))
+
+
 def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, fused_stats=True, deferred=True,
-          graph=False, hip_adam=False, seed=0, step_events=None, depth_losses=False, consistency_loss=False, **kw):
+          graph=False, hip_adam=False, seed=0, step_events=None, depth_losses=False, consistency_loss=False, track_losses=False,
+          n_tracks=4096, **kw):
     """fused_stats: the densification statistics come out of the rasterizer's backward (attach_control_stats) instead
     of a pass over `_current_xys[i].grad`; deferred: no render waits for its intersection count on the host
     (`deferred_size_check`), the counts are verified once per step; graph: the three renders, the loss and the whole
@@ -58,8 +108,12 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
     begins (per-step times without a host sync: scripts/bench_adam.py); depth_losses: add the reference's disparity, depth-gradient
     and mask-L1 losses with its default weights (configs.py: w_depth_reg 0.5, w_depth_grad 1, w_mask 1) - they wait for nothing on
     the host, so the step still captures; consistency_loss: add 2 x exposure_consistency_loss of the dynamic render's sub-samples
-    (one batched PWC-Net pass of 2 (S - 1) pairs under no_grad, one loss kernel; no host wait either)."""
+    (one batched PWC-Net pass of 2 (S - 1) pairs under no_grad, one loss kernel; no host wait either); track_losses: the 2-D track
+    loss and the mapped-depth loss on `n_tracks` synthetic query tracks (make_tracks) with the reference's weights (configs.py:
+    w_track 2 after its division by max(H, W), w_depth_const 0.1) in place of the stand-in on the track channels - True: the HIP
+    path, which captures; "torch": the reference's formulation in eager torch, which waits for the device and does not."""
     assert not graph or (fused_stats and deferred), "graph capture needs the sync-free step"
+    assert track_losses in (False, True, "torch") and not (graph and track_losses == "torch"), "the torch form cannot be captured"
     model, sc = build(W=W, H=H, dev=dev, seed=seed, **kw)
     model.deferred_size_check = bool(deferred)
     w2c, K = sc["viewmat"][None].to(dev), sc["K"][None].to(dev)
@@ -76,6 +130,11 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
             # where the target's background covers the pixel: a hole has depth 0, a disparity of 1e5
             depth_masks = (1.0 - tgt_mask) * (tgt_mid["acc"] > 0.5).float()
             depth_valid = depth_masks > 0.5
+        if track_losses:  # supervision from the perturbed scene's own track points
+            tgt_ts = torch.tensor([1.0, 2.0, 4.0, 5.0], device=dev)
+            tgt_tracks = tgt_model.render(3, w2c, K, (W, H), target_ts=tgt_ts, target_w2cs=w2c.expand(4, 4, 4).contiguous(),
+                                          mode="blury")["tracks_3d"]
+            tracks = make_tracks(tgt_tracks, K.expand(4, 3, 3).contiguous(), tgt_ts, 3.0, min(n_tracks, W * H), seed)
     alignnet = None
     if consistency_loss:  # a seeded random-weight flow network, frozen: the loss differentiates the images, not the network
         with torch.random.fork_rng(devices=[]):
@@ -115,7 +174,12 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
         out3 = model.render(3, w2c, K, (W, H), bg_only=True, return_depth=True, mode="mid")
         # the reference's photometric term, 0.8 L1 + 0.2 (1 - SSIM) (trainer.py:388-392,575-586), fused
         loss = photometric_loss(out1["img"], tgt_sta) + photometric_loss(out2["img"], tgt_dyn) + \
-            0.1 * photometric_loss(out3["img"], tgt_sta) + 1e-3 * out2["tracks_3d"].square().mean()
+            0.1 * photometric_loss(out3["img"], tgt_sta)
+        if track_losses:
+            l2d, ldepth = (torch_track_losses if track_losses == "torch" else hip_track_losses)(out2["tracks_3d"], *tracks)
+            loss = loss + 2.0 * l2d / max(H, W) + 0.1 * ldepth
+        else:  # a stand-in that gives the track channels a gradient
+            loss = loss + 1e-3 * out2["tracks_3d"].square().mean()
         if depth_losses:
             pred_disp = 1.0 / (out3["depth"] + 1e-5)
             loss = loss + 0.5 * masked_l1_loss(pred_disp, tgt_disp, mask=depth_masks, quantile=0.98) + \
@@ -222,6 +286,11 @@ if __name__ == "__main__":
                     help="add the reference's disparity, depth-gradient and mask-L1 losses (quantile-trimmed, HIP, graph-capturable)")
     ap.add_argument("--consistency-loss", action="store_true",
                     help="add the reference's flow-aligned exposure consistency loss (HIP cost volume and warp, graph-capturable)")
+    ap.add_argument("--track-losses", nargs="?", const="hip", default=None, choices=("hip", "torch"),
+                    help="the reference's 2-D track and mapped-depth losses on synthetic query tracks: HIP and graph-capturable, or "
+                         "`torch`: the reference's eager formulation (full-image projection, boolean selection, torch.quantile)")
+    ap.add_argument("--tracks", type=int, default=4096, help="query tracks of --track-losses")
     a = ap.parse_args()
     train(a.steps, control_every=a.control_every, fused_stats=not a.round1, deferred=not a.round1, graph=a.graph, hip_adam=a.hip_adam,
-          depth_losses=a.depth_losses, consistency_loss=a.consistency_loss)
+          depth_losses=a.depth_losses, consistency_loss=a.consistency_loss,
+          track_losses={None: False, "hip": True, "torch": "torch"}[a.track_losses], n_tracks=a.tracks)

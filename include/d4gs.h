@@ -592,12 +592,13 @@ D4GS_API int d4gs_adam_step_cpu(const D4gsAdamRec *table, int32_t n_records);
  * cannot be done without a host wait) and 0 for normalize != 0.  Non-finite inputs are out of scope (no out-of-bounds access).
  * pred, gt [n, D] (D >= 1) fp32 contiguous; 0 <= n, B H W <= 2^31 - 1.  scratch: d4gs_trimmed_scratch_words(n, 1) 32-bit words
  * (gradient: (B H W, 2)), 8-byte aligned; the forward leaves the elements in its first n (gradient: 2 B H W) words - the `values`
- * the backward wants - and writes out [8]: out[0] the loss, out[1] / out[3] the thresholds, out[2] / out[4] 1 / denominator per term.
+ * the backward wants - and writes out [8]: out[0] the loss, out[1] / out[3] the thresholds, out[2] / out[4] 1 / denominator per term
+ * (and out[5] / out[6] each term's own loss).
  * Backward: v_pred = v_loss[0] * dL/dpred (v_loss: device scalar), sign(pred - gt) / D * m_i / denominator on kept elements and
  * zero elsewhere; the gradient form gathers per pixel from its at most four pairs (no atomics).  Nothing flows to gt or the mask.
  * Every sum has a fixed order and the histograms are integer: bitwise reproducible.  D4GS_EINVAL before any GPU call for a NULL
  * pointer, a negative or too large size, a quantile that is not finite or <= 0, or undersized / misaligned scratch. */
-D4GS_API int64_t d4gs_trimmed_scratch_words(int64_t n_max, int32_t terms); /* terms: 1, or 2 for the gradient form; 0: bad argument */
+D4GS_API int64_t d4gs_trimmed_scratch_words(int64_t n_max, int32_t terms); /* terms: 1, or 2 for the gradient and track forms; 0: bad argument */
 D4GS_API int d4gs_masked_l1_fwd(const float *pred, const float *gt, const float *mask, int64_t n, int32_t D, int32_t normalize,
                                 float quantile, void *scratch, int64_t scratch_words, float *out, void *stream);
 D4GS_API int d4gs_masked_l1_bwd(const float *pred, const float *gt, const float *mask, const float *values, const float *out,
@@ -610,6 +611,30 @@ D4GS_API int d4gs_gradient_loss_fwd(const float *pred, const float *gt, const fl
                                     float quantile, void *scratch, int64_t scratch_words, float *out, void *stream);
 D4GS_API int d4gs_gradient_loss_bwd(const float *pred, const float *gt, const float *mask, const float *values, const float *out,
                                     const float *v_loss, int32_t B, int32_t H, int32_t W, float *v_pred, void *stream);
+/* The 2-D track loss and the mapped (track) depth loss of Trainer.compute_dynamic_losses (flow3d/trainer.py:633-667,681-689) in one
+ * pass over n_elements elements e = (row r = b N + n over batch x target frames, query p), ordered as the reference concatenates
+ * its targets.  Per element: pix[e] the query's flat pixel in [B,H,W] (n_pixels = B H W), rows[e] = r, visible[e] one byte, weights[e],
+ * target_2d[e] = (u, v), target_depth[e] = d; Ks [n_rows,3,3] row-major.  A live element (visible != 0, 0 <= pix < n_pixels,
+ * 0 <= rows < n_rows; nothing is read through an index outside these ranges) takes X = tracks_3d[pix, rows % N, 0:3] from the
+ * channel-last [n_pixels, N, 3] image, P = K[r] X, z = max(P_z, 1e-6), (x, y) = P_xy / z, and gives
+ *   term 0: 0.5 (|x - u| + |y - v|), kept when strictly below torch.quantile of the live term-0 elements (quantile >= 1: all kept)
+ *   term 1: |1 / (z + 1e-5) - 1 / (d + 1e-5)|, always kept (the reference's default quantile of 1)
+ * each term = sum_kept v w / (sum_kept w + 1e-8).  The live count is formed on the device.  No live element: term 0 is NaN when it
+ * selects (the reference raises), term 1 is 0.  scratch: d4gs_trimmed_scratch_words(n_elements, 2); its first 2 n_elements words are
+ * the `values` of the backward.  out [8]: out[1] / out[3] thresholds, out[2] / out[4] 1 / denominator, out[5] term 0, out[6] term 1
+ * (out[0] their plain sum).  Backward: v_losses [2] (device) the two upstream gradients; v_tracks_3d [n_pixels, N, 3] is zeroed on
+ * the stream, then every live element adds K^T dL/dP to its point with a float atomicAdd - queries of one row may share a pixel.
+ * With distinct pixels per row every address receives one add onto zero: bitwise reproducible.  No gradient reaches P_z where the
+ * clamp is active (x and y still divide by 1e-6 there).  D4GS_EINVAL before any GPU call for a NULL pointer, N < 1, n_rows not a
+ * positive multiple of N, n_elements < 1, n_pixels < 1 (or either above 2^31 - 1), a bad quantile, undersized / misaligned scratch. */
+D4GS_API int d4gs_track_losses_fwd(const float *tracks_3d, const int32_t *pix, const int32_t *rows, const uint8_t *visible,
+                                   const float *weights, const float *target_2d, const float *target_depth, const float *Ks,
+                                   int64_t n_pixels, int32_t N, int32_t n_rows, int64_t n_elements, float quantile, void *scratch,
+                                   int64_t scratch_words, float *out, void *stream);
+D4GS_API int d4gs_track_losses_bwd(const float *tracks_3d, const int32_t *pix, const int32_t *rows, const uint8_t *visible,
+                                   const float *weights, const float *target_2d, const float *target_depth, const float *Ks,
+                                   const float *values, const float *out, const float *v_losses, int64_t n_pixels, int32_t N,
+                                   int32_t n_rows, int64_t n_elements, float quantile, float *v_tracks_3d, void *stream);
 
 /* Flow-aligned exposure consistency (appended; D4GS_VERSION unchanged): the pieces of the reference's AlignedLoss (flow3d/loss_utils.py,
  * flow3d/models/pwcnet.py) that are not convolutions.  Every tensor is fp32, contiguous, NCHW.
