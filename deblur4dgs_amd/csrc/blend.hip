@@ -16,7 +16,8 @@ struct Policy {
 };
 
 // `win` (optional, [P][C] bytes): for the max / min channels, the sub-sample k_blend_bwd's first-match rule would hand the gradient to
-// (-1: the mean) - the one-call backward reads it instead of re-deriving it from the S - 1 renders (frame.hip, BlendAdj)
+// (-1: the mean) - the one-call backward reads it instead of re-deriving it from the S - 1 renders (frame.hip, BlendAdj).  One signed
+// byte: S <= D4GS_FRAME_BLEND_MAX_S = 129, checked by d4gs_forward and by d4gs_blend_fwd_impl.
 // sum of x[s * stride] over s < S in ascending s, the loads of eight sub-samples in flight at a time.  (Round 5: written as a plain
 // `for` the compiler kept ONE load in flight per lane - load, s_waitcnt vmcnt(0), add, branch - so a lane paid S dependent memory
 // round trips: k_blend_fwd ran at 2.0 - 2.4 TB/s; same additions in the same order, bit for bit.)
@@ -245,6 +246,10 @@ int d4gs_blend_fwd_impl(int32_t S, int64_t P, int32_t C, const int32_t *policy, 
   Policy pol;
   if (C > 64 || C <= 0) {
     d4gs_set_error("blend: C=%d out of range (1..64)", C);
+    return D4GS_EINVAL;
+  }
+  if (win && S > D4GS_FRAME_BLEND_MAX_S) {  // (int8_t)w below: the candidates 0 .. S - 2 must fit 0 .. 127
+    d4gs_set_error("blend: S=%d with a winner map (at most %d)", S, D4GS_FRAME_BLEND_MAX_S);
     return D4GS_EINVAL;
   }
   for (int c = 0; c < 64; c++) pol.p[c] = (c < C && policy) ? (int8_t)policy[c] : 0;

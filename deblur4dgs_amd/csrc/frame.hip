@@ -87,6 +87,11 @@ int check_frame(const char *who, const D4gsDims *d, const D4gsProjIn *in, const 
   int rc = d4gs_query_sizes(d, &z);  // validates dims
   if (rc) return rc;
   if (d->D == 0) return frame_refuses_depth_only(who);
+  if (io && io->blended && d->S > D4GS_FRAME_BLEND_MAX_S) {  // (the winner map is int8_t: index S - 2 must fit)
+    d4gs_set_error("%s: S=%d sub-samples with a blended frame, the one-call frame takes at most %d (its winner map holds one signed byte "
+                   "per pixel and channel); use the staged entry points", who, d->S, D4GS_FRAME_BLEND_MAX_S);
+    return D4GS_EINVAL;
+  }
   if (!in || !io || !ws || !io->renders || !io->alphas || !io->means2d || !io->radii || !io->n_isect ||
       (io->blended && !io->acc) || !in->means || !in->quats || !in->scales || !in->opacities || !in->colors || !in->viewmat ||
       !in->Kmat || (d->G > 0 && (!in->motion_coefs || !in->rots || !in->transls || !in->times)) || d->N == 0) {

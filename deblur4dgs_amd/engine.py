@@ -917,9 +917,14 @@ class FrameFn(torch.autograd.Function):
         return (None, None, *_only_needed([g["v_" + k] for k in _LEAVES], ctx.needs), None, None)
 
 
-def frame_supported(cfg: RenderCfg) -> bool:
-    """One kernel width, no channel chunking: what the one-call path covers."""
-    return cfg.N > 0 and cfg.D in SUPPORTED_D
+FRAME_BLEND_MAX_S = 129  # D4GS_FRAME_BLEND_MAX_S of include/d4gs.h
+
+
+def frame_supported(cfg: RenderCfg, blended: bool = True) -> bool:
+    """One kernel width, no channel chunking: what the one-call path covers.  With a blended frame, at most FRAME_BLEND_MAX_S
+    sub-samples: its winner map holds the max / min channels' winning sub-sample (0 .. S - 2) in one signed byte - beyond that
+    d4gs_forward refuses and the staged chain, whose k_blend_bwd searches the renders, takes the frame."""
+    return cfg.N > 0 and cfg.D in SUPPORTED_D and not (blended and cfg.S > FRAME_BLEND_MAX_S)
 
 
 class PosesFn(torch.autograd.Function):

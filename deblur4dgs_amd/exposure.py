@@ -93,7 +93,8 @@ def render_exposure(
 ):
     """-> dict(renders [S,H,W,D'], alphas [S,H,W,1], blended [H,W,D'] | None, acc [H,W] | None,
                means2d [S,N,2], radii [S,N], state).
-    fused=True takes the one-call path (engine.FrameFn) when the channel count needs no chunking: one autograd node, every
+    fused=True takes the one-call path (engine.FrameFn) when the channel count needs no chunking and, with blend=True, S <= 129
+    (engine.frame_supported; the staged chain below otherwise, same bits): one autograd node, every
     output differentiable; `means2d` is then a plain tensor whose gradient lands in state.xys_sink / state.v_means2d.
     absgrad=True (RenderCfg.absgrad): the backward also leaves gsplat's absgrad [S,N,2] in state.v_means2d_abs (and as `.absgrad`
     of `means2d` on the staged chain, of the xys_sink tensors on the one-call path).
@@ -111,7 +112,7 @@ def render_exposure(
                     exact_cull=exact_cull, grad_arena=grad_arena, control_stats=control_stats,
                     deferred_size_check=deferred_size_check, lazy_sort=lazy_sort, near_target=near_target, exact_tiles=exact_tiles,
                     absgrad=absgrad, antialiased=antialiased)
-    if fused and frame_supported(cfg):
+    if fused and frame_supported(cfg, blended=blend):
         # ONE autograd node over d4gs_forward / d4gs_backward: same kernels and bits as the staged chain below, a fraction
         # of its host work.  `means2d` is then a plain tensor; its gradient goes to st.xys_sink / st.v_means2d.
         resolve_lazy(cfg, means.device)

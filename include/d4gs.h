@@ -467,8 +467,12 @@ D4GS_API int d4gs_blend_bwd(int32_t S, int64_t n_pixels, int32_t C, const int32_
  * The backward takes any of v_blended, v_acc, v_renders, v_alphas when io->blended was given (losses on the blurry frame and
  * on the per-sub-sample images, flow3d/trainer.py:575-618), else v_renders [+ v_alphas]; a caller that needs `means2d` as an
  * autograd intermediate or renders more than 16 colour channels uses the staged entry points. */
+#define D4GS_FRAME_BLEND_MAX_S 129
 typedef struct D4gsFrameIO {
-  float *blended;          /* [H,W,D+depth] or NULL: no blend */
+  float *blended;          /* [H,W,D+depth] or NULL: no blend.  With it, S <= D4GS_FRAME_BLEND_MAX_S (else D4GS_EINVAL): the one-call path
+                              keeps the max / min channels' winning sub-sample as one signed byte per pixel and channel (0 .. 127; -1 =
+                              the mean), and the candidates are the sub-samples 0 .. S - 2.  More sub-samples: the staged entry points
+                              (d4gs_blend_bwd searches the renders for the winner and has no such limit). */
   float *acc;              /* [H,W] (with blended) */
   float *renders;          /* [S,H,W,D+depth] */
   float *alphas;           /* [S,H,W] */

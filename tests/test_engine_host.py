@@ -276,3 +276,48 @@ def test_lazy_sort_auto_decides_from_the_capacity_with_its_constant_left_in(monk
         assert cfg.near_target == (max(256, int(2.5 * f * cap / 1.25 / lists)) if want else 0), (cap, f)
     engine._guess_drop(base + (False,))  # nothing measured: off, whatever the live fraction
     assert engine.resolve_lazy(mk(), dev).lazy_sort is False
+
+
+def test_frame_supported_caps_the_sub_samples_of_a_blended_frame():
+    """The one-call path's winner map is one signed byte per pixel and channel: candidates 0 .. S - 2 <= 127, i.e. S <= 129 with a
+    blended frame (include/d4gs.h, D4GS_FRAME_BLEND_MAX_S); an unblended frame has no map and no cap."""
+    import os
+    import re
+
+    mk = lambda S, D=3, N=100: engine.RenderCfg(N=N, G=0, K=0, T=0, S=S, D=D, width=16, height=16)
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "d4gs.h")).read()
+    assert int(re.search(r"#define\s+D4GS_FRAME_BLEND_MAX_S\s+(\d+)", hdr).group(1)) == engine.FRAME_BLEND_MAX_S == 129
+    assert engine.FRAME_BLEND_MAX_S - 2 == 127  # the last candidate's index is the largest int8_t
+    for S in (1, 11, 128, 129):
+        assert engine.frame_supported(mk(S)) and engine.frame_supported(mk(S), blended=True) and engine.frame_supported(mk(S), blended=False)
+    for S in (130, 131, 257, 1000):
+        assert not engine.frame_supported(mk(S)) and not engine.frame_supported(mk(S), blended=True)
+        assert engine.frame_supported(mk(S), blended=False)
+    assert not engine.frame_supported(mk(3, N=0)) and not engine.frame_supported(mk(3, D=22), blended=False)  # (as before)
+
+
+def test_one_call_entry_points_refuse_a_blended_frame_of_more_than_129_sub_samples():
+    """d4gs_forward / d4gs_backward return D4GS_EINVAL with a message before any HIP call (the fake addresses are never dereferenced)."""
+    import ctypes as C
+
+    from deblur4dgs_amd import _lib as L
+    from tests.test_absgrad_abi import FAKE, _frame_args
+
+    lib = L.lib()
+    d, pin, io, leaf = _frame_args(0)
+    io.blended, io.acc = FAKE, FAKE
+    fg = L.FrameGrads(v_blended=FAKE, v_means2d=FAKE)
+    ws = C.c_void_p(FAKE)
+    for S, refused in ((129, False), (130, True)):
+        d.S = S
+        rc = lib.d4gs_forward(C.byref(d), C.byref(pin), C.byref(io), ws, 0, 1000, 0, None)
+        rcb = lib.d4gs_backward(C.byref(d), C.byref(pin), C.byref(io), C.byref(fg), C.byref(leaf), ws, 0, 1000, 0, None)
+        msg = lib.d4gs_last_error()
+        if refused:
+            assert rc == -1 and rcb == -1 and b"at most 129" in msg, (rc, rcb, msg)
+        else:  # passes the cap and stops at the next check: the workspace of 0 bytes
+            assert rc != 0 and rcb != 0 and b"workspace" in msg, (rc, rcb, msg)
+    d.S = 130
+    io.blended, io.acc = None, None  # no blend, no map, no cap
+    assert lib.d4gs_forward(C.byref(d), C.byref(pin), C.byref(io), ws, 0, 1000, 0, None) != 0
+    assert b"workspace" in lib.d4gs_last_error(), lib.d4gs_last_error()

@@ -24,14 +24,50 @@ def _render(L, K, W, H, fused, blend=True, D=3, **kw):
                            return_depth=True, blend=blend, fused=fused, **kw)
 
 
+def _check_static_routing(grad, wb, ws, S, D):
+    """The gradient BlendFn left on S EQUAL renders [S,H,W,D+1] for the cotangent `wb` on the blended frame: on a max / min channel of
+    the reference's policy a pixel gave g to sub-sample 0 and nothing to the others, or g * (1 / S) to each.  Exact when no further
+    cotangent `ws` sits on the renders themselves; with one, k_blend_bwd adds it in (one more rounding, maybe fused): 2 ulp of the sum."""
+    from deblur4dgs_amd.exposure import POLICY_MEAN, reference_policy
+
+    pol = reference_policy(D + 1)
+    pc = [c for c, p in enumerate(pol) if p != POLICY_MEAN]
+    assert pc and 3 in pc
+    g = wb[..., pc]
+    first = torch.zeros(S, 1, 1, 1, device=grad.device)
+    first[0] = 1.0
+    to_first, spread = (first * g[None]), (g * (torch.ones((), device=grad.device) / S))[None].expand(S, *g.shape)
+    got = grad[..., pc]
+    if ws is None:
+        a, b = (got == to_first).all(0), (got == spread).all(0)
+    else:
+        tol = 2 * 2.0 ** -23 * (g.abs()[None] + ws[..., pc].abs())
+        a, b = ((got - (to_first + ws[..., pc])).abs() <= tol).all(0), ((got - (spread + ws[..., pc])).abs() <= tol).all(0)
+    assert bool((a | b).all()), int((~(a | b)).sum())
+    assert bool(a.any())  # the tie went to sub-sample 0 somewhere (the mean of S equal values rounds to them, or to their wrong side)
+    for c in range(D + 1):  # and a mean channel spreads
+        if c not in pc and ws is None:
+            assert torch.equal(grad[..., c], (wb[..., c] * (torch.ones((), device=grad.device) / S))[None].expand(S, -1, -1))
+
+
 @pytest.mark.parametrize("sub_losses", [True, False])
-@pytest.mark.parametrize("N,G,K_,S,W,H,D", [(5000, 3000, 4, 3, 160, 96, 3), (800, 0, 1, 1, 64, 48, 3), (3000, 3000, 12, 5, 96, 64, 16)])
+@pytest.mark.parametrize("N,G,K_,S,W,H,D", [(5000, 3000, 4, 3, 160, 96, 3), (800, 0, 1, 1, 64, 48, 3), (3000, 3000, 12, 5, 96, 64, 16),
+                                           # the winner map past one 8-wide batch of the blend's scan (S - 1 candidates: 8, 10, 16), read by the
+                                           # folded adjoint (D = 3 + depth) and by k_blend_bwd (D = 16, and wherever sub_losses is set)
+                                           (600, 400, 3, 9, 64, 48, 3), (600, 400, 3, 11, 64, 48, 3), (600, 400, 3, 17, 64, 48, 3),
+                                           (600, 400, 3, 9, 64, 48, 16), (600, 400, 3, 11, 64, 48, 16), (600, 400, 3, 17, 64, 48, 16),
+                                           # G = 0 and S > 1: a STATIC scene under a camera that does not move - every pixel of a max / min
+                                           # channel is an S-way tie, as on every background pixel in training
+                                           (500, 0, 1, 11, 64, 48, 3), (500, 0, 1, 11, 64, 48, 16)])
 def test_one_call_path_equals_the_staged_chain_bitwise(N, G, K_, S, W, H, D, sub_losses):
     """sub_losses=False: gradients arrive on the blended frame and its accumulation only - d4gs_backward then folds the blend's adjoint
     into the composite backward's prologue (renders of <= 5 colour channels; the max / min channel's winner comes from k_blend_fwd's
-    map) instead of launching k_blend_bwd, which the staged chain always does: the two must still agree bit for bit."""
+    map) instead of launching k_blend_bwd, which the staged chain always does: the two must still agree bit for bit.
+    On the static scene the S sub-sample renders are equal, and the staged chain's gradient on them shows where each max / min pixel
+    sent its gradient: all of it to sub-sample 0 (first in stack order), or spread over all S (the mean won by a rounding) - nothing else."""
     dev = torch.device("cuda:0")
-    sc = make_scene(N, G, max(K_, 1), S, W, H, seed=31)
+    static = G == 0 and S > 1
+    sc = make_scene(N, G, max(K_, 1), S, W, H, seed=31, **(dict(cam_jitter=0.0) if static else {}))
     K = sc["K"].to(dev)
     g = torch.Generator().manual_seed(7)
     wb, wa = torch.randn(H, W, D + 1, generator=g).to(dev), torch.randn(H, W, generator=g).to(dev)
@@ -53,8 +89,14 @@ def test_one_call_path_equals_the_staged_chain_bitwise(N, G, K_, S, W, H, D, sub
             r["state"].xys_sink = xys
         else:
             r["means2d"].retain_grad()
+            if static:
+                assert all(torch.equal(sc["RTs"][s], sc["RTs"][0]) for s in range(S))
+                assert all(torch.equal(r["renders"][s], r["renders"][0]) for s in range(S))  # every max / min pixel: an S-way tie
+                r["renders"].retain_grad()
         loss.backward()
         torch.cuda.synchronize()
+        if static and not fused:
+            _check_static_routing(r["renders"].grad, wb, ws if sub_losses else None, S, D)
         m2g = torch.cat([x.grad for x in xys], 0) if fused else r["means2d"].grad
         out[fused] = dict(blended=r["blended"], acc=r["acc"], renders=r["renders"], alphas=r["alphas"], means2d=r["means2d"],
                           radii=r["radii"], m2g=m2g, **{f"g_{k}": v.grad for k, v in L.items() if v is not None})
@@ -62,6 +104,44 @@ def test_one_call_path_equals_the_staged_chain_bitwise(N, G, K_, S, W, H, D, sub
         b = out[True][k]
         assert a is not None and b is not None and torch.equal(a.detach(), b.detach()), k
     assert float(out[True]["g_means"].abs().max()) > 0 and float(out[True]["m2g"].abs().max()) > 0
+
+
+@pytest.mark.parametrize("sub_losses", [False, True])
+def test_more_sub_samples_than_the_winner_map_can_index_take_the_staged_chain(sub_losses):
+    """k_blend_fwd's winner map holds one signed byte per pixel and channel: the indices 0 .. 127 (and -1, the mean), i.e. S <= 129
+    (D4GS_FRAME_BLEND_MAX_S).  S = 130, where sub-sample 128 can win: render_exposure(fused=True) must give the staged chain's frame and
+    gradients bit for bit (engine.frame_supported sends it there; k_blend_bwd searches the renders and has no such limit).  The scene is
+    one on which 128 does win: with index 128 wrapped to -128, those pixels' gradient was dropped (k_blend_bwd) or spread (the fold)."""
+    dev = torch.device("cuda:0")
+    N, G, K_, S, W, H, D = 48, 32, 2, 130, 16, 16, 3
+    sc = make_scene(N, G, K_, S, W, H, seed=31)
+    sc["scales"] = sc["scales"] + 3.5  # splats a few pixels wide: the 16 x 16 frame is covered
+    K = sc["K"].to(dev)
+    g = torch.Generator().manual_seed(7)
+    wb, wa = torch.randn(H, W, D + 1, generator=g).to(dev), torch.randn(H, W, generator=g).to(dev)
+    ws, wsa = torch.randn(S, H, W, D + 1, generator=g).to(dev), torch.randn(S, H, W, 1, generator=g).to(dev)
+    out = {}
+    for fused in (False, True):
+        L = _leaves(sc, dev)
+        r = _render(L, K, W, H, fused, D=D)
+        loss = (r["blended"] * wb).sum() + (r["acc"] * wa).sum()
+        if sub_losses:
+            loss = loss + (r["renders"] * ws).sum() + (r["alphas"] * wsa).sum()
+        if not fused:
+            r["renders"].retain_grad()
+        loss.backward()
+        torch.cuda.synchronize()
+        if not fused and not sub_losses:  # the case is what it claims: somewhere sub-sample 128 takes the whole gradient of the max channel
+            rg = r["renders"].grad[..., 3]
+            took = (rg[128] == wb[..., 3]) & (rg[:128] == 0).all(0) & (rg[129] == 0)
+            print("pixels whose max-channel gradient goes to sub-sample 128:", int(took.sum()))
+            assert int(took.sum()) >= 8
+        out[fused] = dict(blended=r["blended"], acc=r["acc"], renders=r["renders"], alphas=r["alphas"],
+                          **{f"g_{k}": v.grad for k, v in L.items() if v is not None})
+    for k, a in out[False].items():
+        b = out[True][k]
+        assert a is not None and b is not None and torch.equal(a.detach(), b.detach()), k
+    assert float(out[True]["g_means"].abs().max()) > 0
 
 
 @pytest.mark.parametrize("fused", [True, False])
