@@ -294,13 +294,14 @@ __device__ __forceinline__ void chunk_block(uint64_t (&v)[NV], int lane) {  // t
   chunk_plain<K / 4, NV>(v, lane);
 }
 
-// ---- 512-key chunks in registers (round 3) ---------------------------------------------------------------------------
+// ---- chunks of 64 NV keys in registers (round 3: 512 keys, NV = 8) ---------------------------------------------------
 // A wave holds a chunk of 64 * NV keys as NV registers per lane (key index u * 64 + lane).  Inside the chunk every step
 // of the network stays in registers: partner distances < 64 are the DPP / bpermute lane exchanges above, distances
 // 64 .. 32 NV pair two REGISTERS of the same lane (a plain compare-exchange, no cross-lane traffic at all), and a
 // k-block's flip step pairs register u of lane l with the mirrored register of lane 63 - l.  A list of up to 512 keys
 // is therefore sorted by ONE wave without LDS or barriers (round 2: 6 LDS passes + barriers for 512 keys), and longer
-// lists only go through LDS for distances >= 512 (4096 keys: 6 LDS passes instead of 21).
+// lists only go through LDS for distances of a chunk and more (4096 keys in 512-key chunks: 6 LDS passes instead of 21; sort_list_lds
+// below takes 256-key chunks for lists of 513 ... 1 024 keys, whose steps at distance 256 and 512 then go through LDS).
 __device__ __forceinline__ uint64_t rev64(uint64_t v) { return shfl_xor_u64(v, 63); }
 __device__ __forceinline__ void reg_cex(uint64_t &lo, uint64_t &hi) {  // lo = min, hi = max
   const uint64_t a = lo, b = hi;
@@ -439,6 +440,75 @@ __device__ __forceinline__ void wave_sort_list(const SortArgs &a, int base, int 
     }
   }
 }
+// The 2 048-key class of k_tile_sort (lists of 513 ... 2 048 keys, four waves): the chunk width follows the list length, and the list
+// passes through LDS only between the first register sort and the last in-chunk pass.  Each wave sorts chunks of 64 NV keys in registers;
+// it loads them straight from global memory (key c * chunk + u * 64 + lane, UINT64_MAX beyond the list) and writes `sorted_emit` /
+// `sorted_gid` from its registers after the last in-chunk pass; only the steps whose partner distance is at least a chunk go through LDS
+// (`key`, one barrier each).  NV = 4 for 513 ... 1 024 keys: three or four chunks of 256 keys keep all four waves busy where 512-key
+// chunks left two of them idle (cfg2: median list 937 keys; k_tile_sort 68 -> 55 us, profiles/ab_sort_chunk_width.txt).  Padding as in
+// bitonic_sort_lds: chunks made of padding only and cross-chunk pairs with l >= n are skipped.  What a cross-chunk step reads is
+// initialised: its pairs have i < l < n, and the chunk stores write every whole chunk below nchunks * chunk, padding included.
+// n > 64 NV (block-uniform, like every branch around a barrier here).  k_tile_sort_w<LONG> and the larger classes keep bitonic_sort_lds
+// until this form is measured on the scenes that run them.
+template <int NV>
+__device__ __forceinline__ void sort_list_lds(const SortArgs &a, uint64_t *key, int base, int n) {
+  constexpr int CH = 64 * NV;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int nchunks = (n + CH - 1) / CH;
+  int P = CH;
+  while (P < n) P <<= 1;
+  const uint64_t *gk = a.keys + base;
+  for (int c = wv; c < nchunks; c += nw) {
+    uint64_t v[NV];
+#pragma unroll
+    for (int u = 0; u < NV; u++) {
+      const int p = c * CH + u * 64 + lane;
+      v[u] = p < n ? gk[p] : ~0ull;
+    }
+    chunk_sort<NV>(v, lane);
+#pragma unroll
+    for (int u = 0; u < NV; u++) key[c * CH + u * 64 + lane] = v[u];
+  }
+  __syncthreads();
+  for (int k = 2 * CH; k <= P; k <<= 1) {
+    for (int j = k >> 1; j >= CH; j >>= 1) {  // cross-chunk steps
+      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
+        const int blk = t / j, off = t - blk * j;
+        const int i = blk * 2 * j + off;
+        const int l = (j == (k >> 1)) ? (blk * 2 * j + (2 * j - 1 - off)) : (i + j);
+        if (l < n) {
+          const uint64_t x = key[i], y = key[l];
+          if (x > y) key[i] = y, key[l] = x;
+        }
+      }
+      __syncthreads();
+    }
+    for (int c = wv; c < nchunks; c += nw) {  // distances 32 NV .. 1
+      uint64_t v[NV];
+#pragma unroll
+      for (int u = 0; u < NV; u++) v[u] = key[c * CH + u * 64 + lane];
+      reg_plain<NV, NV / 2>(v);
+      chunk_plain<32, NV>(v, lane);
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int p = c * CH + u * 64 + lane;
+        if (k < P) {
+          key[p] = v[u];
+        } else if (p < n) {  // the list is sorted
+          const uint32_t e = (uint32_t)v[u];
+          a.sorted_emit[base + p] = (int32_t)e;
+          a.sorted_gid[base + p] = a.gid_of_emit[e];
+        }
+      }
+    }
+    if (k < P) __syncthreads();
+  }
+}
+__device__ __forceinline__ void sort_list_lds(const SortArgs &a, uint64_t *key, int base, int n) {
+  if (n <= 2 * CHUNK) sort_list_lds<4>(a, key, base, n);
+  else sort_list_lds<CNV>(a, key, base, n);
+}
+
 // LONG (round 6): the workgroup also sorts those of its four lists that hold 513 ... 2 048 keys - all four waves through 16 KB of LDS, one
 // list after the other, exactly the network of k_tile_sort's first class.  A scene whose lists are mostly short (the reference's training
 // shape: p50 450 keys, a few hundred of 6 336 beyond 512; 720p) used to pay a whole launch of that class for the few: 19-21 / 11 us.
@@ -503,7 +573,9 @@ __global__ void __launch_bounds__(1024) k_tile_sort(const SortArgs a) {
     return;
   }
   uint64_t *gk = a.keys + base;
-  if (a.cap >= 0) {
+  if (a.cap == 4 * CHUNK) {  // the first LDS class
+    sort_list_lds(a, skeys, base, n);
+  } else if (a.cap >= 0) {
     int P = CHUNK;
     while (P < n) P <<= 1;
     for (int p = threadIdx.x; p < P; p += blockDim.x) skeys[p] = p < n ? gk[p] : ~0ull;
