@@ -73,6 +73,75 @@ def test_cpu_twin_matches_the_oracle(N, G, K, S, W, H, mask, depth):
     _close("viewmat", vm.grad[:3], w2c.grad[:3], 0.0)
 
 
+# (N, G, K, S, W, H, seed, camera): the two scenes of the first test under the `general` camera (tests/camera_cases.py: rotated and
+# translated w2c, fx != fy, principal point off centre; camera deltas of 0.03 rad instead of 0.01), then the shapes that
+# tests/test_gpu_camera_general.py renders on the device.  Their seeds are chosen HERE: a GPU case's seed is acceptable when the fp32
+# twin shows no element of a no-allowance tensor (rots, transls, times, RTs, viewmat) beyond 1e-4 of the fp64 oracle - then a miss on
+# the device is the kernels', not the scene's (one alpha / radius decision falling the other way in fp32 moves a whole column sum).
+CAMERA_CASES = [(400, 250, 3, 3, 64, 48, 1100, "general"), (350, 0, 1, 1, 56, 40, 1050, "general")]
+GPU_CAMERA_CASES = [(N, G, K, S, 88, 56, seed, cam) for cam, seeds in (("general", (2102, 2101, 2103)), ("rotated", (2102, 2102, 2104)))
+                    for (N, G, K, S), seed in zip(((900, 500, 4, 3), (900, 900, 12, 1), (700, 0, 1, 2)), seeds)]
+
+
+@pytest.mark.parametrize("N,G,K,S,W,H,seed,camera", CAMERA_CASES + GPU_CAMERA_CASES)
+def test_cpu_twin_matches_the_oracle_under_a_general_camera(N, G, K, S, W, H, seed, camera):
+    """Mask and depth channels on.  Per-Gaussian tensors at TOL with FLIPS; rots, transls, times, RTs and viewmat with no allowance
+    (measured: 2.2e-5 of max|ref| at worst - on viewmat - for the dynamic scene, 7.9e-6 for the static one)."""
+    from deblur4dgs_amd.cpu_twin import render_exposure_cpu
+    from tests import camera_cases
+
+    case = camera_cases.exposure_case(N, G, K, S, W, H, seed, camera)
+    L, colors_in, bgc, Kmat = camera_cases.exposure_leaves(case)
+    res = render_exposure_cpu(L["means"], L["quats"], L["scales"], L["opacities"], colors_in, 3, L["motion_coefs"], L["rots"],
+                              L["transls"], L["times"], L["RTs"], L["viewmat"], Kmat, W, H, background=bgc, return_depth=True)
+    for k in ("renders", "blended", "acc"):
+        _close(k, res[k], case["ref"][k])
+    w = case["w"]
+    ((res["blended"] * w["blended"].float()).sum() + (res["acc"] * w["acc"].float()).sum() + (res["renders"] * w["renders"].float()).sum()).backward()
+    shared = ("rots", "transls", "times", "RTs", "viewmat")
+    for k, want in case["grads"].items():
+        got = L[k].grad
+        print(f"{camera} N={N} G={G} K={K} S={S} {k}: {rel_err(got, want):.2e}")
+        assert float(want.abs().max()) > 0 or (k == "times" and S == 1), k  # (S = 1 renders at the integer frame time 3.0, where the oracle's own d / d time is 0)
+        if k in ("viewmat", "RTs"):  # per column, as the device test's check_columns: rotation and translation columns each on their own
+            got, want = (got[:3], want[:3]) if k == "viewmat" else (got, want)
+            for col in range(4):
+                _close(f"{k}[..., {col}]", got[..., col], want[..., col], 0.0)
+        else:
+            _close(k, got, want, 0.0 if k in shared else FLIPS)
+
+
+# the static seam's cases of tests/test_gpu_camera_general.py: (camera, mode, D, seed) at N = 1200, 88 x 56 (`rolled`: 56 x 88)
+GPU_STATIC_CASES = [(cam, mode, D, seed) for cam in ("rotated", "anisotropic", "offcentre", "general", "rolled")
+                    for mode, D, seed in (("RGB+ED", 3, 2203), ("RGB", 16, 2204))]
+GPU_STATIC_SHAPE = (1200, 88, 56)
+
+
+@pytest.mark.parametrize("camera,mode,D,seed", GPU_STATIC_CASES)
+def test_cpu_twin_static_seam_under_every_camera(camera, mode, D, seed):
+    """The seeds of the device test's static cases, by the same rule: the viewmat gradient (no allowance, per column) of the fp32 twin
+    within 1e-4 of the fp64 oracle's."""
+    from deblur4dgs_amd.cpu_twin import render_exposure_cpu
+    from tests import camera_cases
+
+    N, W, H = GPU_STATIC_SHAPE
+    c = camera_cases.static_case(camera, mode, D, N, W, H, seed)
+    W, H = c["W"], c["H"]
+    P = {k: c["inp"][k].float().requires_grad_() for k in ("means", "quats", "scales", "opac", "colors", "V")}
+    res = render_exposure_cpu(P["means"], P["quats"], P["scales"], P["opac"], P["colors"], 0, None, None, None, None, None, P["V"],
+                              c["inp"]["K"].float(), W, H, background=c["bg"].float(), return_depth=mode == "RGB+ED", blend=False,
+                              raw_params=False)
+    _close("renders", res["renders"][0], c["ref_c"])
+    _close("alphas", res["alphas"][0], c["ref_a"])
+    ((res["renders"][0] * c["w_c"].float()).sum() + (res["alphas"][0] * c["w_a"].float()).sum()).backward()
+    for k in ("means", "quats", "scales", "opac", "colors"):
+        _close(k, P[k].grad, c["grads"][k])
+    got, want = P["V"].grad[:3].double(), c["grads"]["V"][:3]
+    for col in range(4):
+        print(f"{camera} {mode} D={D} viewmat[:, {col}]: {rel_err(got[:, col], want[:, col]):.2e}")
+        _close(f"viewmat[:, {col}]", got[:, col], want[:, col], 0.0)
+
+
 def test_cfg1_on_the_cpu_twin_in_full():
     """BASELINE.json configs[0] on its exact workload (seed 1000, identity camera delta) - the CPU-runnable case."""
     from deblur4dgs_amd.cpu_twin import render_exposure_cpu

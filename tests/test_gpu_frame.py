@@ -65,9 +65,14 @@ def test_one_call_path_equals_the_staged_chain_bitwise(N, G, K_, S, W, H, D, sub
     map) instead of launching k_blend_bwd, which the staged chain always does: the two must still agree bit for bit.
     On the static scene the S sub-sample renders are equal, and the staged chain's gradient on them shows where each max / min pixel
     sent its gradient: all of it to sub-sample 0 (first in stack order), or spread over all S (the mean won by a rounding) - nothing else."""
-    dev = torch.device("cuda:0")
     static = G == 0 and S > 1
     sc = make_scene(N, G, max(K_, 1), S, W, H, seed=31, **(dict(cam_jitter=0.0) if static else {}))
+    one_call_equals_the_staged_chain(sc, N, G, S, W, H, D, sub_losses, static)
+
+
+def one_call_equals_the_staged_chain(sc, N, G, S, W, H, D, sub_losses, static=False):
+    """The body of the test above on a given `make_scene` dict (tests/test_gpu_camera_general.py runs it under another camera)."""
+    dev = torch.device("cuda:0")
     K = sc["K"].to(dev)
     g = torch.Generator().manual_seed(7)
     wb, wa = torch.randn(H, W, D + 1, generator=g).to(dev), torch.randn(H, W, generator=g).to(dev)

@@ -24,24 +24,28 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _K(f, W, H):
-    return np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]], np.float64)
+def _K(f, W, H, fy=None, cx=None, cy=None):
+    return np.array([[f, 0, W / 2 if cx is None else cx], [0, f if fy is None else fy, H / 2 if cy is None else cy], [0, 0, 1]], np.float64)
 
 
-def closed_form(mean, s, f, W, H):
-    """SURVEY A.4 steps 2-5 for an isotropic Gaussian (Sigma = s^2 I) seen through the identity view matrix.
+def closed_form(mean, s, f, W, H, fy=None, cx=None, cy=None):
+    """SURVEY A.4 steps 2-5 for an isotropic Gaussian (Sigma = s^2 I) seen through the identity view matrix; K = [[f, 0, cx], [0, fy, cy]]
+    (default: fy = f, the principal point in the image centre).  The clamp of the Jacobian is symmetric about the OPTICAL AXIS - it
+    bounds x / z by 1.3 (W / 2) / fx whatever cx is (gsplat 1.1.1).
     -> dict(mu2 [2], cov2 [2,2] blurred, conic (a, b, c), radius, visible)"""
     x, y, z = (float(v) for v in mean)
-    limx, limy = 1.3 * (0.5 * W / f), 1.3 * (0.5 * H / f)
+    fy = f if fy is None else fy
+    cx, cy = W / 2 if cx is None else cx, H / 2 if cy is None else cy
+    limx, limy = 1.3 * (0.5 * W / f), 1.3 * (0.5 * H / fy)
     tx, ty = z * min(limx, max(-limx, x / z)), z * min(limy, max(-limy, y / z))
-    J = np.array([[f / z, 0, -f * tx / z**2], [0, f / z, -f * ty / z**2]])
+    J = np.array([[f / z, 0, -f * tx / z**2], [0, fy / z, -fy * ty / z**2]])
     cov2 = J @ (s * s * np.eye(3)) @ J.T + EPS2D * np.eye(2)
     det = np.linalg.det(cov2)
     inv = np.linalg.inv(cov2)
     mid = 0.5 * (cov2[0, 0] + cov2[1, 1])
     lam = mid + math.sqrt(max(0.01, mid * mid - det))
     radius = math.ceil(3.0 * math.sqrt(lam))
-    mu2 = np.array([f * x / z + W / 2, f * y / z + H / 2])
+    mu2 = np.array([f * x / z + cx, fy * y / z + cy])
     return dict(mu2=mu2, cov2=cov2, conic=(inv[0, 0], inv[0, 1], inv[1, 1]), radius=radius)
 
 
@@ -56,7 +60,7 @@ def alpha_image(cf, o, W, H):
     return al, sig, dx, dy
 
 
-def render(means, scales, opac, colors, f, W, H, bg=None, mode="RGB+ED", need_grad=False, **kw):
+def render(means, scales, opac, colors, f, W, H, bg=None, mode="RGB+ED", need_grad=False, fy=None, cx=None, cy=None, **kw):
     from deblur4dgs_amd.rasterization import rasterization
 
     dev = _dev()
@@ -70,7 +74,7 @@ def render(means, scales, opac, colors, f, W, H, bg=None, mode="RGB+ED", need_gr
         for v in t.values():
             v.requires_grad_()
     V = torch.eye(4, device=dev)
-    Km = torch.tensor(_K(f, W, H), dtype=torch.float32, device=dev)
+    Km = torch.tensor(_K(f, W, H, fy, cx, cy), dtype=torch.float32, device=dev)
     bgs = None if bg is None else torch.tensor(np.asarray(bg), dtype=torch.float32, device=dev)[None]
     rc, ra, info = rasterization(t["means"], t["quats"], t["scales"], t["opac"], t["colors"], V[None], Km[None], W, H,
                                  backgrounds=bgs, render_mode=mode, **kw)
@@ -230,13 +234,23 @@ def test_fov_clamp_of_the_projection_jacobian():
     """x / z beyond 1.3 tan(fov / 2): the Jacobian uses the CLAMPED x (A.4 step 3), the 2-D mean does not.  The conic, the
     radius and the pixels the splat reaches at the image border must follow the clamped closed form - and differ
     measurably from the unclamped one."""
+    _fov_clamp(0.0)
+
+
+def test_fov_clamp_with_an_off_centre_principal_point():
+    """The same with cx = W / 2 + 9: the clamp stays where it was (symmetric about the optical axis), the image moves."""
+    _fov_clamp(9.0)
+
+
+def _fov_clamp(cx_off):
     W, H, f, z, s, o = 64, 48, 64.0, 2.0, 0.5, 0.9
+    cx = W / 2 + cx_off
     lim = 1.3 * 0.5 * W / f
-    mean = np.array([1.5 * (0.5 * W / f) * z, 0.0, z])  # x / z = 0.75 > lim = 0.65; projects to x = 80 (16 px off-screen)
+    mean = np.array([1.5 * (0.5 * W / f) * z, 0.0, z])  # x / z = 0.75 > lim = 0.65; projects to x = 80 + cx_off (16 + cx_off px off-screen)
     assert mean[0] / z > lim
-    cf = closed_form(mean, s, f, W, H)
-    rc, ra, info, _ = render([mean], [s], [o], [[1.0, 1.0, 1.0]], f, W, H, bg=[0, 0, 0], mode="RGB")
-    close(info["means2d"][0, 0], [80.0, 24.0], what="unclamped 2-D mean")
+    cf = closed_form(mean, s, f, W, H, cx=cx)
+    rc, ra, info, _ = render([mean], [s], [o], [[1.0, 1.0, 1.0]], f, W, H, bg=[0, 0, 0], mode="RGB", cx=cx)
+    close(info["means2d"][0, 0], [80.0 + cx_off, 24.0], what="unclamped 2-D mean")
     close(info["conics"].view(-1, 3)[0], cf["conic"], what="conic with the clamped Jacobian")
     assert int(info["radii"][0, 0]) == cf["radius"]
     al = alpha_image(cf, o, W, H)[0]
@@ -245,3 +259,63 @@ def test_fov_clamp_of_the_projection_jacobian():
     J_un = np.array([[f / z, 0, -f * mean[0] / z**2], [0, f / z, 0.0]])
     inv_un = np.linalg.inv(J_un @ (s * s * np.eye(3)) @ J_un.T + EPS2D * np.eye(2))
     assert abs(inv_un[0, 0] - cf["conic"][0]) > 1e-2 * cf["conic"][0]  # the clamp matters in this case
+
+    # the branch switches at exactly x / z = +-lim, on both sides: Gaussians 0.2 % inside and 0.2 % outside the clamp, each rendered
+    # alone; conic by the closed form, dL/dmean against central differences of the closed form (fp64; h far inside the 0.2 %).  Inside,
+    # the Jacobian moves with x (d conic / d x != 0); outside it is frozen - the x gradients of two Gaussians 0.4 % apart differ by far
+    # more than that.
+    g = np.random.default_rng(5)
+    wa = g.standard_normal((H, W))
+    wt = torch.tensor(wa, dtype=torch.float32, device=_dev())
+    gx = {}
+    for side in (1.0, -1.0):
+        for where, ratio in (("inside", 0.998), ("outside", 1.002)):
+            m = np.array([side * ratio * lim * z, 0.1 * z, z])
+            assert (abs(m[0] / z) > lim) == (where == "outside")
+            cf = closed_form(m, s, f, W, H, cx=cx)
+            rc, ra, info, t = render([m], [s], [o], [[1.0, 1.0, 1.0]], f, W, H, bg=[0, 0, 0], mode="RGB", need_grad=True, cx=cx)
+            close(info["conics"].view(-1, 3)[0], cf["conic"], what=f"conic {where} the clamp, side {side:+.0f}")
+            assert int(info["radii"][0, 0]) == cf["radius"] and alpha_image(cf, o, W, H)[0].max() > 0.05
+            (ra * wt).sum().backward()
+            torch.cuda.synchronize()
+
+            def L(mean_):
+                return (wa * alpha_image(closed_form(mean_, s, f, W, H, cx=cx), o, W, H)[0]).sum()
+
+            h = 1e-6
+            gm = [(L(m + h * e) - L(m - h * e)) / (2 * h) for e in np.eye(3)]
+            close(t["means"].grad[0], gm, rtol=1e-4, what=f"dL/dmean {where} the clamp, side {side:+.0f}")
+            gx[(side, where)] = gm[0]
+            # the other branch's conic is measurably different (0.2 % of J02 is ~1e-3 of the conic: 50 x the tolerance)
+            other = closed_form(np.array([side * (2 - ratio) * lim * z, 0.1 * z, z]), s, f, W, H, cx=cx)
+            assert abs(other["conic"][0] - cf["conic"][0]) > 2e-4 * abs(cf["conic"][0])
+    for side in (1.0, -1.0):
+        a, b = gx[(side, "inside")], gx[(side, "outside")]
+        assert abs(a - b) > 0.05 * max(abs(a), abs(b)), (side, a, b)
+
+
+def test_isotropic_gaussian_on_and_off_the_optical_axis_under_a_general_k():
+    """fx != fy, cx != W / 2, cy != H / 2.  On the axis: means2d == (cx, cy) EXACTLY, the conic is diag(1 / ((fx s / z)^2 + 0.3),
+    1 / ((fy s / z)^2 + 0.3)) to 1e-6, radius = ceil(3 sqrt(max(a, c))).  Off the axis: means2d = (fx x / z + cx, fy y / z + cy), conic
+    and radius by the closed form."""
+    W, H, fx, fy, cx, cy, z, s, o = 56, 40, 70.0, 47.5, 33.25, 16.75, 4.0, 0.4, 0.7
+    rc, ra, info, _ = render([[0.0, 0.0, z]], [s], [o], [[0.2, 0.5, 0.9]], fx, W, H, bg=[0, 0, 0], fy=fy, cx=cx, cy=cy)
+    assert info["means2d"][0, 0].tolist() == [cx, cy]
+    a, c = (fx * s / z) ** 2 + EPS2D, (fy * s / z) ** 2 + EPS2D
+    assert (0.5 * (a - c)) ** 2 > 0.01  # (above the floor under the square root of the radius formula: lambda_max = max(a, c))
+    con = info["conics"].view(-1, 3)[0].double().cpu().numpy()
+    assert abs(con[0] - 1 / a) <= 1e-6 / a and abs(con[1]) <= 1e-6 / a and abs(con[2] - 1 / c) <= 1e-6 / c
+    assert int(info["radii"][0, 0]) == math.ceil(3.0 * math.sqrt(max(a, c)))
+    cf = closed_form([0.0, 0.0, z], s, fx, W, H, fy=fy, cx=cx, cy=cy)
+    close(ra, alpha_image(cf, o, W, H)[0], what="alpha image on the axis")
+    assert abs(ra[16, 33].item() - o * math.exp(-0.5 * (0.25**2 / a + 0.25**2 / c))) < 1e-6  # pixel centre (33.5, 16.5): 1/4 px from (cx, cy)
+    # off the axis, inside the clamp (x / z = 0.2 < 0.52, y / z = -0.15 > -0.55)
+    mean = np.array([0.2 * z, -0.15 * z, z])
+    cf = closed_form(mean, s, fx, W, H, fy=fy, cx=cx, cy=cy)
+    rc, ra, info, _ = render([mean], [s], [o], [[0.2, 0.5, 0.9]], fx, W, H, bg=[0, 0, 0], fy=fy, cx=cx, cy=cy)
+    assert abs(cf["mu2"][0] - (fx * 0.2 + cx)) < 1e-12 and abs(cf["mu2"][1] - (-fy * 0.15 + cy)) < 1e-12
+    close(info["means2d"][0, 0], cf["mu2"], rtol=1e-6, what="means2d off the axis")
+    close(info["conics"].view(-1, 3)[0], cf["conic"], what="conic off the axis")
+    assert abs(cf["conic"][1]) > 1e-3 * cf["conic"][0]  # (the off-axis Jacobian couples x and y)
+    assert int(info["radii"][0, 0]) == cf["radius"]
+    close(ra, alpha_image(cf, o, W, H)[0], what="alpha image off the axis")

@@ -133,10 +133,14 @@ def _sh_inputs(N, W, H, K, seed):
                                                  ("RGB", 3, 16, "1NK3", 346), ("RGB+ED", 4, 25, "NK3", 365),
                                                  ("RGB+ED", 3, 25, "NK3", 355)])
 def test_rasterization_sh_matches_oracle(mode, d, K, shape, seed):
+    N, W, H = 1500, 96, 64
+    sh_parity(_sh_inputs(N, W, H, K, seed=seed), mode, d, K, shape, N, W, H)
+
+
+def sh_parity(inp, mode, d, K, shape, N, W, H, tag=""):
+    """The body of the test above on given inputs (tests/test_gpu_camera_general.py runs it under a camera whose K is general too)."""
     from deblur4dgs_amd.rasterization import rasterization
 
-    N, W, H = 1500, 96, 64
-    inp = _sh_inputs(N, W, H, K, seed=seed)
     bg = torch.tensor([0.2, 0.5, 0.8], dtype=torch.float64)
     # reference: the projection's viewmat and the camera centre's are separate leaves, so the test can check that the
     # camera-position term is a sizeable part of the viewmat gradient
@@ -163,7 +167,7 @@ def test_rasterization_sh_matches_oracle(mode, d, K, shape, seed):
     info["means2d"].retain_grad()
     ((rc[0] * w_c.float().to(DEV)).sum() + (ra[0] * w_a.float().to(DEV)).sum()).backward()
     torch.cuda.synchronize()
-    case = f"S1 sh_degree={d} K={K} {shape} {mode} N={N} {W}x{H}"
+    case = f"S1 sh_degree={d} K={K} {shape} {mode} N={N} {W}x{H}{tag}"
     check(case, "render_colors", rc[0].cpu(), ref_c, TOL, FLIPS)
     check(case, "render_alphas", ra[0].cpu(), ref_a, TOL, FLIPS)
     check(case, "means2d.grad", info["means2d"].grad[0].cpu(), ref_info["means2d"].grad, TOL, FLIPS)
