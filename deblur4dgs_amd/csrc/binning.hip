@@ -227,29 +227,27 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
   }
 }
 
-// all-ascending bitonic network on `n` keys (any n): step (k, j) compares i with its partner l > i.
-// Generic form (used on global memory for lists beyond the LDS budget).
-template <typename KeyPtr>
-__device__ __forceinline__ void bitonic_sort(KeyPtr key, int n) {
-  int P = 1;
-  while (P < n) P <<= 1;
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-        const int blk = t / j, off = t - blk * j;
-        const int i = blk * 2 * j + off;
-        const int l = (j == (k >> 1)) ? (blk * 2 * j + (2 * j - 1 - off)) : (i + j);
-        if (l < n) {
-          uint64_t a = key[i], b = key[l];
-          if (a > b) {
-            key[i] = b;
-            key[l] = a;
-          }
-        }
-      }
-      __syncthreads();
+// All-ascending bitonic network on `n` keys (any n), as if padded with UINT64_MAX to a power of two P: step (k, j) compares i with its
+// partner l > i (mirrored in the k-block's first step, i + j after it) and ends in a barrier.  A pair whose upper partner is padding never
+// swaps, so the pairs with l >= n are skipped and the padding is never read (work ~ n, not P).  `key` is LDS (sort_list_lds) or global memory.
+__device__ __forceinline__ void bitonic_step(uint64_t *key, int P, int n, int k, int j) {
+  for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
+    const int blk = t / j, off = t - blk * j;
+    const int i = blk * 2 * j + off;
+    const int l = (j == (k >> 1)) ? (blk * 2 * j + (2 * j - 1 - off)) : (i + j);
+    if (l < n) {
+      const uint64_t x = key[i], y = key[l];
+      if (x > y) key[i] = y, key[l] = x;
     }
   }
+  __syncthreads();
+}
+// the whole network step by step (on global memory, for lists beyond the LDS budget)
+__device__ __forceinline__ void bitonic_sort(uint64_t *key, int n) {
+  int P = 1;
+  while (P < n) P <<= 1;
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) bitonic_step(key, P, n, k, j);
 }
 
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
@@ -354,48 +352,6 @@ __device__ __forceinline__ void chunk_sort(uint64_t (&v)[NV], int lane) {  // th
 }
 constexpr int CNV = 8, CHUNK = 64 * CNV;  // keys per lane / per chunk
 
-// LDS form.  `key[0..P)` holds the list padded with UINT64_MAX to a power of two P >= CHUNK.  Chunks of 512 keys are
-// sorted in registers; only the steps with distance >= 512 go through LDS with a barrier each.
-__device__ __forceinline__ void bitonic_sort_lds(uint64_t *key, int P, int n) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  // keys [n, P) are UINT64_MAX padding: in this all-ascending network a pair whose upper partner is padding never
-  // swaps, so chunks made of padding only and cross-chunk pairs reaching into it are skipped (work ~ n, not P)
-  const int nchunks = (n + CHUNK - 1) / CHUNK;
-  for (int c = wv; c < nchunks; c += nw) {
-    uint64_t v[CNV];
-#pragma unroll
-    for (int u = 0; u < CNV; u++) v[u] = key[c * CHUNK + u * 64 + lane];
-    chunk_sort<CNV>(v, lane);
-#pragma unroll
-    for (int u = 0; u < CNV; u++) key[c * CHUNK + u * 64 + lane] = v[u];
-  }
-  __syncthreads();
-  for (int k = 2 * CHUNK; k <= P; k <<= 1) {
-    for (int j = k >> 1; j >= CHUNK; j >>= 1) {  // cross-chunk steps
-      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-        const int blk = t / j, off = t - blk * j;
-        const int i = blk * 2 * j + off;
-        const int l = (j == (k >> 1)) ? (blk * 2 * j + (2 * j - 1 - off)) : (i + j);
-        if (l < n) {
-          const uint64_t a = key[i], b = key[l];
-          if (a > b) key[i] = b, key[l] = a;
-        }
-      }
-      __syncthreads();
-    }
-    for (int c = wv; c < nchunks; c += nw) {  // distances 256 .. 1
-      uint64_t v[CNV];
-#pragma unroll
-      for (int u = 0; u < CNV; u++) v[u] = key[c * CHUNK + u * 64 + lane];
-      reg_plain<CNV, CNV / 2>(v);
-      chunk_plain<32, CNV>(v, lane);
-#pragma unroll
-      for (int u = 0; u < CNV; u++) key[c * CHUNK + u * 64 + lane] = v[u];
-    }
-    __syncthreads();
-  }
-}
-
 struct SortArgs {
   const int32_t *tile_offsets;
   uint64_t *keys;
@@ -422,6 +378,13 @@ __device__ __forceinline__ bool lazy_range(const SortArgs &a, int t, int &base, 
   return true;
 }
 
+// list position `at` holds the splat of `key`: the output pair of every sort
+__device__ __forceinline__ void put_sorted(const SortArgs &a, int at, uint64_t key) {
+  const uint32_t e = (uint32_t)key;
+  a.sorted_emit[at] = (int32_t)e;
+  a.sorted_gid[at] = a.gid_of_emit[e];
+}
+
 // lists of up to 512 keys: one WAVE per list, straight from global memory into registers and back - no LDS, no barrier
 template <int NV>
 __device__ __forceinline__ void wave_sort_list(const SortArgs &a, int base, int n, int lane) {
@@ -431,25 +394,25 @@ __device__ __forceinline__ void wave_sort_list(const SortArgs &a, int base, int 
   for (int u = 0; u < NV; u++) v[u] = (u * 64 + lane < n) ? gk[u * 64 + lane] : ~0ull;
   chunk_sort<NV>(v, lane);
 #pragma unroll
-  for (int u = 0; u < NV; u++) {
-    const int p = u * 64 + lane;
-    if (p < n) {
-      const uint32_t e = (uint32_t)v[u];
-      a.sorted_emit[base + p] = (int32_t)e;
-      a.sorted_gid[base + p] = a.gid_of_emit[e];
-    }
-  }
+  for (int u = 0; u < NV; u++)
+    if (u * 64 + lane < n) put_sorted(a, base + u * 64 + lane, v[u]);
 }
-// The 2 048-key class of k_tile_sort (lists of 513 ... 2 048 keys, four waves): the chunk width follows the list length, and the list
-// passes through LDS only between the first register sort and the last in-chunk pass.  Each wave sorts chunks of 64 NV keys in registers;
-// it loads them straight from global memory (key c * chunk + u * 64 + lane, UINT64_MAX beyond the list) and writes `sorted_emit` /
+__device__ __forceinline__ void wave_sort_list(const SortArgs &a, int base, int n, int lane) {  // n <= CHUNK
+  if (n <= 64) wave_sort_list<1>(a, base, n, lane);
+  else if (n <= 128) wave_sort_list<2>(a, base, n, lane);
+  else if (n <= 256) wave_sort_list<4>(a, base, n, lane);
+  else wave_sort_list<8>(a, base, n, lane);
+}
+// Lists of 513 ... 16 384 keys, one workgroup of 4 ... 16 waves per list (k_tile_sort's LDS classes; k_tile_sort_w<LONG>): the list passes
+// through LDS only between the first register sort and the last in-chunk pass.  Each wave sorts chunks of 64 NV keys in registers; it
+// loads them straight from global memory (key c * chunk + u * 64 + lane, UINT64_MAX beyond the list) and writes `sorted_emit` /
 // `sorted_gid` from its registers after the last in-chunk pass; only the steps whose partner distance is at least a chunk go through LDS
-// (`key`, one barrier each).  NV = 4 for 513 ... 1 024 keys: three or four chunks of 256 keys keep all four waves busy where 512-key
-// chunks left two of them idle (cfg2: median list 937 keys; k_tile_sort 68 -> 55 us, profiles/ab_sort_chunk_width.txt).  Padding as in
-// bitonic_sort_lds: chunks made of padding only and cross-chunk pairs with l >= n are skipped.  What a cross-chunk step reads is
-// initialised: its pairs have i < l < n, and the chunk stores write every whole chunk below nchunks * chunk, padding included.
-// n > 64 NV (block-uniform, like every branch around a barrier here).  k_tile_sort_w<LONG> and the larger classes keep bitonic_sort_lds
-// until this form is measured on the scenes that run them.
+// (`key`, at least nchunks * chunk keys; one barrier each).  The chunk width follows the list length - NV = 4 for 513 ... 1 024 keys:
+// three or four chunks of 256 keys keep all four waves busy where 512-key chunks left two of them idle (cfg2: median list 937 keys;
+// k_tile_sort 68 -> 55 us, profiles/ab_sort_chunk_width.txt).  Chunks made of padding only are skipped, like the pairs bitonic_step skips.
+// What a cross-chunk step reads is initialised: its pairs have i < l < n, and the chunk stores write every whole chunk below nchunks *
+// chunk, padding included.  n > 64 NV: the output is written in the last k-block only (block-uniform, like every branch around a barrier
+// here).  No barrier at the end: a caller that sorts another list in the same `key` puts one in between (k_tile_sort_w<LONG>).
 template <int NV>
 __device__ __forceinline__ void sort_list_lds(const SortArgs &a, uint64_t *key, int base, int n) {
   constexpr int CH = 64 * NV;
@@ -471,18 +434,7 @@ __device__ __forceinline__ void sort_list_lds(const SortArgs &a, uint64_t *key, 
   }
   __syncthreads();
   for (int k = 2 * CH; k <= P; k <<= 1) {
-    for (int j = k >> 1; j >= CH; j >>= 1) {  // cross-chunk steps
-      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-        const int blk = t / j, off = t - blk * j;
-        const int i = blk * 2 * j + off;
-        const int l = (j == (k >> 1)) ? (blk * 2 * j + (2 * j - 1 - off)) : (i + j);
-        if (l < n) {
-          const uint64_t x = key[i], y = key[l];
-          if (x > y) key[i] = y, key[l] = x;
-        }
-      }
-      __syncthreads();
-    }
+    for (int j = k >> 1; j >= CH; j >>= 1) bitonic_step(key, P, n, k, j);  // cross-chunk steps
     for (int c = wv; c < nchunks; c += nw) {  // distances 32 NV .. 1
       uint64_t v[NV];
 #pragma unroll
@@ -492,13 +444,8 @@ __device__ __forceinline__ void sort_list_lds(const SortArgs &a, uint64_t *key, 
 #pragma unroll
       for (int u = 0; u < NV; u++) {
         const int p = c * CH + u * 64 + lane;
-        if (k < P) {
-          key[p] = v[u];
-        } else if (p < n) {  // the list is sorted
-          const uint32_t e = (uint32_t)v[u];
-          a.sorted_emit[base + p] = (int32_t)e;
-          a.sorted_gid[base + p] = a.gid_of_emit[e];
-        }
+        if (k < P) key[p] = v[u];
+        else if (p < n) put_sorted(a, base + p, v[u]);  // the list is sorted
       }
     }
     if (k < P) __syncthreads();
@@ -524,12 +471,7 @@ __global__ void __launch_bounds__(256) k_tile_sort_w(const SortArgs a) {
     n = a.tile_offsets[t + 1] - base;
     if (a.pass && !lazy_range(a, t, base, n)) n = 0;
   }
-  if (n > 0 && n <= CHUNK) {
-    if (n <= 64) wave_sort_list<1>(a, base, n, lane);
-    else if (n <= 128) wave_sort_list<2>(a, base, n, lane);
-    else if (n <= 256) wave_sort_list<4>(a, base, n, lane);
-    else wave_sort_list<8>(a, base, n, lane);
-  }
+  if (n > 0 && n <= CHUNK) wave_sort_list(a, base, n, lane);
   if constexpr (LONG) {
     __shared__ int lb[4], ln[4];
     if (lane == 0) lb[threadIdx.x >> 6] = base, ln[threadIdx.x >> 6] = (n > CHUNK && n <= 4 * CHUNK) ? n : 0;
@@ -537,19 +479,8 @@ __global__ void __launch_bounds__(256) k_tile_sort_w(const SortArgs a) {
     for (int q = 0; q < 4; q++) {
       const int nq = ln[q];  // (block-uniform)
       if (nq == 0) continue;
-      const uint64_t *gk = a.keys + lb[q];
-      int P = CHUNK;
-      while (P < nq) P <<= 1;
-      const int fill = ((nq + CHUNK - 1) / CHUNK) * CHUNK;
-      for (int p = threadIdx.x; p < fill; p += blockDim.x) wkeys[p] = p < nq ? gk[p] : ~0ull;
-      __syncthreads();
-      bitonic_sort_lds(wkeys, P, nq);
-      for (int p = threadIdx.x; p < nq; p += blockDim.x) {
-        const uint32_t e = (uint32_t)wkeys[p];
-        a.sorted_emit[lb[q] + p] = (int32_t)e;
-        a.sorted_gid[lb[q] + p] = a.gid_of_emit[e];
-      }
-      __syncthreads();
+      sort_list_lds(a, wkeys, lb[q], nq);
+      __syncthreads();  // the next list's chunk stores overwrite what other waves may still be reading in their last in-chunk pass
     }
   }
 }
@@ -563,36 +494,15 @@ __global__ void __launch_bounds__(1024) k_tile_sort(const SortArgs a) {
   if (a.pass && !lazy_range(a, t, base, n)) return;
   if (n <= a.lo || (a.cap >= 0 && n > a.cap)) return;
   if (n <= CHUNK) {  // (only when lo == 0, the first class of a scene that also has longer lists: one launch for both kinds)
-    if (threadIdx.x < 64) {  // one wave sorts the list in registers, exactly as k_tile_sort_w would
-      const int lane = threadIdx.x;
-      if (n <= 64) wave_sort_list<1>(a, base, n, lane);
-      else if (n <= 128) wave_sort_list<2>(a, base, n, lane);
-      else if (n <= 256) wave_sort_list<4>(a, base, n, lane);
-      else wave_sort_list<8>(a, base, n, lane);
-    }
+    if (threadIdx.x < 64) wave_sort_list(a, base, n, threadIdx.x);  // one wave sorts the list in registers, exactly as k_tile_sort_w would
     return;
   }
-  uint64_t *gk = a.keys + base;
-  if (a.cap == 4 * CHUNK) {  // the first LDS class
+  if (a.cap >= 0) {
     sort_list_lds(a, skeys, base, n);
-  } else if (a.cap >= 0) {
-    int P = CHUNK;
-    while (P < n) P <<= 1;
-    for (int p = threadIdx.x; p < P; p += blockDim.x) skeys[p] = p < n ? gk[p] : ~0ull;
-    __syncthreads();
-    bitonic_sort_lds(skeys, P, n);
-    for (int p = threadIdx.x; p < n; p += blockDim.x) {
-      const uint32_t e = (uint32_t)skeys[p];
-      a.sorted_emit[base + p] = (int32_t)e;
-      a.sorted_gid[base + p] = a.gid_of_emit[e];
-    }
   } else {  // list longer than the LDS budget: same network on global memory (rare; correctness path)
+    uint64_t *gk = a.keys + base;
     bitonic_sort(gk, n);
-    for (int p = threadIdx.x; p < n; p += blockDim.x) {
-      const uint32_t e = (uint32_t)gk[p];
-      a.sorted_emit[base + p] = (int32_t)e;
-      a.sorted_gid[base + p] = a.gid_of_emit[e];
-    }
+    for (int p = threadIdx.x; p < n; p += blockDim.x) put_sorted(a, base + p, gk[p]);
   }
 }
 
@@ -622,17 +532,16 @@ int launch_sorts(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect 
   // passes of a lazy sort, cfg5: 609 -> 739 us - four of them queue up inside one workgroup.  Measured (profiles/r06_ab_sort_merge_long.txt):
   // the reference's training shape 56.4 -> 46.8 us, cfg3 97.8 -> 87.7.
   const bool merge_long = !merge_short && !no_long && longest > CHUNK && pass == 0 && isect->n_isect < (int64_t)640 * n_tiles;
+  SortArgs s{proj->tile_offsets, isect->keys, isect->gid_of_emit, isect->sorted_gid, isect->sorted_emit,
+             0, CHUNK, proj->n_isect, isect->n_isect, isect->max_tile_count, n_tiles, lw.near, lw.flag, pass};
   if (!merge_short) {
-    SortArgs s{proj->tile_offsets, isect->keys, isect->gid_of_emit, isect->sorted_gid, isect->sorted_emit,
-               0, CHUNK, proj->n_isect, isect->n_isect, isect->max_tile_count, n_tiles, lw.near, lw.flag, pass};
     if (merge_long) D4GS_LAUNCH("k_tile_sort_w", k_tile_sort_w<true>, dim3((n_tiles + 3) / 4), dim3(256), 4 * CHUNK * 8, stream, s);
     else D4GS_LAUNCH("k_tile_sort_w", k_tile_sort_w<false>, dim3((n_tiles + 3) / 4), dim3(256), 0, stream, s);
   }
   const int classes[6][3] = {{merge_short ? 0 : CHUNK, 2048, 256}, {2048, 4096, 512}, {4096, 8192, 1024}, {8192, 16384, 1024}, {16384, -1, 1024}};
   for (int c = merge_long ? 1 : 0; c < 5; c++) {
     if (longest <= classes[c][0]) break;  // no list is that long
-    SortArgs s{proj->tile_offsets, isect->keys, isect->gid_of_emit, isect->sorted_gid, isect->sorted_emit,
-               classes[c][0], classes[c][1], proj->n_isect, isect->n_isect, isect->max_tile_count, n_tiles, lw.near, lw.flag, pass};
+    s.lo = classes[c][0], s.cap = classes[c][1];
     const size_t lds = classes[c][1] > 0 ? (size_t)classes[c][1] * 8 : 0;
     D4GS_LAUNCH("k_tile_sort", k_tile_sort, dim3(n_tiles), dim3(classes[c][2]), lds, stream, s);
   }
@@ -668,42 +577,32 @@ int fill_emit_args(EmitArgs &e, const D4gsDims *dims, const D4gsProjOut *proj, c
   return D4GS_OK;
 }
 
+template <int PT, int LZ>
+void emit_one(const EmitArgs &e, unsigned eblocks, size_t ebytes, hipStream_t stream) {
+  if (ebytes > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_emit<PT, LZ>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+  D4GS_LAUNCH("k_emit", (k_emit<PT, LZ>), dim3(eblocks), dim3(EMIT_THREADS), ebytes, stream, e);
+}
+template <int PT>
+void emit_pt(const EmitArgs &e, int lz, unsigned eblocks, size_t ebytes, hipStream_t stream) {
+  switch (lz) {
+    case 0: return emit_one<PT, 0>(e, eblocks, ebytes, stream);
+    case 1: return emit_one<PT, 1>(e, eblocks, ebytes, stream);
+    default: return emit_one<PT, 2>(e, eblocks, ebytes, stream);
+  }
+}
 // lz: 0 plain, 1 / 2 the near parts / the flagged tiles' far parts of a D4GS_LAZY_SORT frame (k_emit)
 int launch_emit(const EmitArgs &e, const D4gsDims *dims, int lz, hipStream_t stream) {
   const int pt = d4gs_chunk_per_thread(dims), per_block = EMIT_THREADS * pt;
   const unsigned eblocks = (unsigned)(((dims->N + per_block - 1) / per_block) * dims->S);
   const size_t ebytes = e.use_lds ? sizeof(int) * (size_t)e.tw * e.th * (lz ? 2 : 1) : 0;
-#define D4GS_EMIT(PT_, LZ_)                                                                                               \
-  do {                                                                                                                    \
-    if (ebytes > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_emit<PT_, LZ_>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); \
-    D4GS_LAUNCH("k_emit", (k_emit<PT_, LZ_>), dim3(eblocks), dim3(EMIT_THREADS), ebytes, stream, e);                     \
-  } while (0)
-  if (pt == 1) {
-    if (lz == 0) D4GS_EMIT(1, 0);
-    else if (lz == 1) D4GS_EMIT(1, 1);
-    else D4GS_EMIT(1, 2);
-  } else if (pt == 2) {
-    if (lz == 0) D4GS_EMIT(2, 0);
-    else if (lz == 1) D4GS_EMIT(2, 1);
-    else D4GS_EMIT(2, 2);
-  } else if (pt == 3) {
-    if (lz == 0) D4GS_EMIT(3, 0);
-    else if (lz == 1) D4GS_EMIT(3, 1);
-    else D4GS_EMIT(3, 2);
-  } else if (pt == 5) {
-    if (lz == 0) D4GS_EMIT(5, 0);
-    else if (lz == 1) D4GS_EMIT(5, 1);
-    else D4GS_EMIT(5, 2);
-  } else if (pt == 6) {
-    if (lz == 0) D4GS_EMIT(6, 0);
-    else if (lz == 1) D4GS_EMIT(6, 1);
-    else D4GS_EMIT(6, 2);
-  } else {
-    if (lz == 0) D4GS_EMIT(4, 0);
-    else if (lz == 1) D4GS_EMIT(4, 1);
-    else D4GS_EMIT(4, 2);
+  switch (pt) {
+    case 1: emit_pt<1>(e, lz, eblocks, ebytes, stream); break;
+    case 2: emit_pt<2>(e, lz, eblocks, ebytes, stream); break;
+    case 3: emit_pt<3>(e, lz, eblocks, ebytes, stream); break;
+    case 5: emit_pt<5>(e, lz, eblocks, ebytes, stream); break;
+    case 6: emit_pt<6>(e, lz, eblocks, ebytes, stream); break;
+    default: emit_pt<4>(e, lz, eblocks, ebytes, stream); break;
   }
-#undef D4GS_EMIT
   return d4gs_check_launch("k_emit");
 }
 

@@ -1,8 +1,9 @@
 """Scenes whose per-tile list lengths are chosen exactly (test infrastructure, no GPU needed to build or check them).
 
 The composite, the sort and the depth segmentation change behaviour at fixed list lengths: the forward's batches of 255 / 256 / 127
-splats, the backward's 64-splat batches, the 256-multiple segment unit, the register sorts of 64 .. 512 keys, k_tile_sort_w's 513 ..
-2 048-key LDS form, the LDS classes at 4 096 / 8 192 / 16 384 keys and the global-memory fallback beyond them.  A random scene crosses
+splats, the backward's 64-splat batches, the 256-multiple segment unit, the register sorts of 64 .. 512 keys, the register-chunk LDS
+sort beyond them (k_tile_sort_w's 513 .. 2 048-key lists and the classes at 2 048 / 4 096 / 8 192 / 16 384 keys: 256-key chunks up to
+1 024 keys, 512-key chunks dealt round-robin to 4 / 8 / 16 waves beyond) and the global-memory fallback past 16 384.  A random scene crosses
 some of those edges by chance; a ladder scene puts a list on each edge on purpose.
 
 Construction (identity view matrix): every splat of a tile has its projected centre within 0.5 px of the tile's centre and a screen
@@ -158,6 +159,11 @@ SCENES = {
     # capacity crosses 768 per tile: merge_short
     "between": dict(W=91, H=53, seed=14, ties=((6, 3), (9, 11)),
                     lengths=(5, 63, 127, 254, 510, 2047, 2048, 2049, 4095, 4097, 128, 129)),
+    # 16 tiles, merge_short: the chunk counts inside the larger LDS classes - five | six and seven | eight 512-key chunks on the eight waves
+    # of the 4 096-key class, nine | ten and twelve | thirteen on the sixteen waves of the 8 192-key class, a second chunk per wave
+    # (24 | 25) and a single key of padding (16 383) in the 16 384-key class; each tie group spans a chunk boundary
+    "chunks": dict(W=64, H=64, seed=16, ties=((3, 600), (9, 640)),
+                   lengths=(2560, 2561, 3584, 3585, 4608, 4609, 6144, 6145, 12288, 12289, 16383)),
 }
 # 1300 x 1000: 82 x 63 = 5 166 tiles (more than D4GS_SEG_TILES_MAX_NARROW, not a multiple of 4 or 8): no depth segments at any width
 GRID = dict(W=1300, H=1000, seed=15, ties=((5, 3),), lengths=(1, 2, 3, 4, 5, 513, 64, 65, 256, 257))

@@ -109,7 +109,7 @@ def lists_case(name, merge_long_allowed=True):
 def test_tile_lists_equal_the_oracle_in_every_sort_regime(name):
     seen = lists_case(name)
     designed = {"short": ("merge_long", 0), "mid": ("merge_long", 1), "long": ("merge_short", 5), "between": ("neither", 3),
-                "grid": ("merge_long", 0)}[name]
+                "chunks": ("merge_short", 4), "grid": ("merge_long", 0)}[name]
     assert seen[0] == designed, seen  # the cold render ran the regime and classes the scene was designed for
     if name == "between":
         assert seen[1] == ("merge_short", 3), seen

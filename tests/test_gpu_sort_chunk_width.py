@@ -1,9 +1,9 @@
 """The LDS sort of 513 .. 2 048-key tile lists at every length where a chunk width or a chunk count changes.
 
-k_tile_sort's first class (`sort_list_lds`, csrc/binning.hip) sorts lists of 513 .. 1 024 keys as three or four register chunks of 256
-keys and lists of 1 025 .. 2 048 keys as three or four chunks of 512; a wave loads its chunks from global memory and writes the sorted
-list out of its registers.  k_tile_sort_w<LONG> sorts the same lengths in 512-key chunks through LDS, up to four lists one after the other
-in one workgroup.  The edges are therefore 512 | 513 (one wave, no LDS | LDS), 768 | 769 (three | four 256-key chunks), 1 024 | 1 025
+`sort_list_lds` (csrc/binning.hip) sorts lists of 513 .. 1 024 keys as three or four register chunks of 256 keys and lists of 1 025 ..
+2 048 keys as three or four chunks of 512; a wave loads its chunks from global memory and writes the sorted list out of its registers.
+k_tile_sort's first class calls it for one list per workgroup, k_tile_sort_w<LONG> for up to four lists one after the other in one
+workgroup, through the same 16 KB of LDS at either chunk width.  The edges are therefore 512 | 513 (one wave, no LDS | LDS), 768 | 769 (three | four 256-key chunks), 1 024 | 1 025
 (256-key | 512-key chunks; two | three of them), 1 536 | 1 537 (three | four) and 2 048 (the last full chunk, no padding), plus the
 lengths one short of a full chunk (767, 1 023, 1 535, 2 047).  The ladder scenes of tests/test_gpu_list_edges.py hit only some of them.
 A scene in the merge_short regime takes the k_tile_sort path, one in merge_long the k_tile_sort_w<LONG> path, where every workgroup

@@ -41,6 +41,13 @@ def test_ladder_lists_come_out_as_designed(name):
         assert (rel >= 0).all() and ((rel == 0) | (rel > 4e-5)).all()
     if ladder.SCENES.get(name, {}).get("regime") == "translucent":
         assert al.max() < 1.0 - 2e-4  # no pixel's transmittance near the 1e-4 stop
+    if name == "chunks":  # one tie group in a list of the 4 096-key class, one in the 16 384-key class, each across a 512-key chunk boundary
+        assert sorted(sc["counts"][sc["counts"] > 0].tolist()) == [2560, 2561, 3584, 3585, 4608, 4609, 6144, 6145, 12288, 12289, 16383]
+        assert ladder.sort_launches(N, sc["counts"].size, 16383) == ("merge_short", 0, 4)
+        for g, (lo, hi) in zip(sc["ties"], ((2048, 4096), (8192, 16384))):
+            t = sc["tile_of"][g[0]]
+            p = pos[g] - offs[t]
+            assert lo < sc["counts"][t] <= hi and len(g) >= 600 and p[0] // 512 != p[-1] // 512
     if name == "long":  # mixed regime: the long lists stop early, at steps that differ inside a 2x2 quad of one tile
         last = ctx["last"]
         t = int(np.argmax(sc["counts"]))
