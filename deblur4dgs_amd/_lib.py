@@ -122,6 +122,7 @@ EXPORTS = (
     "d4gs_gradient_loss_fwd", "d4gs_gradient_loss_bwd", "d4gs_track_losses_fwd", "d4gs_track_losses_bwd",
     "d4gs_correlation_fwd", "d4gs_correlation_bwd", "d4gs_backwarp_fwd", "d4gs_backwarp_bwd",
     "d4gs_aligned_l1_blocks", "d4gs_aligned_l1_fwd", "d4gs_aligned_l1_bwd",
+    "d4gs_motion_regs_workspace_bytes", "d4gs_motion_regs_fwd", "d4gs_motion_regs_bwd",
 )
 
 # Appended to ABI 305 after A/B libraries of older trees were built.  The product library must have them (as every export; build()
@@ -227,6 +228,10 @@ def lib() -> C.CDLL:
         L.d4gs_aligned_l1_blocks.restype = C.c_int64
         L.d4gs_aligned_l1_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
         L.d4gs_aligned_l1_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+        L.d4gs_motion_regs_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        L.d4gs_motion_regs_workspace_bytes.restype = C.c_size_t
+        L.d4gs_motion_regs_fwd.argtypes = [vp] * 7 + [i32] * 4 + [C.c_float, C.c_float, vp, C.c_size_t, vp, vp]
+        L.d4gs_motion_regs_bwd.argtypes = [vp] * 5 + [i32] * 4 + [C.c_float, C.c_float, vp, C.c_size_t, vp, P(LeafGrads), vp]
         if L.d4gs_version() != VERSION:
             raise RuntimeError(f"libd4gs.so version {L.d4gs_version()} != {VERSION} (stale build?)")
         _lib = L

@@ -852,7 +852,7 @@ struct BwdPlan {
   const void *fn;
 };
 template <int MODE>
-static BwdPlan plan_bwd(const D4gsDims *dims) {
+static BwdPlan plan_bwd(const D4gsDims *dims, bool ask_device = true) {
   BwdPlan p;
   const int K = dims->G > 0 ? dims->K : 0;
   const int KP = K | 1;
@@ -874,7 +874,7 @@ static BwdPlan plan_bwd(const D4gsDims *dims) {
     // static one; the reference's 40 k + 100 k training shape: 2.8 groups per block) is balanced better by the hardware's
     // own block scheduler - measured 113 us one group per block against 146 us persistent (cfg5, 20 groups per block:
     // 1149 against 1012 us).
-    const int res = resident_blocks(p.fn, lds_of(true));
+    const int res = ask_device ? resident_blocks(p.fn, lds_of(true)) : 0;
     const bool uniform = dims->G == 0 || dims->G == dims->N;
     if (res > 0 && p.blocks >= (uniform ? 2 : 8) * res) p.blocks = res, p.persist = 1, p.lds = lds_of(true);
     // sub-group mapping (S < 3): the shared-gradient sums always go through LDS, so that a block leaves ONE partial vector (the
@@ -890,6 +890,14 @@ extern "C" size_t d4gs_bwd_partials_elems(const D4gsDims *d) {
   const int b0 = plan_bwd<MODE_RENDER>(d).nparts, b1 = plan_bwd<MODE_POSES>(d).nparts;
   const size_t extra = (size_t)d->S * (d->G > 0 ? d->K : 0) * 16;  // room for the blended-bases table of a caller without one
   return ((size_t)(b0 > b1 ? b0 : b1) + RCH + 1) * (size_t)n_shared_of(d) + extra;
+}
+
+// The pose adjoint's `partials` size as pure host arithmetic: the plan of a host without a device - one group per block, the most
+// partial vectors any device's plan leaves (a resident grid is taken only when it is at most half as many blocks) - so a buffer of this
+// size serves whatever device the launch meets.
+size_t d4gs_poses_bwd_partials_bound(const D4gsDims *d) {
+  const size_t extra = (size_t)d->S * (d->G > 0 ? d->K : 0) * 16;
+  return ((size_t)plan_bwd<MODE_POSES>(d, false).nparts + RCH + 1) * (size_t)n_shared_of(d) + extra;
 }
 
 template <int MODE>

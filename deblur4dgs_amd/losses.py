@@ -15,12 +15,17 @@ statistics come from a radix select and nothing is read on the host, so the loss
 `track_losses` is the 2-D track loss and the mapped (track) depth loss of `Trainer.compute_dynamic_losses`
 (flow3d/trainer.py:633-667,681-689) on the same machinery: one value pass gathers the rendered track points at the query pixels
 and projects them, the selection runs for the 2-D term only, one kernel scatters the gradient back.
+
+`motion_regularizers` is what is left of that function beyond the render (flow3d/trainer.py:691-728): the smoothness of the motion
+bases, the smoothness of every foreground track, the acceleration along the viewing ray and the variance of the raw scales, in one
+call forward and one backward on the pose kernels (`csrc/motion_regs.hip`).
 """
 from __future__ import annotations
 
 import ctypes as C
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
@@ -309,3 +314,85 @@ def track_losses(tracks_3d, query_tracks_2d, target_Ks, target_tracks_2d, target
     vis = torch.cat([v.detach().reshape(-1) != 0 for v in visibles]).to(torch.uint8).contiguous()
     return _TrackLossesFn.apply(tracks_3d, pix, rows, vis, w.contiguous(), _f32(torch.cat([t.reshape(-1, 2) for t in tgt2d])),
                                 _f32(torch.cat([d.reshape(-1) for d in depths])), _f32(torch.cat(Ks).reshape(-1, 9)), q)
+
+
+class _MotionRegsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, motion_coefs, rots, transls, scales, ts, w2cs, weight_rot, weight_transl):
+        G, K, T, B = means.shape[0], rots.shape[0], rots.shape[1], ts.shape[0]
+        leaves = tuple(_f32(x) for x in (means, motion_coefs, scales, rots, transls))
+        t, w = _f32(ts), _f32(w2cs)
+        lib = L.lib()
+        nbytes = lib.d4gs_motion_regs_workspace_bytes(G, K, T, B)
+        if nbytes == 0:
+            raise RuntimeError(f"motion_regularizers: unsupported size G={G} K={K} T={T} B={B} (K <= 32, 9 B G <= 2^31 - 1)")
+        ws = torch.empty(nbytes, device=means.device, dtype=torch.uint8)
+        out = torch.empty(4, device=means.device, dtype=torch.float32)
+        stream = C.c_void_p(L.raw_stream(means.device.index))
+        L.check(lib.d4gs_motion_regs_fwd(*[_p(x) for x in leaves], _p(t), _p(w), G, K, T, B, weight_rot, weight_transl, _p(ws), nbytes,
+                                         _p(out), stream), "d4gs_motion_regs_fwd")
+        ctx.save_for_backward(*leaves, ws)  # version-checked: a leaf changed in place before the backward raises
+        ctx.args = (G, K, T, B, weight_rot, weight_transl, nbytes, tuple(x.dtype for x in (means, motion_coefs, rots, transls, scales)))
+        return out[0].clone(), out[1].clone(), out[2].clone(), out[3].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v_sb, v_st, v_za, v_sv):
+        means, coefs, scales, rots, transls, ws = ctx.saved_tensors
+        G, K, T, B, weight_rot, weight_transl, nbytes, dtypes = ctx.args
+        v = torch.stack([x.detach().float().reshape(()) for x in (v_sb, v_st, v_za, v_sv)])
+        g = dict(v_means=torch.empty_like(means), v_motion_coefs=torch.empty_like(coefs), v_scales=torch.empty_like(scales),
+                 v_rots=torch.empty_like(rots), v_transls=torch.empty_like(transls))
+        stream = C.c_void_p(L.raw_stream(means.device.index))
+        L.check(L.lib().d4gs_motion_regs_bwd(_p(means), _p(coefs), _p(scales), _p(rots), _p(transls), G, K, T, B, weight_rot, weight_transl,
+                                             _p(ws), nbytes, _p(v), C.byref(L.fill(L.LeafGrads(), **g)), stream), "d4gs_motion_regs_bwd")
+        outs = (g["v_means"], g["v_motion_coefs"], g["v_rots"], g["v_transls"], g["v_scales"])
+        return tuple(o.to(dt) if need else None for o, dt, need in zip(outs, dtypes, ctx.needs_input_grad[:5])) + (None,) * 4
+
+
+def motion_regularizers(means, motion_coefs, rots, transls, scales, ts, w2cs, *, weight_rot: float = 1.0, weight_transl: float = 2.0):
+    """-> (smooth_bases, smooth_tracks, z_accel, scale_var), four 0-dim tensors: the regularizers of flow3d/trainer.py:691-728.
+
+    means [G,3], raw motion_coefs [G,K] and raw scales [G,3] of the foreground, rots [K,T,6], transls [K,T,3], ts [B] frame indices
+    (any real dtype), w2cs [B,4,4].  With tc = clamp(ts, 1, T-2) and m0, m1, m2 [G,B,3] the deformed means at tc-1, tc, tc+1:
+      smooth_bases  = compute_se3_smoothness_loss(rots, transls, weight_rot, weight_transl)     (loss_utils.py:138-157)
+      smooth_tracks = 0.5 * |2 m1 - m0 - m2|.mean()                                             (trainer.py:699-717)
+      z_accel       = compute_z_acc_loss(stack(m0, m1, m2), w2cs)                               (loss_utils.py:118-135)
+      scale_var     = torch.var(scales, dim=-1).mean()                                          (trainer.py:721-724)
+    unweighted: the caller applies w_smooth_bases 0.1, w_smooth_tracks 2, w_z_accel 1, w_scale_var 0.01.  Gradients flow to means,
+    motion_coefs, rots, transls and scales (those that require one), none to ts or w2cs, which are data in the reference too.  The
+    gradient of a norm that is exactly zero is zero, as torch's.  Nothing is read on the host (the neighbour times and the camera
+    centres - a cofactor inverse instead of torch.linalg.inv, whose error check waits for the device - are formed on the device), so
+    the call can sit inside a captured HIP graph; forward and backward are bitwise reproducible.  T < 3 has no interior frame (the
+    reference's mean over nothing is NaN) and is refused."""
+    # (name, tensor, number of leading free axes, fixed trailing axes)
+    for name, x, lead, tail in (("means", means, 1, (3,)), ("motion_coefs", motion_coefs, 2, ()), ("rots", rots, 2, (6,)),
+                                ("transls", transls, 2, (3,)), ("scales", scales, 1, (3,)), ("ts", ts, 1, ()), ("w2cs", w2cs, 1, (4, 4))):
+        if not torch.is_tensor(x) or x.dim() != lead + len(tail) or tuple(x.shape[lead:]) != tail:
+            raise ValueError(f"{name} {tuple(x.shape) if torch.is_tensor(x) else type(x)}: expected "
+                             "means [G,3], motion_coefs [G,K], rots [K,T,6], transls [K,T,3], scales [G,3], ts [B], w2cs [B,4,4]")
+    G, K, T, B = means.shape[0], rots.shape[0], rots.shape[1], ts.shape[0]
+    if G == 0:
+        raise ValueError("no foreground Gaussians (G == 0)")
+    if motion_coefs.shape != (G, K) or scales.shape[0] != G or transls.shape[:2] != (K, T):
+        raise ValueError(f"mismatched sizes: means {tuple(means.shape)}, motion_coefs {tuple(motion_coefs.shape)}, scales {tuple(scales.shape)}, "
+                         f"rots {tuple(rots.shape)}, transls {tuple(transls.shape)} (G Gaussians, K bases, T frames)")
+    if K == 0:
+        raise ValueError("no motion bases (K == 0)")
+    if T < 3:
+        raise ValueError(f"T = {T} frames: the regularizers need an interior frame (T >= 3)")
+    if B == 0 or w2cs.shape[0] != B:
+        raise ValueError(f"{B} times and {w2cs.shape[0]} cameras: one w2c per entry of ts, at least one")
+    for x in (means, motion_coefs, rots, transls, scales, ts, w2cs):
+        if not x.is_cuda:
+            raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+    return _MotionRegsFn.apply(means, motion_coefs, rots, transls, scales, ts, w2cs, float(weight_rot), float(weight_transl))
+
+
+def scene_motion_regularizers(model, ts, w2cs, **kw):
+    """`motion_regularizers` on a SceneModel's own leaves: fg.params["means" | "motion_coefs" | "scales"] and
+    motion_bases.params["rots" | "transls"].  The trainer's block becomes
+        sb, st, za, sv = scene_motion_regularizers(self.model, ts, w2cs)
+        loss += w_smooth_bases * sb + w_smooth_tracks * st + w_z_accel * za + w_scale_var * sv"""
+    fg, mb = model.fg.params, model.motion_bases.params
+    return motion_regularizers(fg["means"], fg["motion_coefs"], mb["rots"], mb["transls"], fg["scales"], ts, w2cs, **kw)

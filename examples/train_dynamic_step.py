@@ -14,12 +14,17 @@ With --track-losses the 2-D track loss and the mapped-depth loss (trainer.py:633
 DESIGN.md section 17) on synthetic query tracks replace the stand-in that otherwise gives the twelve track channels a gradient;
 `--track-losses torch` evaluates the same two terms the way the reference writes them, in eager torch (a timing comparator: it
 waits for the device and cannot be captured).
+With --motion-regs the step also carries the four regularizers of the trainer that look at no image (trainer.py:691-728: smooth
+motion bases, smooth foreground tracks, small acceleration along the viewing ray, the variance of the raw scales;
+deblur4dgs_amd.losses.scene_motion_regularizers); `--motion-regs torch` evaluates them the way the reference
+writes them, in eager torch on the pose API (a timing comparator: torch.linalg.inv waits for the device, so it cannot be captured).
 It exists to show the seam in a real autograd + optimizer loop:
 
     python examples/train_dynamic_step.py --steps 20
     python examples/train_dynamic_step.py --graph --hip-adam --depth-losses
     python examples/train_dynamic_step.py --graph --hip-adam --consistency-loss
     python examples/train_dynamic_step.py --graph --hip-adam --track-losses
+    python examples/train_dynamic_step.py --graph --hip-adam --motion-regs
 """
 from __future__ import annotations
 
@@ -34,7 +39,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from deblur4dgs_amd import engine  # noqa: E402
 from deblur4dgs_amd.control import ControlCfg, accumulate_from_model, cull_step, densify_step, spatial_order_step  # noqa: E402
-from deblur4dgs_amd.losses import compute_gradient_loss, masked_l1_loss, photometric_loss, track_losses as hip_track_losses  # noqa: E402
+from deblur4dgs_amd.losses import (compute_gradient_loss, masked_l1_loss, photometric_loss, scene_motion_regularizers,  # noqa: E402
+                                   track_losses as hip_track_losses)
 from deblur4dgs_amd.pwcnet import PWCNet, exposure_consistency_loss  # noqa: E402
 from deblur4dgs_amd.scene_model import GaussianParams, MotionBases, SceneModel  # noqa: E402
 from deblur4dgs_amd.synth import make_scene  # noqa: E402
@@ -94,9 +100,26 @@ def torch_track_losses(tracks_3d, query, target_Ks, target_2d, visibles, weights
     return normalised(v2d, v2d < torch.quantile(v2d, quantile)), normalised(vdepth, torch.ones_like(vis[vis]))
 
 
+def torch_motion_regularizers(model, ts, w2cs):
+    """The four regularizers in eager torch on the pose API, the reference's way (trainer.py:691-728): the (G, 3n, 3, 4) transforms of
+    the three neighbour times, a pad and an einsum for the means, norms, torch.linalg.inv for the camera centres (its error check
+    waits for the device) and torch.var.  A timing comparator for scene_motion_regularizers; it cannot be captured."""
+    bases, fg = model.motion_bases.params, model.fg.params
+    accel = lambda x: torch.linalg.vector_norm(x[:, 1:-1] * 2 - (x[:, :-2] + x[:, 2:]), dim=-1).mean()
+    smooth_bases = accel(bases["rots"]) + 2.0 * accel(bases["transls"])
+    tc = ts.clamp(1, model.num_frames - 2)
+    tfs = model.compute_transforms(torch.cat((tc - 1, tc, tc + 1)))
+    nbs = torch.einsum("gnij,gj->gni", tfs, torch.nn.functional.pad(fg["means"], (0, 1), value=1.0)).reshape(tfs.shape[0], 3, -1, 3)
+    before, at, after = nbs.unbind(1)
+    smooth_tracks = torch.linalg.vector_norm(at * 2 - (before + after), dim=-1).mean() / 2
+    ray = torch.nn.functional.normalize(at - torch.linalg.inv(w2cs)[:, :3, 3], dim=-1)
+    z_accel = ((at - before) * ray).sum(-1).square().mean() + ((after - at) * ray).sum(-1).square().mean()
+    return smooth_bases, smooth_tracks, z_accel, torch.var(fg["scales"], dim=-1).mean()
+
+
 def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, fused_stats=True, deferred=True,
           graph=False, hip_adam=False, seed=0, step_events=None, depth_losses=False, consistency_loss=False, track_losses=False,
-          n_tracks=4096, **kw):
+          n_tracks=4096, motion_regs=False, **kw):
     """fused_stats: the densification statistics come out of the rasterizer's backward (attach_control_stats) instead
     of a pass over `_current_xys[i].grad`; deferred: no render waits for its intersection count on the host
     (`deferred_size_check`), the counts are verified once per step; graph: the three renders, the loss and the whole
@@ -111,9 +134,13 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
     (one batched PWC-Net pass of 2 (S - 1) pairs under no_grad, one loss kernel; no host wait either); track_losses: the 2-D track
     loss and the mapped-depth loss on `n_tracks` synthetic query tracks (make_tracks) with the reference's weights (configs.py:
     w_track 2 after its division by max(H, W), w_depth_const 0.1) in place of the stand-in on the track channels - True: the HIP
-    path, which captures; "torch": the reference's formulation in eager torch, which waits for the device and does not."""
+    path, which captures; "torch": the reference's formulation in eager torch, which waits for the device and does not;
+    motion_regs: add the reference's smooth-bases, smooth-tracks, z-acceleration and scale-variance regularizers with its weights
+    (configs.py: 0.1, 2, 1, 0.01) for the step's frame and camera - True: one HIP call each way, which captures; "torch": the
+    reference's wording in eager torch (torch_motion_regularizers), which does not."""
     assert not graph or (fused_stats and deferred), "graph capture needs the sync-free step"
     assert track_losses in (False, True, "torch") and not (graph and track_losses == "torch"), "the torch form cannot be captured"
+    assert motion_regs in (False, True, "torch") and not (graph and motion_regs == "torch"), "the torch form cannot be captured"
     model, sc = build(W=W, H=H, dev=dev, seed=seed, **kw)
     model.deferred_size_check = bool(deferred)
     w2c, K = sc["viewmat"][None].to(dev), sc["K"][None].to(dev)
@@ -161,6 +188,7 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
              "max_radii": torch.zeros(N, device=dev)}
     target_ts = torch.tensor([1.0, 2.0, 4.0, 5.0], device=dev)
     target_w2cs = w2c.expand(4, 4, 4).contiguous()
+    reg_ts = torch.tensor([3.0], device=dev)  # the frame every render of the step looks at
     losses = []
     warm = min(5, steps // 2)  # lazy initialisation (Adam state, code objects) stays out of the timing
     def fwd_bwd():
@@ -187,6 +215,9 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
                 1.0 * masked_l1_loss(out2["mask"], tgt_mask, quantile=0.98)
         if consistency_loss:
             loss = loss + 2.0 * exposure_consistency_loss(out2["exposure_imgs"], alignnet)
+        if motion_regs:
+            sb, st, za, sv = (torch_motion_regularizers if motion_regs == "torch" else scene_motion_regularizers)(model, reg_ts, w2c)
+            loss = loss + 0.1 * sb + 2.0 * st + 1.0 * za + 0.01 * sv
         loss.backward()
         return loss.detach(), side
 
@@ -290,7 +321,11 @@ if __name__ == "__main__":
                     help="the reference's 2-D track and mapped-depth losses on synthetic query tracks: HIP and graph-capturable, or "
                          "`torch`: the reference's eager formulation (full-image projection, boolean selection, torch.quantile)")
     ap.add_argument("--tracks", type=int, default=4096, help="query tracks of --track-losses")
+    ap.add_argument("--motion-regs", nargs="?", const="hip", default=None, choices=("hip", "torch"),
+                    help="the reference's smooth-bases, smooth-tracks, z-acceleration and scale-variance regularizers: HIP and "
+                         "graph-capturable, or `torch`: the reference's eager formulation on the pose API (torch.linalg.inv)")
     a = ap.parse_args()
     train(a.steps, control_every=a.control_every, fused_stats=not a.round1, deferred=not a.round1, graph=a.graph, hip_adam=a.hip_adam,
           depth_losses=a.depth_losses, consistency_loss=a.consistency_loss,
-          track_losses={None: False, "hip": True, "torch": "torch"}[a.track_losses], n_tracks=a.tracks)
+          track_losses={None: False, "hip": True, "torch": "torch"}[a.track_losses], n_tracks=a.tracks,
+          motion_regs={None: False, "hip": True, "torch": "torch"}[a.motion_regs])

@@ -640,6 +640,39 @@ D4GS_API int d4gs_track_losses_bwd(const float *tracks_3d, const int32_t *pix, c
                                    const float *values, const float *out, const float *v_losses, int64_t n_pixels, int32_t N,
                                    int32_t n_rows, int64_t n_elements, float quantile, float *v_tracks_3d, void *stream);
 
+/* Motion and scale regularizers (appended; D4GS_VERSION unchanged): the four terms of Trainer.compute_dynamic_losses that look at no
+ * image (flow3d/trainer.py:691-728, flow3d/loss_utils.py:118-157), one call forward and one backward.  Inputs, fp32 contiguous:
+ * the foreground means [G,3], raw motion_coefs [G,K] (softmax is applied), raw scales [G,3] (penalised before exp, as the reference
+ * does), rots [K,T,6], transls [K,T,3], ts [B] (frame units, any float), w2cs [B,4,4] = [A t; 0 0 0 1] with A any invertible 3x3.
+ * With tc_b = clamp(ts_b, 1, T-2) and m_j[g,b] (j = 0, 1, 2) the deformed mean of Gaussian g at tc_b + (j - 1) (the deformation of
+ * d4gs_poses_fwd), c_b = -A_b^-1 t_b the camera centre and d = (m_1 - c_b) / max(|m_1 - c_b|, 1e-12), out [4] (device) receives
+ *   out[0] smooth_bases  = weight_rot * mean_{k, 1 <= tau <= T-2} |2 rots[k,tau] - rots[k,tau-1] - rots[k,tau+1]| + weight_transl * (the
+ *                          same on transls)                                                   (the reference's weights: 1, 2)
+ *   out[1] smooth_tracks = 0.5 * mean_{g,b} |2 m_1 - m_0 - m_2|
+ *   out[2] z_accel       = mean_{g,b} ((m_1 - m_0) . d)^2 + mean_{g,b} ((m_2 - m_1) . d)^2
+ *   out[3] scale_var     = mean_g sum_i (s_gi - mean_i s_gi)^2 / 2
+ * The neighbour times and the camera centres are formed on the device: nothing is read on the host.  workspace:
+ * d4gs_motion_regs_workspace_bytes(G, K, T, B) bytes (0: bad sizes), 16-byte aligned; the forward leaves the neighbour times, the
+ * centres and the neighbour means [3B,G,3] in it, and the backward must be given the same, unmodified workspace.
+ * Backward: v_out [4] (device) the four upstream gradients; fills v_means [G,3], v_motion_coefs [G,K], v_scales [G,3], v_rots [K,T,6]
+ * and v_transls [K,T,3] of `grads` (overwritten; all five required, the other fields - .partials too - are ignored).  Nothing flows
+ * to ts or w2cs.  The gradient of a norm that is exactly zero is zero (torch's convention): a static set of bases, or a basis row
+ * that is the exact midpoint of its neighbours, gives 0 and not 0 / 0.  Every sum has a fixed order and every gradient address one
+ * writer: forward and backward are bitwise reproducible.  A NaN in ts is not propagated: the clamp takes it to frame 1 (torch.clamp
+ * would return NaN); non-finite inputs are otherwise out of scope (no out-of-bounds access follows from them).  D4GS_EINVAL, by host
+ * arithmetic alone and before any HIP call, for a NULL pointer, G < 1, K outside 1..32, T < 3 (no interior frame: the reference's
+ * mean over nothing is NaN), B < 1, 9 B G or 9 K T > 2^31 - 1, or an undersized or misaligned workspace.  The workspace size depends
+ * on the four sizes only, not on the device. */
+D4GS_API size_t d4gs_motion_regs_workspace_bytes(int32_t G, int32_t K, int32_t T, int32_t B);
+D4GS_API int d4gs_motion_regs_fwd(const float *means, const float *motion_coefs, const float *scales, const float *rots,
+                                  const float *transls, const float *ts, const float *w2cs, int32_t G, int32_t K, int32_t T, int32_t B,
+                                  float weight_rot, float weight_transl, void *workspace, size_t workspace_bytes, float *out,
+                                  void *stream);
+D4GS_API int d4gs_motion_regs_bwd(const float *means, const float *motion_coefs, const float *scales, const float *rots,
+                                  const float *transls, int32_t G, int32_t K, int32_t T, int32_t B, float weight_rot,
+                                  float weight_transl, void *workspace, size_t workspace_bytes, const float *v_out,
+                                  const D4gsLeafGrads *grads, void *stream);
+
 /* Flow-aligned exposure consistency (appended; D4GS_VERSION unchanged): the pieces of the reference's AlignedLoss (flow3d/loss_utils.py,
  * flow3d/models/pwcnet.py) that are not convolutions.  Every tensor is fp32, contiguous, NCHW.
  *
