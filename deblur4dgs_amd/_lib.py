@@ -123,6 +123,7 @@ EXPORTS = (
     "d4gs_correlation_fwd", "d4gs_correlation_bwd", "d4gs_backwarp_fwd", "d4gs_backwarp_bwd",
     "d4gs_aligned_l1_blocks", "d4gs_aligned_l1_fwd", "d4gs_aligned_l1_bwd",
     "d4gs_motion_regs_workspace_bytes", "d4gs_motion_regs_fwd", "d4gs_motion_regs_bwd",
+    "d4gs_metrics_blocks", "d4gs_masked_metrics",
 )
 
 # Appended to ABI 305 after A/B libraries of older trees were built.  The product library must have them (as every export; build()
@@ -232,6 +233,9 @@ def lib() -> C.CDLL:
         L.d4gs_motion_regs_workspace_bytes.restype = C.c_size_t
         L.d4gs_motion_regs_fwd.argtypes = [vp] * 7 + [i32] * 4 + [C.c_float, C.c_float, vp, C.c_size_t, vp, vp]
         L.d4gs_motion_regs_bwd.argtypes = [vp] * 5 + [i32] * 4 + [C.c_float, C.c_float, vp, C.c_size_t, vp, P(LeafGrads), vp]
+        L.d4gs_metrics_blocks.argtypes = [i32] * 4
+        L.d4gs_metrics_blocks.restype = C.c_int64
+        L.d4gs_masked_metrics.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         if L.d4gs_version() != VERSION:
             raise RuntimeError(f"libd4gs.so version {L.d4gs_version()} != {VERSION} (stale build?)")
         _lib = L

@@ -10,6 +10,12 @@
 #define D4GS_PROJ_BLOCK 256
 
 
+// The 11-tap sigma-1.5 Gaussian of both SSIMs (photometric.hip: pytorch_msssim's; metrics.hip: the dycheck masked one):
+// exp(-k^2 / 4.5) / sum, k = -5..5, in double.  Each translation unit keeps its own __constant__ copy of these eleven numbers.
+#define D4GS_SSIM_WINDOW                                                                                                   \
+  {0.00102838008447911, 0.007598758135239185, 0.03600077212843083, 0.10936068950970002, 0.2130055377112537, 0.26601172486179436, \
+   0.2130055377112537,  0.10936068950970002,  0.03600077212843083, 0.007598758135239185, 0.00102838008447911}
+
 // host-side error plumbing (capi.cpp)
 void d4gs_set_error(const char *fmt, ...);
 int d4gs_check_launch(const char *what);

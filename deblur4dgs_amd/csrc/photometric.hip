@@ -32,10 +32,7 @@ namespace {
 constexpr int PW = 11, PT = 16, PH = PT + PW - 1;  // window, tile, tile + halo (26)
 constexpr int PC = 3;                                      // channels (the reference's SSIM is built for 3)
 constexpr int PM = 5;                                      // map floats per output pixel and channel: a, b, e, E[u] - E[v], E[v]
-// exp(-k^2 / 4.5) / sum, k = -5..5, in double (bitwise the oracle's window)
-__constant__ double c_wind[PW] = {0.00102838008447911, 0.007598758135239185, 0.03600077212843083, 0.10936068950970002,
-                                  0.2130055377112537,  0.26601172486179436,  0.2130055377112537,  0.10936068950970002,
-                                  0.03600077212843083, 0.007598758135239185, 0.00102838008447911};
+__constant__ double c_wind[PW] = D4GS_SSIM_WINDOW;  // (bitwise the oracle's window)
 constexpr double SSIM_C1 = 1e-4, SSIM_C2 = 9e-4;
 
 // the offset of 16x16 tile (ty, tx) of image b: the masked value at its centre pixel (clamped into the image)

@@ -711,6 +711,25 @@ D4GS_API int d4gs_aligned_l1_fwd(const float *pred, const float *flow, const flo
 D4GS_API int d4gs_aligned_l1_bwd(const float *pred, const float *flow, const float *target, const float *mask, const float *v_loss,
                                  int32_t P, int32_t H, int32_t W, float *v_pred, float *v_target, void *stream);
 
+/* Masked image metrics (appended; D4GS_VERSION unchanged): what the reference's mPSNR and mSSIM accumulate (flow3d/metrics.py:99-124,
+ * 142-217), for M masks of B images in one call.  pred, target [B,H,W,3] fp32 channel-last as the rasterizer writes them; masks
+ * [M,B,H,W] fp32, any values (the reference's are binary), or NULL = one mask of ones (M must be 1).  out [M,B,3] doubles (device):
+ *   out[m,b,0] = sum over pixels and channels of ((pred - target) * mask)^2
+ *   out[m,b,1] = sum of the mask
+ *   out[m,b,2] = the mean over the [H-10,W-10,3] map of the dycheck masked SSIM (want_ssim != 0; otherwise 0 and H, W may be < 11):
+ *                the moments p, t, p^2, t^2, p t each pass a count-normalised 11-tap sigma-1.5 filter along x, then along y,
+ *                  cnt = sum_window mask, out = cnt != 0 ? (sum_window f z mask) * 11 / cnt : 0, mask' = (cnt != 0),
+ *                the y pass on the x pass's result under its mask'; variances clipped at 0, the covariance to the geometric mean;
+ *                c1 = 1e-4, c2 = 9e-4.  A position whose windows are empty scores 1, as in the reference.
+ * Every sum is in double and has a fixed order (no atomics): bitwise reproducible, and each (m, b) does not depend on M.  partials:
+ * [d4gs_metrics_blocks(M,B,H,W), 3] doubles of scratch, 8-byte aligned.  Nothing is read on the host.  D4GS_EINVAL, by host
+ * arithmetic alone and before any HIP call, for a NULL pred / target / partials / out, a misaligned pointer, M, B, H or W < 1,
+ * masks == NULL with M != 1, want_ssim with H < 11 or W < 11, or sizes beyond the grid (M * B or ceil(H / 16) > 65535, more than
+ * 2^31 - 1 blocks). */
+D4GS_API int64_t d4gs_metrics_blocks(int32_t M, int32_t B, int32_t H, int32_t W); /* 0: illegal sizes */
+D4GS_API int d4gs_masked_metrics(const float *pred, const float *target, const float *masks, int32_t M, int32_t B, int32_t H,
+                                 int32_t W, int32_t want_ssim, double *partials, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
