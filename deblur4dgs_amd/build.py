@@ -47,7 +47,8 @@ def _stale(src: str, obj: str) -> bool:
     if not os.path.exists(obj):
         return True
     t = os.path.getmtime(obj)
-    deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "d4gs.h")]
+    deps = [os.path.join(CSRC, src), os.path.join(HERE, "..", "include", "d4gs.h")]
+    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]  # every header: any source may include any
     deps += [os.path.join(CSRC, "variants", f) for f in os.listdir(os.path.join(CSRC, "variants"))] if obj.endswith(".var.o") else []
     return any(os.path.getmtime(d) > t for d in deps)
 

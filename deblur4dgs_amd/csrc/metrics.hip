@@ -16,6 +16,7 @@
 // count-normalised filter is not shift-invariant.  The algebra is compiled without fma contraction, so that pred == target gives
 // numerator == denominator bit for bit and an SSIM of exactly 1.  Block partials carry sum (1 - ssim); the mean is 1 - sum / n.
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -157,37 +158,22 @@ __global__ void __launch_bounds__(256) k_metrics(const MetricsArgs a) {
       }
     }
   }
-  // block sums in a fixed order: lanes (shuffle tree), then the 4 waves
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sse += __shfl_xor(sse, o), msum += __shfl_xor(msum, o), osum += __shfl_xor(osum, o);
-  if ((tid & 63) == 0) red[(tid >> 6) * MP] = sse, red[(tid >> 6) * MP + 1] = msum, red[(tid >> 6) * MP + 2] = osum;
+  double v[MP] = {sse, msum, osum};
+  block_sum_store(v, red);
   __syncthreads();
   if (tid < MP) {
     const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    a.partials[blk * MP + tid] = (red[tid] + red[MP + tid]) + (red[2 * MP + tid] + red[3 * MP + tid]);
+    a.partials[blk * MP + tid] = block_sum_combine<MP>(red, tid);
   }
 }
 
 // One block per (m, b): its tiles' partials in a fixed order.  out[mb] = sse, mask sum, 1 - sum(1 - ssim) / n  (0 without SSIM).
 __global__ void __launch_bounds__(256) k_metrics_finish(const double *partials, int tiles, double n_ssim, double *out) {
-  __shared__ double rs[MP][256];
-  const double *p = partials + (size_t)blockIdx.x * tiles * MP;
-  double s[MP] = {0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < tiles; i += 256)
-#pragma unroll
-    for (int j = 0; j < MP; j++) s[j] += p[(size_t)i * MP + j];
-#pragma unroll
-  for (int j = 0; j < MP; j++) rs[j][threadIdx.x] = s[j];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-#pragma unroll
-      for (int j = 0; j < MP; j++) rs[j][threadIdx.x] += rs[j][threadIdx.x + o];
-    __syncthreads();
-  }
+  double t[MP];
+  ordered_total(partials + (size_t)blockIdx.x * tiles * MP, tiles, MP, t);
   if (threadIdx.x == 0) {
     double *o = out + (size_t)blockIdx.x * MP;
-    o[0] = rs[0][0], o[1] = rs[1][0], o[2] = n_ssim > 0.0 ? 1.0 - rs[2][0] / n_ssim : 0.0;
+    o[0] = t[0], o[1] = t[1], o[2] = n_ssim > 0.0 ? 1.0 - t[2] / n_ssim : 0.0;
   }
 }
 

@@ -14,6 +14,7 @@
 // address has one writer.  The same input gives the same bits on every run and every graph replay.
 // The gradient of a norm at exactly zero is zero (torch's convention): tracks of a static basis set and straight basis rows get 0, not 0/0.
 #include "common.h"
+#include "reduce.h"
 
 int d4gs_poses_fwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsPoses *, hipStream_t);
 int d4gs_poses_bwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsPoses *, const D4gsLeafGrads *, hipStream_t);
@@ -21,7 +22,7 @@ size_t d4gs_poses_bwd_partials_bound(const D4gsDims *);  // host arithmetic only
 
 namespace {
 
-constexpr int MB = 256;  // threads per block, all kernels: one lane per Gaussian / basis row
+constexpr int MB = REDUCE_NT;  // threads per block, all kernels: one lane per Gaussian / basis row
 constexpr int PARTIAL_DOUBLES = 3;
 constexpr float NORM_EPS = 1e-12f;  // F.normalize's clamp on the norm
 
@@ -155,25 +156,15 @@ __global__ void __launch_bounds__(MB) k_motion_loss_fwd(const float *__restrict_
 // one block adds the block partials in block order (a fixed tree) and scales them into the four values
 __global__ void __launch_bounds__(MB) k_motion_finish(const double *__restrict__ partials, int gblocks, int bblocks, int G, int K, int T,
                                                       int B, float w_rot, float w_transl, float *__restrict__ out) {
-  __shared__ double r[5][MB];
-  double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // tracks, z, scale | bases rots, transls
-  for (int i = threadIdx.x; i < gblocks; i += MB)
-    for (int k = 0; k < 3; k++) a[k] += partials[(size_t)i * PARTIAL_DOUBLES + k];
-  for (int i = threadIdx.x; i < bblocks; i += MB)
-    for (int k = 0; k < 2; k++) a[3 + k] += partials[(size_t)(gblocks + i) * PARTIAL_DOUBLES + k];
-  for (int k = 0; k < 5; k++) r[k][threadIdx.x] = a[k];
-  __syncthreads();
-  for (int o = MB / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o)
-      for (int k = 0; k < 5; k++) r[k][threadIdx.x] += r[k][threadIdx.x + o];
-    __syncthreads();
-  }
+  double g[3], b[2];  // tracks, z, scale | bases rots, transls
+  ordered_total(partials, gblocks, PARTIAL_DOUBLES, g);
+  ordered_total(partials + (size_t)gblocks * PARTIAL_DOUBLES, bblocks, PARTIAL_DOUBLES, b);
   if (threadIdx.x == 0) {
     const double gb = (double)G * (double)B, rows = (double)K * (double)(T - 2);
-    out[0] = (float)(((double)w_rot * r[3][0] + (double)w_transl * r[4][0]) / rows);
-    out[1] = (float)(0.5 * r[0][0] / gb);
-    out[2] = (float)(r[1][0] / gb);
-    out[3] = (float)(r[2][0] / (double)G);
+    out[0] = (float)(((double)w_rot * b[0] + (double)w_transl * b[1]) / rows);
+    out[1] = (float)(0.5 * g[0] / gb);
+    out[2] = (float)(g[1] / gb);
+    out[3] = (float)(g[2] / (double)G);
   }
 }
 

@@ -26,6 +26,7 @@
 //     the SSIM gradient;
 //   * the block partials are sums of 1 - S (not S), so a loss of 1e-4 keeps its relative precision.
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -65,7 +66,7 @@ __global__ void __launch_bounds__(256) k_photo_fwd(const PhotoArgs a) {
   // stage the 26x26 input patch (masked, centred).  Tiles cover the INPUT grid, so every input pixel's |x - y| is owned
   // by exactly one block (its 16x16 top-left cells); output pixels exist only for oy < H - 10, ox < W - 10.  Cells
   // outside the image are only ever read by windows of output pixels that do not exist.
-  float l1 = 0.f;
+  float l1[1] = {0.f};  // (arrays of one: the block sum takes R values)
   for (int i = tid; i < PH * PH; i += 256) {
     const int ly = i / PH, lx = i - ly * PH;
     const int y = ty0 + ly, x = tx0 + lx;
@@ -78,7 +79,7 @@ __global__ void __launch_bounds__(256) k_photo_fwd(const PhotoArgs a) {
         const float pv = a.pred[p * PC + c], gv = a.gt[p * PC + c];
         u[c] = (float)((double)pv * (double)m - (double)offx[c]);
         v[c] = (float)((double)gv * (double)m - (double)offy[c]);
-        if (ly < PT && lx < PT) l1 += fabsf(pv - gv) * fabsf(m);
+        if (ly < PT && lx < PT) l1[0] += fabsf(pv - gv) * fabsf(m);
       }
     }
 #pragma unroll
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(256) k_photo_fwd(const PhotoArgs a) {
   const int ly = tid / PT, lx = tid % PT;
   const int oy = ty0 + ly, ox = tx0 + lx;
   const bool live = oy < a.Ho && ox < a.Wo;
-  double osum = 0.0;  // sum of 1 - S
+  double osum[1] = {0.0};  // sum of 1 - S
 #pragma unroll
   for (int c = 0; c < PC; c++) {
     __syncthreads();  // staging done (c == 0) / the previous channel's vertical pass done with hbuf
@@ -121,7 +122,7 @@ __global__ void __launch_bounds__(256) k_photo_fwd(const PhotoArgs a) {
       const double L = 1.0 - d * d * iB1;
       const double ocs = (s1 + s2 - 2.0 * s12) * iB2;  // 1 - CS
       const double S = L * (1.0 - ocs);
-      osum += (d * d * iB1 + ocs) - d * d * iB1 * ocs;  // 1 - S
+      osum[0] += (d * d * iB1 + ocs) - d * d * iB1 * ocs;  // 1 - S
       float *mp = a.maps + ((((size_t)b * a.Ho + oy) * a.Wo + ox) * PC + c) * PM;
       mp[0] = (float)(-2.0 * d * (mu2 * (mu1 + mu2) + SSIM_C1) * iB1 * iB1 * (1.0 - ocs));
       mp[1] = (float)(-S * iB2);
@@ -130,15 +131,12 @@ __global__ void __launch_bounds__(256) k_photo_fwd(const PhotoArgs a) {
       mp[4] = (float)ev;
     }
   }
-  // block sums in a fixed order: lanes (shuffle tree), then the 4 waves
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) osum += __shfl_xor(osum, o), l1 += __shfl_xor(l1, o);
-  if ((tid & 63) == 0) red[tid >> 6] = osum, redl[tid >> 6] = l1;
+  block_sum_store(osum, red), block_sum_store(l1, redl);  // both block sums (reduce.h) behind one barrier
   __syncthreads();
   if (tid == 0) {
     const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    a.partials[blk * 2] = (float)((red[0] + red[1]) + (red[2] + red[3]));
-    a.partials[blk * 2 + 1] = (redl[0] + redl[1]) + (redl[2] + redl[3]);
+    a.partials[blk * 2] = (float)block_sum_combine<1>(red, 0);
+    a.partials[blk * 2 + 1] = block_sum_combine<1>(redl, 0);
   }
 }
 
@@ -146,17 +144,10 @@ __global__ void __launch_bounds__(256) k_photo_fwd(const PhotoArgs a) {
 // 1 - ssim, and the loss is formed from it in double, so a small 1 - ssim is not rounded through an ssim near 1.
 __global__ void __launch_bounds__(256) k_photo_finish(const float *partials, int n_blocks, double inv_nssim, double inv_nl1,
                                                       float w_l1, float w_ssim, float *loss) {
-  __shared__ double rs[256], rl[256];
-  double s = 0.0, l = 0.0;
-  for (int i = threadIdx.x; i < n_blocks; i += 256) s += partials[2 * i], l += partials[2 * i + 1];
-  rs[threadIdx.x] = s, rl[threadIdx.x] = l;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) rs[threadIdx.x] += rs[threadIdx.x + o], rl[threadIdx.x] += rl[threadIdx.x + o];
-    __syncthreads();
-  }
+  double t[2];  // sum of 1 - ssim_map, sum of |x - y|
+  ordered_total(partials, n_blocks, 2, t);
   if (threadIdx.x == 0) {
-    const double dssim = rs[0] * inv_nssim, l1 = rl[0] * inv_nl1;
+    const double dssim = t[0] * inv_nssim, l1 = t[1] * inv_nl1;
     loss[0] = (float)((double)w_l1 * l1 + (double)w_ssim * dssim), loss[1] = (float)l1, loss[2] = (float)(1.0 - dssim);
   }
 }

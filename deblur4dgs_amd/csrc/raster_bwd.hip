@@ -1041,4 +1041,55 @@ extern "C" D4GS_API int d4gs_test_wave_sum(int R, const float *in, float *out, v
 #undef D4GS_WS
   return hipGetLastError() == hipSuccess ? 0 : D4GS_ELAUNCH;
 }
+
+// Test hooks of the A/B build only (tests/test_gpu_ordered_sum.py): the two halves of the losses' fixed-order sum (reduce.h), one
+// block each.  The header is included here, inside the A/B build's part, and by nothing the product build of this file compiles.
+#include "reduce.h"
+namespace {
+template <int R, class T>
+__global__ void __launch_bounds__(REDUCE_NT) k_test_block_sum(const T *in, T *out) {  // in [256,R] -> out [R]
+  __shared__ T red[4 * R];
+  T v[R];
+#pragma unroll
+  for (int k = 0; k < R; k++) v[k] = in[threadIdx.x * R + k];
+  block_sum_store(v, red);
+  __syncthreads();
+  if (threadIdx.x < R) out[threadIdx.x] = block_sum_combine<R>(red, threadIdx.x);
+}
+template <int R, class Tin>
+__global__ void __launch_bounds__(REDUCE_NT) k_test_ordered_total(const Tin *in, int64_t n, int64_t stride, double *out) {
+  double t[R];
+  ordered_total(in, n, stride, t);
+  if (threadIdx.x == REDUCE_NT - 1)  // every thread holds the totals: read them from the last one
+#pragma unroll
+    for (int k = 0; k < R; k++) out[k] = t[k];
+}
+template <class T>
+int test_block_sum(int R, const T *in, T *out, hipStream_t st) {
+  void (*const k[])(const T *, T *) = {k_test_block_sum<1, T>, k_test_block_sum<2, T>, k_test_block_sum<3, T>};
+  if (R < 1 || R > 3) return D4GS_EINVAL;
+  hipLaunchKernelGGL(k[R - 1], dim3(1), dim3(REDUCE_NT), 0, st, in, out);
+  return hipGetLastError() == hipSuccess ? 0 : D4GS_ELAUNCH;
+}
+template <class T>
+int test_ordered_total(int R, const T *in, int64_t n, int64_t stride, double *out, hipStream_t st) {
+  void (*const k[])(const T *, int64_t, int64_t, double *) = {k_test_ordered_total<1, T>, k_test_ordered_total<2, T>, k_test_ordered_total<3, T>,
+                                                              nullptr, k_test_ordered_total<5, T>};
+  if (R < 1 || R > 5 || !k[R - 1]) return D4GS_EINVAL;
+  hipLaunchKernelGGL(k[R - 1], dim3(1), dim3(REDUCE_NT), 0, st, in, n, stride, out);
+  return hipGetLastError() == hipSuccess ? 0 : D4GS_ELAUNCH;
+}
+}  // namespace
+// in [256,R] and out [R] of float (is_double == 0) or double; R in {1, 2, 3}
+extern "C" D4GS_API int d4gs_test_block_sum(int R, int is_double, const void *in, void *out, void *stream) {
+  if (!in || !out) return D4GS_EINVAL;
+  return is_double ? test_block_sum(R, (const double *)in, (double *)out, (hipStream_t)stream)
+                   : test_block_sum(R, (const float *)in, (float *)out, (hipStream_t)stream);
+}
+// in: at least (n - 1) stride + R elements of float (is_double == 0) or double, stride >= R; out [R] doubles; R in {1, 2, 3, 5}
+extern "C" D4GS_API int d4gs_test_ordered_total(int R, int is_double, const void *in, int64_t n, int64_t stride, double *out, void *stream) {
+  if (!in || !out || n < 1 || stride < R) return D4GS_EINVAL;
+  return is_double ? test_ordered_total(R, (const double *)in, n, stride, out, (hipStream_t)stream)
+                   : test_ordered_total(R, (const float *)in, n, stride, out, (hipStream_t)stream);
+}
 #endif

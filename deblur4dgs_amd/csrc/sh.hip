@@ -10,10 +10,11 @@
 // = -sum_n v_p[n] is a deterministic two-level sum (per-block partials in a fixed tree order, then one ordered block),
 // like the photometric loss's.
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
-constexpr int SH_BLOCK = 256;
+constexpr int SH_BLOCK = REDUCE_NT;
 
 // forward-mode dual number: value and its partials w.r.t. the unit direction's (x, y, z); gives each basis polynomial's
 // gradient from the same source as its value
@@ -204,38 +205,18 @@ __global__ void __launch_bounds__(SH_BLOCK) k_sh_bwd(const ShArgs a) {
     }
   }
   if (!a.partials) return;  // uniform over the launch
-  // block sum of v_p in a fixed order: lanes (shuffle tree), then the 4 waves
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) vp[ch] += __shfl_xor(vp[ch], o);
-  const int w = threadIdx.x / D4GS_WAVE;
-  if ((threadIdx.x & (D4GS_WAVE - 1)) == 0) red[3 * w] = vp[0], red[3 * w + 1] = vp[1], red[3 * w + 2] = vp[2];
+  block_sum_store(vp, red);  // the block's sum of v_p
   __syncthreads();
-  if (threadIdx.x < 3) {
-    const int ch = threadIdx.x;
-    a.partials[3 * (int64_t)blockIdx.x + ch] = (red[ch] + red[3 + ch]) + (red[6 + ch] + red[9 + ch]);
-  }
+  if (threadIdx.x < 3) a.partials[3 * (int64_t)blockIdx.x + threadIdx.x] = block_sum_combine<3>(red, threadIdx.x);
 }
-static_assert(SH_BLOCK == 4 * D4GS_WAVE, "k_sh_bwd's block sum is written for four waves");
 
-// v_origin = -sum of the block partials; one block, fixed order (strided fp64 sums, then a tree)
+// v_origin = -sum of the block partials; one block
 __global__ void __launch_bounds__(256) k_sh_finish(const float *partials, int64_t n_blocks, float *v_origin) {
-  __shared__ double r[3][256];
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int64_t i = threadIdx.x; i < n_blocks; i += 256)
+  double t[3];
+  ordered_total(partials, n_blocks, 3, t);
+  if (threadIdx.x == 0)
 #pragma unroll
-    for (int ch = 0; ch < 3; ch++) s[ch] += partials[3 * i + ch];
-#pragma unroll
-  for (int ch = 0; ch < 3; ch++) r[ch][threadIdx.x] = s[ch];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-#pragma unroll
-      for (int ch = 0; ch < 3; ch++) r[ch][threadIdx.x] += r[ch][threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) v_origin[threadIdx.x] = (float)-r[threadIdx.x][0];
+    for (int ch = 0; ch < 3; ch++) v_origin[ch] = (float)-t[ch];
 }
 
 int64_t sh_blocks(int64_t N) { return (N + SH_BLOCK - 1) / SH_BLOCK; }

@@ -18,10 +18,11 @@
 // first two), so a wave first peels off up to TRIM_PEEL groups of lanes that share a digit - one add of the group's size each - and
 // only the lanes left after that add one by one (keys spread over many bins, where lanes rarely meet).
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
-constexpr int TB = 256;                      // threads per block, all kernels
+constexpr int TB = REDUCE_NT;                      // threads per block, all kernels
 constexpr int TRIM_ITEMS = 8;                // elements per thread before the grid stops growing
 constexpr int TRIM_MAX_BLOCKS = 1024;        // 4 per CU; beyond that the data passes stride
 constexpr int TRIM_PEEL = 4;
@@ -209,7 +210,7 @@ __device__ __forceinline__ bool trim_kept(float v, float t, bool keep_all) { ret
 
 __global__ void __launch_bounds__(TB) k_trim_sum(const float *__restrict__ values, const float *__restrict__ weights, int64_t n_max,
                                                  const uint32_t *__restrict__ ctrl_all, int sel_terms, double *__restrict__ partials) {
-  __shared__ double red[3][TB / 64];
+  __shared__ double red[PARTIAL_DOUBLES * (TB / 64)];
   const int term = blockIdx.y, tid = threadIdx.x;
   const bool keep_all = term >= sel_terms;
   const float t = __uint_as_float(ctrl_all[(int64_t)term * C_WORDS + C_T]);
@@ -223,11 +224,11 @@ __global__ void __launch_bounds__(TB) k_trim_sum(const float *__restrict__ value
       s_vm += (double)(vi * m), s_m += (double)m, cnt += 1.0;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s_vm += __shfl_xor(s_vm, o), s_m += __shfl_xor(s_m, o), cnt += __shfl_xor(cnt, o);
-  if ((tid & 63) == 0) red[0][tid >> 6] = s_vm, red[1][tid >> 6] = s_m, red[2][tid >> 6] = cnt;
+  double s[PARTIAL_DOUBLES] = {s_vm, s_m, cnt};
+  block_sum_store(s, red);
   __syncthreads();
-  if (tid < 3) partials[((int64_t)term * gridDim.x + blockIdx.x) * PARTIAL_DOUBLES + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+  if (tid < PARTIAL_DOUBLES)
+    partials[((int64_t)term * gridDim.x + blockIdx.x) * PARTIAL_DOUBLES + tid] = block_sum_combine<PARTIAL_DOUBLES>(red, tid);
 }
 
 // out[0] = sum of the terms' losses; per term k: out[1 + 2k] = threshold, out[2 + 2k] = 1 / denominator (what the backward scales by),
@@ -236,26 +237,16 @@ __global__ void __launch_bounds__(TB) k_trim_sum(const float *__restrict__ value
 // a term that selected among no live slot at all (its threshold is NaN) is NaN, as the mean forms are
 __global__ void __launch_bounds__(TB) k_trim_finish(const double *__restrict__ partials, int n_blocks, int terms, int mode,
                                                     const uint32_t *__restrict__ ctrl_all, float *out) {
-  __shared__ double r[3][TB];
   double total = 0.0;
   for (int term = 0; term < terms; term++) {
-    double a[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < n_blocks; i += TB)
-      for (int k = 0; k < 3; k++) a[k] += partials[((int64_t)term * n_blocks + i) * PARTIAL_DOUBLES + k];
-    for (int k = 0; k < 3; k++) r[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int o = TB / 2; o > 0; o >>= 1) {
-      if (threadIdx.x < o)
-        for (int k = 0; k < 3; k++) r[k][threadIdx.x] += r[k][threadIdx.x + o];
-      __syncthreads();
-    }
-    const double den = mode == 1 ? r[2][0] : r[1][0] + 1e-8;
+    double r[PARTIAL_DOUBLES];  // every thread gets the term's sums: sum v * m, sum m, count
+    ordered_total(partials + (int64_t)term * n_blocks * PARTIAL_DOUBLES, n_blocks, PARTIAL_DOUBLES, r);
+    const double den = mode == 1 ? r[2] : r[1] + 1e-8;
     const float t = __uint_as_float(ctrl_all[(int64_t)term * C_WORDS + C_T]);
-    double loss = r[0][0] / den;  // 0 / 0 = NaN: an empty kept set, as torch's mean of nothing
+    double loss = r[0] / den;  // 0 / 0 = NaN: an empty kept set, as torch's mean of nothing
     if (mode == 2 && t != t) loss = (double)t;
     total += loss;
     if (threadIdx.x == 0) out[1 + 2 * term] = t, out[2 + 2 * term] = (float)(1.0 / den), out[5 + term] = (float)loss;
-    __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = (float)total;
 }
@@ -353,12 +344,6 @@ __global__ void __launch_bounds__(TB) k_track_values(const float *__restrict__ t
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(&cnt, c);
   __syncthreads();
   if (threadIdx.x < 2 && cnt) atomicAdd(&ctrl[threadIdx.x * C_WORDS + C_COUNT], cnt);
-}
-
-// (a kernel, not a memset node: csrc/warp.hip, k_warp_zero)
-__global__ void __launch_bounds__(TB) k_track_zero(float *__restrict__ p, int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += stride) p[i] = 0.f;
 }
 
 // one thread per live element adds K^T dL/d(K X) to its point.  torch.clamp(min) passes the gradient where its input is >= the
@@ -593,8 +578,9 @@ int d4gs_track_losses_bwd(const float *tracks_3d, const int32_t *pix, const int3
   if (int rc = track_check("d4gs_track_losses_bwd", ptrs, 12, n_pixels, N, n_rows, n_elements, quantile)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t n_floats = n_pixels * N * 3;
-  D4GS_LAUNCH("k_track_zero", k_track_zero, dim3((unsigned)trim_blocks(n_floats)), dim3(TB), 0, s, v_tracks_3d, n_floats);
-  if (int rc = d4gs_check_launch("k_track_zero")) return rc;
+  // (a kernel, not a memset node: reduce.h)
+  D4GS_LAUNCH("k_zero_f32", k_zero_f32<>, dim3((unsigned)trim_blocks(n_floats)), dim3(TB), 0, s, v_tracks_3d, n_floats);
+  if (int rc = d4gs_check_launch("k_zero_f32")) return rc;
   D4GS_LAUNCH("k_track_bwd", k_track_bwd, dim3((unsigned)trim_blocks(n_elements)), dim3(TB), 0, s, tracks_3d, pix, rows, visible, weights,
               target_2d, target_depth, Ks, values, out, v_losses, n_pixels, (int)N, (int)n_rows, n_elements, (int)(quantile >= 1.f),
               v_tracks_3d);

@@ -8,10 +8,11 @@
 // in-bounds weights; mask = coverage > 0.999.  Gradients go to the sampled image only: a scatter with float atomics (the forward
 // sums are ordered and reproducible, the scattered gradient is not bitwise so).
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
-constexpr int WB = 256;
+constexpr int WB = REDUCE_NT;
 constexpr int WARP_MAX_BLOCKS = 4096;
 constexpr int AL1_MAX_BLOCKS = 128;  // per pair
 constexpr int AL1_C = 3;
@@ -110,30 +111,21 @@ __global__ void __launch_bounds__(WB) k_al1_fwd(const float *__restrict__ pred, 
                                                 const float *__restrict__ mask, int H, int W, double *__restrict__ partials) {
   __shared__ double red[WB / 64];
   const int64_t p = blockIdx.y, plane = (int64_t)H * W;
-  double sum = 0.0;
+  double sum[1] = {0.0};
   for (int64_t r = (int64_t)blockIdx.x * WB + threadIdx.x; r < plane; r += (int64_t)gridDim.x * WB) {
     const Al1Pixel q = al1_pixel(flow, mask, p, r, H, W);
-    for (int c = 0; c < AL1_C; c++) sum += (double)fabsf(al1_diff(pred, target, q, p * AL1_C + c, r, H, W));
+    for (int c = 0; c < AL1_C; c++) sum[0] += (double)fabsf(al1_diff(pred, target, q, p * AL1_C + c, r, H, W));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  block_sum_store(sum, red);
   __syncthreads();
-  if (threadIdx.x == 0) partials[p * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) partials[p * gridDim.x + blockIdx.x] = block_sum_combine<1>(red, 0);
 }
 
 // one block per pair adds its partials in a fixed order
 __global__ void __launch_bounds__(WB) k_al1_finish(const double *__restrict__ partials, int n_blocks, double inv_n, float *__restrict__ losses) {
-  __shared__ double r[WB];
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n_blocks; i += WB) a += partials[(int64_t)blockIdx.x * n_blocks + i];
-  r[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = WB / 2; o > 0; o >>= 1) {
-    if (threadIdx.x < o) r[threadIdx.x] += r[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) losses[blockIdx.x] = (float)(r[0] * inv_n);
+  double t[1];
+  ordered_total(partials + (int64_t)blockIdx.x * n_blocks, n_blocks, 1, t);
+  if (threadIdx.x == 0) losses[blockIdx.x] = (float)(t[0] * inv_n);
 }
 
 __global__ void __launch_bounds__(WB) k_al1_bwd(const float *__restrict__ pred, const float *__restrict__ flow, const float *__restrict__ target,
@@ -150,12 +142,6 @@ __global__ void __launch_bounds__(WB) k_al1_bwd(const float *__restrict__ pred, 
       if (v_target) v_target[(p * AL1_C + c) * plane + r] = -g;
     }
   }
-}
-
-// the scatter targets are zeroed by a kernel, not by hipMemsetAsync: a memset node did not take effect when a captured graph was
-// replayed (tests/test_gpu_pwc.py::test_graph_capture_and_replay saw the scatter land on uninitialised memory)
-__global__ void __launch_bounds__(WB) k_warp_zero(float *__restrict__ p, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * WB + threadIdx.x; i < n; i += (int64_t)gridDim.x * WB) p[i] = 0.f;
 }
 
 int warp_check(const char *who, int32_t B, int32_t C, int32_t H, int32_t W) {
@@ -179,9 +165,10 @@ unsigned warp_blocks(int64_t n, int cap) {
   return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
+// the scatter targets are zeroed by a kernel, not by a memset node (reduce.h)
 int warp_zero(float *p, int64_t n, hipStream_t stream) {
-  D4GS_LAUNCH("k_warp_zero", k_warp_zero, dim3(warp_blocks(n, WARP_MAX_BLOCKS)), dim3(WB), 0, stream, p, n);
-  return d4gs_check_launch("k_warp_zero");
+  D4GS_LAUNCH("k_zero_f32", k_zero_f32<>, dim3(warp_blocks(n, WARP_MAX_BLOCKS)), dim3(WB), 0, stream, p, n);
+  return d4gs_check_launch("k_zero_f32");
 }
 
 }  // namespace

@@ -1,0 +1,254 @@
+"""Two builds of libd4gs.so give the same bits in every loss and metric that sums in a fixed order (csrc/reduce.h) - and take the same time.
+
+    python scripts/ab_bitwise.py PARENT.so [NEW.so] [--times] [--rounds 2] [--out FILE]
+
+PARENT.so: the parent commit's library (export it with `git archive <parent>` into the git-ignored scripts/ablate/parent/, build it there
+with `python -m deblur4dgs_amd.build --force`); NEW.so defaults to this tree's deblur4dgs_amd/libd4gs.so.  D4GS_LIB_PATH is read when
+the package loads the library, so every library gets a fresh child process of its own, each under its own `timeout`; the chain stops
+at the first child that fails.
+
+Digests (the default): each child runs seeded cases through the public entry points - photometric_loss, masked_l1_loss,
+trimmed_l1_loss, compute_gradient_loss, track_losses, motion_regularizers, masked_image_metrics with and without SSIM, the aligned-L1
+path of pwcnet, spherical harmonics forward and backward with a view-origin gradient - forward and backward, at two sizes: a smallest
+shape of the loss's GPU test and one whose count of block partials exceeds 256 (aligned L1 caps its partials at 128 per pair: that
+size), and prints the sha256 of every output and gradient.  The script fails if a digest differs between the libraries.
+
+--times: the losses at their own benchmarks' sizes (scripts/bench_photometric.py, bench_metrics.py, bench_trimmed.py, bench_aligned.py's
+frame and pair count for the aligned L1 alone, bench_sh.py's first configuration, the regularizers at the size of
+profiles/motion_regs_step_times.json), forward + backward captured once into a HIP graph, device events around windows of replays;
+parent and new alternate, --rounds children each, and the new library's median is held against the spread of the parent's own runs.
+"""
+import argparse
+import hashlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHILD_SECONDS = 420
+
+
+# ---- the cases: name -> (builder(size) -> callable returning the outputs and gradients).  size: "small" | "large" | "bench" ----
+
+def _cases():
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from deblur4dgs_amd import losses as Ls
+    from deblur4dgs_amd import metrics as M
+    from deblur4dgs_amd import pwcnet as P
+    from deblur4dgs_amd.sh import SHFn
+
+    dev = "cuda:0"
+
+    def rnd(seed):
+        g = torch.Generator().manual_seed(seed)
+        return (lambda *s: torch.rand(*s, generator=g)), (lambda *s: torch.randn(*s, generator=g))
+
+    def fwd_bwd(fn, leaves):
+        xs = [x.clone().requires_grad_() for x in leaves]
+        out = fn(*xs)
+        outs = list(out) if isinstance(out, (tuple, list)) else [out]
+        total = sum((1.0 + 0.5 * i) * o.sum() for i, o in enumerate(outs))
+        total.backward()
+        return [o.detach() for o in outs] + [x.grad for x in xs]
+
+    def photometric(size):
+        B, H, W = {"small": (3, 16, 11), "large": (1, 288, 512), "bench": (1, 288, 512)}[size]
+        u, n = rnd(1)
+        gt = u(B, H, W, 3)
+        pred = (gt + 0.1 * n(B, H, W, 3)).clamp(0, 1).to(dev)
+        mask = (u(B, H, W, 1) > 0.3).float().to(dev)
+        gt = gt.to(dev)
+        return lambda: fwd_bwd(lambda x: Ls.photometric_loss(x, gt, mask, return_terms=True), [pred])
+
+    def depth_inputs(size, seed):
+        shape = {"small": (1, 3, 5, 1), "large": (1, 640, 1000, 1), "bench": (1, 288, 512, 1)}[size]
+        u, n = rnd(seed)
+        gt = 1.0 / (2.0 + 3.0 * u(*shape))
+        pred = (gt * (1.0 + 0.1 * n(*shape))).to(dev)
+        mask = (u(*shape) < 0.8).float().to(dev)
+        return pred, gt.to(dev), mask
+
+    def masked_l1(size):
+        pred, gt, mask = depth_inputs(size, 2)
+        return lambda: fwd_bwd(lambda x: Ls.masked_l1_loss(x, gt, mask, quantile=0.98), [pred])
+
+    def trimmed_l1(size):
+        pred, gt, _ = depth_inputs(size, 3)
+        return lambda: fwd_bwd(lambda x: Ls.trimmed_l1_loss(x, gt, 0.9), [pred])
+
+    def gradient_loss(size):
+        pred, gt, mask = depth_inputs(size, 4)
+        valid = mask > 0.5
+        if size == "small":
+            valid = torch.ones_like(valid)
+        return lambda: fwd_bwd(lambda x: Ls.compute_gradient_loss(x, gt, valid, quantile=0.95), [pred])
+
+    def tracks(size):
+        # distinct query pixels in raster order: every gradient address gets one add onto zero, so the scatter is bitwise too
+        N, Pq, H, W = {"small": (1, 1, 12, 16), "large": (4, 140000, 400, 400), "bench": (7, 4096, 288, 512)}[size]
+        u, n = rnd(5)
+        g = torch.Generator().manual_seed(55)
+        idx = torch.sort(torch.randperm(H * W, generator=g)[:Pq]).values
+        q = torch.stack([idx % W, idx // W], -1).float() + 0.5
+        K = torch.eye(3).repeat(N, 1, 1)
+        K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2] = 300.0, 300.0, W / 2, H / 2
+        z = 1.0 + 4.0 * u(1, H, W, N)
+        t3 = torch.stack([(u(1, H, W, N) - 0.5) * z, (u(1, H, W, N) - 0.5) * z, z], -1).to(dev)
+        kw = dict(query_tracks_2d=q.to(dev), target_Ks=K.to(dev), target_tracks_2d=(torch.tensor([W, H]) * u(N, Pq, 2)).to(dev),
+                  target_visibles=(u(N, Pq) < 0.7).to(dev), track_weights=(0.1 + u(N * Pq)).to(dev),
+                  target_track_depths=(1.0 + 4.0 * u(N, Pq)).to(dev))
+        return lambda: fwd_bwd(lambda x: Ls.track_losses(x, quantile=0.98, **kw), [t3])
+
+    def motion(size):
+        G, K, T, B = {"small": (1, 1, 3, 1), "large": (70000, 32, 2100, 2), "bench": (40000, 20, 7, 8)}[size]
+        u, n = rnd(6)
+        rots = torch.eye(3)[:2].reshape(6).expand(K, T, 6) + 0.1 * n(K, T, 6)
+        leaves = [n(G, 3), n(G, K), rots, 0.1 * n(K, T, 3), 0.3 * n(G, 3)]  # means, motion_coefs, rots, transls, scales
+        ts = (u(B) * (T - 1)).to(dev)
+        w2c = torch.eye(4).repeat(B, 1, 1)
+        w2c[:, :3, :3] += 0.05 * n(B, 3, 3)
+        w2c[:, :3, 3] = n(B, 3) + torch.tensor([0.0, 0.0, 6.0])
+        w2c = w2c.to(dev)
+        leaves = [x.to(dev) for x in leaves]
+        return lambda: fwd_bwd(lambda m, c, r, t, s: Ls.motion_regularizers(m, c, r, t, s, ts, w2c), leaves)
+
+    def metrics(size, ssim):
+        shapes = {"small": [(1, 1, 11, 11)], "large": [(3, 1, 288, 512)], "bench": [(3, 1, 288, 512), (3, 1, 720, 1280)]}[size]
+        data = []
+        for Mm, B, H, W in shapes:
+            u, n = rnd(7 + H)
+            target = u(B, H, W, 3)
+            pred = (target + 0.1 * n(B, H, W, 3)).clamp(0, 1).to(dev)
+            masks = (u(Mm, B, H, W) < 0.9).float().to(dev)
+            data.append((pred, target.to(dev), masks))
+
+        def run():
+            with torch.no_grad():
+                return [o for pred, target, masks in data for o in M.masked_image_metrics(pred, target, masks, ssim=ssim) if torch.is_tensor(o)]
+        return run
+
+    def aligned(size):
+        Pn, H, W = {"small": (2, 8, 12), "large": (3, 288, 512), "bench": (20, 288, 512)}[size]
+        u, n = rnd(8)
+        pred, target, flow = u(Pn, 3, H, W).to(dev), u(Pn, 3, H, W).to(dev), (3.0 * n(Pn, 2, H, W)).to(dev)
+        mask = (0.2 + 0.8 * u(Pn, 1, H, W)).to(dev)
+        if size == "bench":  # as the training step calls it: the gradient goes to pred
+            return lambda: fwd_bwd(lambda p: P.aligned_l1(p, flow, target, mask), [pred])
+        # the scatter onto pred's gradient uses float atomics and is not bitwise (csrc/warp.hip): digest the losses and the target's gradient
+        return lambda: fwd_bwd(lambda t: P.aligned_l1(pred, flow, t, mask), [target])
+
+    def sh(size):
+        d, K, N = {"small": (2, 9, 1), "large": (3, 16, 70001), "bench": (3, 16, 1 << 20)}[size]
+        u, n = rnd(9)
+        p, o, c = (4 * n(N, 3)).to(dev), torch.tensor([0.1, -0.2, -3.0]).to(dev), (0.3 * n(N, K, 3)).to(dev)
+        return lambda: fwd_bwd(lambda pp, oo, cc: SHFn.apply(d, pp, oo, cc, None, True), [p, o, c])
+
+    return {"photometric_loss": photometric, "masked_l1_loss": masked_l1, "trimmed_l1_loss": trimmed_l1, "compute_gradient_loss": gradient_loss,
+            "track_losses": tracks, "motion_regularizers": motion, "masked_image_metrics ssim": lambda s: metrics(s, True),
+            "masked_image_metrics psnr only": lambda s: metrics(s, False), "aligned_l1": aligned, "sh fwd+bwd with origin": sh}
+
+
+def child(times, iters, windows):
+    import torch
+
+    assert torch.cuda.is_available(), "ab_bitwise.py runs on the GPU"
+    for name, make in _cases().items():
+        if not times:
+            for size in ("small", "large"):
+                outs = make(size)()
+                torch.cuda.synchronize()
+                for i, o in enumerate(outs):
+                    h = hashlib.sha256(o.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+                    print(f"DIGEST {name} | {size} | {i} {tuple(o.shape)} | {h}", flush=True)
+            continue
+        fn = make("bench")
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()  # replayed from a graph: the host's own time per call is several times the kernels' and noisier
+        with torch.cuda.graph(graph):
+            keep = fn()  # noqa: F841  (the graph's outputs stay alive)
+        for _ in range(20):
+            graph.replay()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(windows):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                graph.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(1e3 * e0.elapsed_time(e1) / iters)
+        print("TIME " + json.dumps({"case": name, "median_us": statistics.median(us), "min_us": min(us), "max_us": max(us)}), flush=True)
+
+
+def run_child(lib, extra):
+    env = dict(os.environ, D4GS_LIB_PATH=os.path.abspath(lib))
+    cmd = ["timeout", "-k", "10", str(CHILD_SECONDS), sys.executable, os.path.abspath(__file__), "--child", *extra]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
+    if r.returncode != 0:
+        sys.stdout.write(r.stdout[-4000:] + r.stderr[-4000:])
+        raise SystemExit(f"the child of {lib} ended with status {r.returncode}: stopping here")
+    return r.stdout.splitlines()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("parent", nargs="?")
+    ap.add_argument("new", nargs="?", default=os.path.join(ROOT, "deblur4dgs_amd", "libd4gs.so"))
+    ap.add_argument("--child", action="store_true")
+    ap.add_argument("--times", action="store_true")
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--iters", type=int, default=500)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.times, a.iters, a.windows)
+    if not a.parent:
+        ap.error("the parent commit's library is required")
+    sha = lambda p: hashlib.sha256(open(p, "rb").read()).hexdigest()
+    lines = [f"parent {sha(a.parent)}  {os.path.relpath(a.parent, ROOT)}", f"new    {sha(a.new)}  {os.path.relpath(a.new, ROOT)}"]
+    ok = True
+    if not a.times:
+        dig = {}
+        for tag, lib in (("parent", a.parent), ("new", a.new)):
+            dig[tag] = {k: v for k, v in (ln[7:].rsplit(" | ", 1) for ln in run_child(lib, []) if ln.startswith("DIGEST "))}
+        assert dig["parent"] and dig["parent"].keys() == dig["new"].keys(), "the two children did not run the same cases"
+        for k, h in dig["parent"].items():
+            same = dig["new"][k] == h
+            ok &= same
+            lines.append(f"{'equal ' if same else 'DIFFER'} {k} | {h[:16]} {'' if same else dig['new'][k][:16]}")
+        lines.append(f"{len(dig['parent'])} digests, {'every one equal' if ok else 'NOT all equal'}")
+    else:
+        runs = {"parent": [], "new": []}
+        for _ in range(a.rounds):
+            for tag, lib in (("parent", a.parent), ("new", a.new)):
+                out = run_child(lib, ["--times", "--iters", str(a.iters), "--windows", str(a.windows)])
+                runs[tag].append({r["case"]: r for r in (json.loads(ln[5:]) for ln in out if ln.startswith("TIME "))})
+        lines.append(f"us per forward + backward (graph replay); {a.rounds} processes per library, alternating; each figure the median of {a.windows} windows of {a.iters} graph replays")
+        lines.append(f"{'case':34s} {'parent runs':>24s} {'parent spread':>14s} {'new runs':>24s} {'new median':>11s}  verdict")
+        for case in runs["parent"][0]:
+            p = [r[case]["median_us"] for r in runs["parent"]]
+            n = [r[case]["median_us"] for r in runs["new"]]
+            spread, med = max(p) - min(p), statistics.median(n)
+            inside = min(p) - spread <= med <= max(p) + spread
+            ok &= med <= max(p) + spread
+            lines.append(f"{case:34s} {' '.join(f'{x:.1f}' for x in p):>24s} {spread:14.2f} {' '.join(f'{x:.1f}' for x in n):>24s} {med:11.1f}  "
+                         f"{'inside the parent runs or within their spread' if inside else ('FASTER than the parent by more than its spread' if med < min(p) else 'SLOWER than the parent by more than its spread')}")
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(text)
+    if not ok:
+        raise SystemExit(1)
+
+
+if __name__ == "__main__":
+    main()
