@@ -442,6 +442,24 @@ __device__ __forceinline__ float4 stage_conic(float a, float b, float c, float w
   return make_float4(a * (0.5f * LOG2E_), b * LOG2E_, c * (0.5f * LOG2E_), w);
 }
 
+// The forward composite's block filter (raster_fwd.hip): d4gs_ellipse_hits_rect on a staged record - g1 = stage_conic(a, b, c, tau *
+// log2(e)), tau = d4gs_alpha_tau(opacity), everything in splat_sigma2's units - for the pixel-centre rectangle [X0, X1] x [Y0, Y1] of
+// a 4x4 block.  Branch-free: sigma is convex, so its minimum over the rectangle lies on the point of the line u = uc (vc: v = vc)
+// nearest to that line's own minimiser, uc / vc = the rectangle's coordinate nearest to the centre; where the centre's coordinate is
+// inside the rectangle's range that line is no edge but still part of the rectangle, so the smaller of the two values is the
+// minimum either way (0 when the centre is inside).  Compared negated: a NaN keeps the pair.
+__device__ __forceinline__ float d4gs_alpha_tau(float opac) { return __logf(255.f * opac) * 1.01f + 0.02f; }
+__device__ __forceinline__ bool d4gs_block_filter_keep(float mx, float my, const float4 g1, float X0, float X1, float Y0, float Y1) {
+#pragma clang fp contract(off)
+  const float U0 = X0 - mx, U1 = X1 - mx, V0 = Y0 - my, V1 = Y1 - my;
+  const float uc = __builtin_amdgcn_fmed3f(0.f, U0, U1), vc = __builtin_amdgcn_fmed3f(0.f, V0, V1);
+  // g1 = (a / 2, b, c / 2) log2(e): v* = -b uc / c = -(g1.y uc) / (2 g1.z)
+  const float v = __builtin_amdgcn_fmed3f((g1.y * uc) * __builtin_amdgcn_rcpf(-2.f * g1.z), V0, V1);
+  const float u = __builtin_amdgcn_fmed3f((g1.y * vc) * __builtin_amdgcn_rcpf(-2.f * g1.x), U0, U1);
+  const float best = fminf(splat_sigma2(g1, uc, v), splat_sigma2(g1, u, vc));
+  return !(best > g1.w * 1.001f + 1.5e-4f);  // (d4gs_ellipse_hits_rect's hair of slack, times log2(e))
+}
+
 // ---- fused DPP adds ------------------------------------------------------------------------------------------
 // hipcc lowers `x + update_dpp(x)` to v_mov_b32_dpp + v_add_f32 (2 issue slots per step).  The asm blocks below
 // issue the fused v_add_f32_dpp instead.  Inside one block consecutive steps on the same register are >= 3

@@ -44,6 +44,7 @@ struct RasterFwdArgs {
   const int32_t *lazy_near;
   int32_t *lazy_flag;
   int lazy_pass;
+  int block_filter;  // D4GS_BLOCK_FILTER: the rows' lists of a batch are filtered with the exact ellipse test before they are composited
 #ifdef D4GS_TRACE  // A/B builds only (scripts/trace_wgs.py --fwd): per-workgroup wall clock {start, end}, hardware id, list entries,
   unsigned long long *trace;  // and the time spent in the staging / list-building / compositing phases of its batches
 #endif
@@ -225,8 +226,8 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
       const float4 *gp = reinterpret_cast<const float4 *>(a.geom + (inst_base + gid) * D4GS_GEOM_STRIDE);
       const float4 q0 = gp[0], q1 = gp[1];
       sg0[tid] = q0;
-      sg1[tid] = stage_conic(q1.x, q1.y, q1.z, 0.f);
-      const float tau = __logf(255.f * q0.z) * 1.01f + 0.02f;
+      const float tau = d4gs_alpha_tau(q0.z);
+      sg1[tid] = stage_conic(q1.x, q1.y, q1.z, tau * 1.4426950408889634f);  // (w: the block filter's threshold; splat_sigma2 does not read it)
       const float det = q1.x * q1.z - q1.y * q1.y;
       const float idet = 1.f / det;
       float ex = -1.f, ey = -1.f;
@@ -242,7 +243,10 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
     __syncthreads();
     D4GS_TCLK(_tb)
     D4GS_TADD(_ts, _ta, _tb)
-    const int nb = min(FBE, end - b) + (NULL0 ? 1 : 0);  // slots in use
+    // A wave whose 64 pixels are all saturated while another wave of the tile is not lists nothing: its composite loop would look at
+    // `done` only after 16 steps, in every batch the tile still stages.
+    const bool wave_live = __builtin_amdgcn_ballot_w64(done) != ~0ull;  // wave-uniform
+    const int nb = wave_live ? min(FBE, end - b) + (NULL0 ? 1 : 0) : 0;  // slots in use
     // ---- per-row lists of this wave's quadrant ----
     int c0 = 0, c1 = 0, c2 = 0, c3 = 0;  // wave-uniform list lengths
     // The wave's four lists start out as zeros (one 16-byte store per lane and batch): the composite loop reads list bytes past a
@@ -272,10 +276,45 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
       c0 += __popcll(m0), c1 += __popcll(m1), c2 += __popcll(m2), c3 += __popcll(m3);
     }
     __builtin_amdgcn_wave_barrier();
+    // ---- block filter: the box test above is loose (profiles/pair_stats_fwd_ellipse.txt: 18 % of the pairs it lists are not reached by the
+    // splat's alpha >= 1/255 ellipse).  Every row tests the entries of its own list against its own block with the exact ellipse
+    // test (common.h: d4gs_block_filter_keep) - the row's 16 lanes take 16 list positions per pass, the four rows side by side as in
+    // the composite, so the list, the rectangle and the row's lanes are the lane's own from batch to batch - and writes the survivors
+    // back in place, in order.  It may only remove steps in which no pixel of the block passes alpha >= 1/255: the image does not
+    // change.
+    int cnt = row == 0 ? c0 : row == 1 ? c1 : row == 2 ? c2 : c3;
+    int imax = max(max(c0, c1), max(c2, c3));
+    if (a.block_filter) {
+      // (the lane's constants of the pass are formed here, per batch, from a copy of `lane` the compiler cannot see through: hoisted out
+      // of the batch loop they would stay live across the composite loop, which has no register to spare - 64 VGPRs, 8 waves per SIMD)
+      int lf = lane;
+      asm volatile("" : "+v"(lf));
+      const int kf = lf & 15, rsh = lf & 48;  // place in the row, the row's first lane
+      unsigned char *mylist_w = wlist + rsh * (FB / 16);
+      const float X0 = pxf - (float)(kf & 3), Y0 = pyf - (float)(kf >> 2);  // the block's first pixel centre (image coordinates, as the staged centres)
+      const float X1 = X0 + 3.f, Y1 = Y0 + 3.f;
+      const unsigned below = (1u << kf) - 1u;  // the lanes of the row in front of this one
+      int n = 0;  // survivors of this lane's row so far
+      for (int i = 0; i < imax; i += 16) {
+        const int p = i + kf;
+        bool keep = false;
+        unsigned char jb = 0;
+        if (p < cnt) {
+          jb = mylist_w[p];
+          const float4 g0 = sg0[jb], g1 = sg1[jb];
+          keep = d4gs_block_filter_keep(g0.x, g0.y, g1, X0, X1, Y0, Y1);
+          if constexpr (NULL0) mylist_w[p] = 0;  // these kernels composite whatever the bytes past a row's count say: the null record again
+        }
+        const unsigned m16 = (unsigned)(__builtin_amdgcn_ballot_w64(keep) >> rsh) & 0xffffu;  // the pass's survivors of this lane's row
+        if (keep) mylist_w[n + __popc(m16 & below)] = jb;  // (never past the pass's own reads)
+        n += __popc(m16);
+      }
+      cnt = n;
+      imax = max(max(__builtin_amdgcn_readlane(n, 0), __builtin_amdgcn_readlane(n, 16)), max(__builtin_amdgcn_readlane(n, 32), __builtin_amdgcn_readlane(n, 48)));
+      __builtin_amdgcn_wave_barrier();
+    }
     D4GS_TCLK(_tc0)
     D4GS_TADD(_tl, _tb, _tc0)
-    const int cnt = row == 0 ? c0 : row == 1 ? c1 : row == 2 ? c2 : c3;
-    const int imax = max(max(c0, c1), max(c2, c3));
     int last16 = -1;  // 16 x the slot of the batch's last contributor to this pixel
     unsigned long long donem = __builtin_amdgcn_ballot_w64(done);  // the saturated pixels of this wave as a lane mask (all 64 lanes are active here)
     // One composite step of this lane's row: staged splat `jr` (ignored past the row's count).
@@ -539,6 +578,8 @@ int d4gs_raster_fwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   a.out = r->render_colors, a.alphas = r->render_alphas, a.last_ids = r->last_ids, a.final_T = r->final_T;
   a.seg_state = d4gs_seg_on(dims, isect, r) ? r->seg_state : nullptr;
   a.lazy_near = nullptr, a.lazy_flag = nullptr, a.lazy_pass = 0;
+  const char *bf = getenv("D4GS_BLOCK_FILTER");  // (read per call, like D4GS_SEG: tests and the A/B toggle it) "0": off
+  a.block_filter = !(bf && bf[0] == '0');
   const bool lazy = d4gs_lazy_on(dims, proj) && isect->n_isect > 0;
   if (lazy) {
     const LazyWs lw = d4gs_lazy_carve(proj->lazy_ws, dims->S, a.tw * a.th);
@@ -577,3 +618,22 @@ int d4gs_raster_fwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   a.lazy_pass = 2;
   return launch(a);
 }
+
+#ifdef D4GS_VARIANTS
+// Test hook of the A/B build only (tests/libd4gs_variants.so, tests/test_gpu_block_filter.py): the forward's block filter on caller-given
+// pairs.  rec[i] = {centre x, y, opacity, conic a, b, c, X0, X1, Y0, Y1}; the record is staged as the kernel stages it; keep[i] = 1 / 0.
+namespace {
+__global__ void __launch_bounds__(64) k_test_block_filter(int n, const float *rec, int32_t *keep) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const float *r = rec + (size_t)i * 10;
+  const float4 g1 = stage_conic(r[3], r[4], r[5], d4gs_alpha_tau(r[2]) * 1.4426950408889634f);
+  keep[i] = d4gs_block_filter_keep(r[0], r[1], g1, r[6], r[7], r[8], r[9]) ? 1 : 0;
+}
+}  // namespace
+extern "C" D4GS_API int d4gs_test_block_filter(int n, const float *rec, int32_t *keep, void *stream) {
+  if (n <= 0) return D4GS_EINVAL;
+  hipLaunchKernelGGL(k_test_block_filter, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, rec, keep);
+  return hipGetLastError() == hipSuccess ? 0 : D4GS_ELAUNCH;
+}
+#endif

@@ -45,6 +45,13 @@ NCHK = {64: (maxlen + 63) // 64 + 1, 128: (maxlen + 127) // 128 + 1, 256: (maxle
 chunk_cnt = {nb: torch.zeros(S * tw * th, NCHK[nb], 16, dtype=torch.int32, device=dev) for nb in NCHK}
 chunk_cnt_g = {nb: torch.zeros(S * tw * th, NCHK[nb], 16, dtype=torch.int32, device=dev) for nb in NCHK}
 chunk_q = {nb: torch.zeros(S * tw * th, NCHK[nb], 4, dtype=torch.int32, device=dev) for nb in NCHK}
+# the forward's batches run from the head of the list (128 entries with depth segments, 256 without); [.., 0]: whole lists,
+# [.., 1]: entries at or before the last contributor of the block's quadrant (a wave leaves a batch once its 64 pixels are saturated)
+FNB = (128, 256)
+NCHF = {nb: (maxlen + nb - 1) // nb + 1 for nb in FNB}
+fwd_box = {nb: torch.zeros(S * tw * th, NCHF[nb], 16, 2, dtype=torch.int32, device=dev) for nb in FNB}
+fwd_ell = {nb: torch.zeros(S * tw * th, NCHF[nb], 16, 2, dtype=torch.int32, device=dev) for nb in FNB}
+K_fwd_bits_zero = 0
 blk_len = torch.zeros(S * tw * th, 16, dtype=torch.long, device=dev)
 blk_len_nz = torch.zeros_like(blk_len)
 q_len = torch.zeros(S * tw * th, 4, dtype=torch.long, device=dev)
@@ -96,6 +103,17 @@ for a0 in range(0, n, CH):
     blk_len_g.index_put_(ti16, (bk & (gb > 0)).long(), accumulate=True)
     q_len_g.index_put_((tile_of[sl][:, None].expand(-1, 4), torch.arange(4, device=dev)[None].expand(hit.shape[0], -1)),
                      (hit_k & (gq > 0)).long(), accumulate=True)
+    # the forward's block filter keeps a (splat, block) pair iff the ellipse reaches the block (gb > 0 stands for it: the filter is
+    # conservative by its margin only); a backward replay none of whose four blocks survived it could be skipped with those bits
+    ell = bhit & (gb > 0)
+    K_fwd_bits_zero += int((hit_k & ~ell.view(-1, 2, 2, 2, 2).permute(0, 1, 3, 2, 4).reshape(-1, 4, 4).any(-1)).sum())
+    lastq_b = lastq.view(-1, 2, 1, 2, 1).expand(-1, 2, 2, 2, 2).reshape(-1, 16)  # the block's quadrant's last contributor
+    liveb = idx_in_list[sl, None] <= lastq_b
+    for nb in FNB:
+        ckf = (idx_in_list[sl] - offs[tile_of[sl]]) // nb
+        ii = (tile_of[sl][:, None].expand(-1, 16), ckf[:, None].expand(-1, 16), torch.arange(16, device=dev)[None].expand(bhit.shape[0], -1))
+        fwd_box[nb].index_put_(ii, torch.stack([bhit, bhit & liveb], -1).int(), accumulate=True)
+        fwd_ell[nb].index_put_(ii, torch.stack([ell, ell & liveb], -1).int(), accumulate=True)
     for nb in NCHK:
         hi_t = torch.minimum(last_tile[tile_of[sl]], offs[tile_of[sl] + 1] - 1)
         ck = ((hi_t - idx_in_list[sl]).clamp(min=0) // nb)
@@ -136,6 +154,19 @@ for nb in NCHK:
     cg = chunk_cnt_g[nb].view(-1, NCHK[nb], 2, 2, 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(-1, NCHK[nb], 4, 4)
     print(f"batch {nb}: quadrant iterations today {int(chunk_q[nb].sum())}; 4-row scheme sum over (batch, wave) of max row: "
           f"{int(c.max(-1).values.sum())} (box), {int(cg.max(-1).values.sum())} (exact); per-wave barrier-max over waves (box): {int(c.max(-1).values.max(-1).values.sum() * 4)}")
+
+# ---- the forward's lock-step iterations with the block filter (D4GS_BLOCK_FILTER) ----
+for nb in FNB:
+    def rows(t, k):  # [tile, batch, block, 2] -> [tile, batch, quadrant-wave, row]
+        return t[..., k].view(-1, NCHF[nb], 2, 2, 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(-1, NCHF[nb], 4, 4)
+    for k, what in ((0, "whole lists"), (1, "up to the quadrant's last contributor")):
+        cb_, ce_ = rows(fwd_box[nb], k), rows(fwd_ell[nb], k)
+        passes = ((cb_.sum(-1) + 63) // 64).sum()
+        print(f"fwd batch {nb}, {what}: sum over (batch, wave) of max row: {int(cb_.max(-1).values.sum())} (box), "
+              f"{int(ce_.max(-1).values.sum())} (ellipse); listed pairs {int(cb_.sum())} -> {int(ce_.sum())}; "
+              f"filter passes of 64 listed pairs: {int(passes)}")
+print(f"bwd: of the {K_hits} quadrant replays, {K_fwd_bits_zero} have no block that survives the forward's filter "
+      f"({K_fwd_bits_zero / K_hits:.3f}; the kernel's own zero-by-geometry count above: {K_geo_zero})")
 
 import json
 import hashlib
