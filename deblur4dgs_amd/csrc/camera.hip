@@ -131,7 +131,23 @@ __device__ inline T taylor(T x, int kind) {
 }
 
 // pypose-style guarded coefficient: theta^2 > eps ? big(theta) : small(theta^2)
-#define D4GS_GUARDED(t2, th, BIG, SMALL) ((t2).v > 1e-12f ? ([&](Dual th) { return BIG; })(Sqrt(t2)) : ([&](Dual x) { return SMALL; })(t2))
+//
+// Two switch points.  GUARD_EPS = 1e-12 is pypose's and the oracle's, and it is right for so3_exp / so3_log, whose closed forms
+// (sin(th/2)/th, cos(th/2), atan(n/w)/n) do not cancel.  The coefficients of left_jacobian / left_jacobian_inv do:
+// (1 - cos th)/th^2, (th - sin th)/th^3 and (1 - th cos(th/2) / (2 sin(th/2)))/th^2 are each a difference of two nearly equal
+// numbers divided by a power of th.  With e the rounding of the larger operand, the coefficient is off by ~ e/th^2, and the dual
+// part of the quotient - a difference of two terms of size 1/th for a derivative whose true size is th/12 - by ~ e/th^3.  That
+// derivative reaches the Jacobian multiplied by |phi| |tau|, in the rotation-rows / d phi block, whose own size is ~ |tau1 - tau0|/8.
+//   fp64 (the oracle), e = 1e-16: at its guard th = 1e-6 the block is off by at most ~ 1e-16/th^2 |tau| = 1e-4 |tau| and 100 times less
+//     at th = 1e-5; measured over the test table 1e-5 of the block at worst (tests/camera_path_cases.py).  It may keep 1e-12.
+//   fp32 (here), e = 6e-8: 1 - cosf(th) is exactly 0 below th = 3e-4, and the block is off by ~ 6e-8/th^2 |tau| up to th = 2.5e-4
+//     (every |tau|-sized entry wrong by its own size and more) and still 1e-4 of itself at th = 2.5e-2: measured on the MI355X, 25 % to
+//     350 % of the block for head rotations of 2e-6 .. 1e-3, which the zero-initialised heads cross in the first thousands of steps.
+// So these three take their series up to th^2 = SERIES_T2 = 1e-2, with terms through x^3: the first term left out is x^4/3628800,
+// 6e-15 of c1 at the switch, and just above it the closed forms leave the block within 2e-5 of itself (DESIGN.md section 21 has the
+// block errors measured on both sides of the switch).
+constexpr float GUARD_EPS = 1e-12f, SERIES_T2 = 1e-2f;
+#define D4GS_GUARDED(t2, eps, th, BIG, SMALL) ((t2).v > (eps) ? ([&](Dual th) { return BIG; })(Sqrt(t2)) : ([&](Dual x) { return SMALL; })(t2))
 
 struct Q4 {
   V3<Dual> v;
@@ -140,14 +156,14 @@ struct Q4 {
 
 __device__ inline Q4 so3_exp(V3<Dual> phi) {
   Dual t2 = dot(phi, phi);
-  Dual im = D4GS_GUARDED(t2, th, Sin(0.5f * th) / th, 0.5f - x / 48.f + x * x / 3840.f);
-  Dual re = D4GS_GUARDED(t2, th, Cos(0.5f * th), 1.f - x / 8.f + x * x / 384.f);
+  Dual im = D4GS_GUARDED(t2, GUARD_EPS, th, Sin(0.5f * th) / th, 0.5f - x / 48.f + x * x / 3840.f);
+  Dual re = D4GS_GUARDED(t2, GUARD_EPS, th, Cos(0.5f * th), 1.f - x / 8.f + x * x / 384.f);
   return {{phi.x * im, phi.y * im, phi.z * im}, re};
 }
 __device__ inline V3<Dual> so3_log(Q4 q) {
   Dual n2 = dot(q.v, q.v);
   Dual w = q.w;
-  Dual f = D4GS_GUARDED(n2, n, 2.f * Atan(n / w) / n, 2.f / w - 2.f * x / (3.f * w * w * w));
+  Dual f = D4GS_GUARDED(n2, GUARD_EPS, n, 2.f * Atan(n / w) / n, 2.f / w - 2.f * x / (3.f * w * w * w));
   return {f * q.v.x, f * q.v.y, f * q.v.z};
 }
 __device__ inline Q4 so3_mul(Q4 p, Q4 q) {
@@ -160,14 +176,16 @@ __device__ inline Q4 so3_inv(Q4 q) { return {{-q.v.x, -q.v.y, -q.v.z}, q.w}; }
 __device__ inline M3<Dual> left_jacobian(V3<Dual> phi) {
   Dual t2 = dot(phi, phi);
   M3<Dual> K = skew(phi), K2 = matmul(K, K);
-  Dual c1 = D4GS_GUARDED(t2, th, (1.f - Cos(th)) / (th * th), 0.5f - x / 24.f);
-  Dual c2 = D4GS_GUARDED(t2, th, (th - Sin(th)) / (th * th * th), 1.f / 6.f - x / 120.f);
+  Dual c1 = D4GS_GUARDED(t2, SERIES_T2, th, (1.f - Cos(th)) / (th * th), 0.5f - x * (1.f / 24.f - x * (1.f / 720.f - x / 40320.f)));
+  Dual c2 = D4GS_GUARDED(t2, SERIES_T2, th, (th - Sin(th)) / (th * th * th),
+                         1.f / 6.f - x * (1.f / 120.f - x * (1.f / 5040.f - x / 362880.f)));
   return eye_plus(1.f, c1, K, c2, K2);
 }
 __device__ inline M3<Dual> left_jacobian_inv(V3<Dual> phi) {
   Dual t2 = dot(phi, phi);
   M3<Dual> K = skew(phi), K2 = matmul(K, K);
-  Dual c2 = D4GS_GUARDED(t2, th, (1.f - th * Cos(0.5f * th) / (2.f * Sin(0.5f * th))) / (th * th), 1.f / 12.f + x / 720.f);
+  Dual c2 = D4GS_GUARDED(t2, SERIES_T2, th, (1.f - th * Cos(0.5f * th) / (2.f * Sin(0.5f * th))) / (th * th),
+                         1.f / 12.f + x * (1.f / 720.f + x * (1.f / 30240.f + x / 1209600.f)));
   return eye_plus(1.f, mk(-0.5f), K, c2, K2);
 }
 
