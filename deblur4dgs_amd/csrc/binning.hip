@@ -34,11 +34,6 @@ struct EmitArgs {
   const uint64_t *tile_masks;  // D4GS_EXACT_TILES: per instance, the tiles of its rectangle that are binned (0: all of them); or NULL
 };
 
-// D4gsIsect.n_isect is a CAPACITY: the host may size the lists from a guess and look at the real count afterwards.
-__device__ __forceinline__ bool over_capacity(const int64_t *n_dev, int64_t cap, int64_t max_hint) {
-  return n_dev && (n_dev[0] > cap || (max_hint > 0 && n_dev[1] > max_hint));
-}
-
 // Slot assignment without per-intersection global atomics.  Block b takes 4096 instances of sub-sample b % S
 // (1024 lanes x 4, the chunks of k_count_tiles):
 //   1. histogram of the chunk's tile touches in LDS;
@@ -56,7 +51,7 @@ constexpr int EMIT_THREADS = 1024;
 template <int EMIT_PER_THREAD, int LZ>  // EMIT_PER_THREAD = d4gs_chunk_per_thread(dims), like k_count_tiles
 __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
   extern __shared__ int bins[];  // [tiles] (+ LZ: [tiles] pivots)
-  if (over_capacity(a.n_dev, a.cap, a.max_hint)) return;
+  if (lists_overflowed(a.n_dev, a.cap, a.max_hint)) return;
   constexpr bool LAZY = LZ != 0;
   const int tiles = a.tw * a.th, tid = threadIdx.x;
   const int s = blockIdx.x % a.d.S, chunk = blockIdx.x / a.d.S;
@@ -462,7 +457,7 @@ __device__ __forceinline__ void sort_list_lds(const SortArgs &a, uint64_t *key, 
 template <bool LONG>
 __global__ void __launch_bounds__(256) k_tile_sort_w(const SortArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint64_t wkeys[];  // LONG: 2 048 keys
-  if (over_capacity(a.n_dev, a.n_cap, a.max_hint)) return;  // (block-uniform)
+  if (lists_overflowed(a.n_dev, a.n_cap, a.max_hint)) return;  // (block-uniform)
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   int base = 0, n = 0;
@@ -487,7 +482,7 @@ __global__ void __launch_bounds__(256) k_tile_sort_w(const SortArgs a) {
 
 __global__ void __launch_bounds__(1024) k_tile_sort(const SortArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint64_t skeys[];
-  if (over_capacity(a.n_dev, a.n_cap, a.max_hint)) return;
+  if (lists_overflowed(a.n_dev, a.n_cap, a.max_hint)) return;
   const int t = blockIdx.x;
   int base = a.tile_offsets[t];
   int n = a.tile_offsets[t + 1] - base;

@@ -194,13 +194,25 @@ __device__ __forceinline__ void tile_rect(float mx, float my, int radius, int tw
   y1 = (int)fminf(fmaxf(ceilf(ty + tr), 0.f), (float)th);
 }
 
+// The alpha >= 1/255 threshold of every culling stage (tile rectangles, exact tiles, the composites' boxes and block filter): a pixel
+// can pass the rasterizer's alpha test only where sigma <= tau, tau = ln(255*opacity) (alpha = opacity*exp(-sigma) >= 1/255).  tau
+// carries a 1% + 0.02 margin so fp32 rounding of sigma / exp in the rasterizer can never admit a pixel outside it: this is the ONE
+// statement of the formula and its margins - "exact cull on == off" holds because every stage is at least this generous.
+// (The macro is the function's body and nothing else.  Two kernels expand it in place because the function would change their code
+// and no benchmark workload times every instantiation of them (profiles/refactor_composite_isa.txt).  The backward composite stages
+// its boxes under `fp contract(off)` and has always rounded the product and the sum separately, while the function, like every other
+// stage, fuses them: a contraction pragma is lexical, so only an expansion inside the kernel keeps the two roundings - either one is
+// within the margin.  And k_project_fwd's exact-tiles + antialiased instantiation, written as a call, no longer shares the product
+// 255 * opacity with tight_rect's and gains an instruction.)
+#define D4GS_ALPHA_TAU(opac_) (__logf(255.f * (opac_)) * 1.01f + 0.02f)
+__device__ __forceinline__ float d4gs_alpha_tau(float opac) { return D4GS_ALPHA_TAU(opac); }
+
 // D4GS_EXACT_CULL: shrink the gsplat tile rectangle to the tiles that contain a pixel centre inside the ellipse
-// sigma <= tau, tau = ln(255*opacity) (alpha = opacity*exp(-sigma) >= 1/255).  Half-extents of that ellipse are
-// sqrt(2 tau Sigma_xx), sqrt(2 tau Sigma_yy) with Sigma the blurred 2-D covariance.  tau carries a 1% + 0.02 margin
-// and the extents 1e-3 px so fp32 rounding of sigma / exp in the rasterizer can never admit a pixel outside it.
+// sigma <= tau (d4gs_alpha_tau).  Half-extents of that ellipse are sqrt(2 tau Sigma_xx), sqrt(2 tau Sigma_yy) with Sigma the
+// blurred 2-D covariance; they carry another 1e-3 px.
 __device__ __forceinline__ void tight_rect(float mx, float my, float opac, float cov_xx, float cov_yy, int &x0, int &y0,
                                            int &x1, int &y1) {
-  const float tau = __logf(255.f * opac) * 1.01f + 0.02f;
+  const float tau = d4gs_alpha_tau(opac);
   if (!(tau > 0.f)) {
     x1 = x0, y1 = y0;
     return;
@@ -448,7 +460,6 @@ __device__ __forceinline__ float4 stage_conic(float a, float b, float c, float w
 // nearest to that line's own minimiser, uc / vc = the rectangle's coordinate nearest to the centre; where the centre's coordinate is
 // inside the rectangle's range that line is no edge but still part of the rectangle, so the smaller of the two values is the
 // minimum either way (0 when the centre is inside).  Compared negated: a NaN keeps the pair.
-__device__ __forceinline__ float d4gs_alpha_tau(float opac) { return __logf(255.f * opac) * 1.01f + 0.02f; }
 __device__ __forceinline__ bool d4gs_block_filter_keep(float mx, float my, const float4 g1, float X0, float X1, float Y0, float Y1) {
 #pragma clang fp contract(off)
   const float U0 = X0 - mx, U1 = X1 - mx, V0 = Y0 - my, V1 = Y1 - my;
@@ -637,19 +648,12 @@ __device__ __forceinline__ float4 d4gs_unpack_box(uint2 p) {
 }
 
 
-// Dynamic-LDS padding that caps a kernel's residency at `q` workgroups per CU (160 KB of LDS per CU; allocation granule taken as
-// 1280 B): the composites are issue-bound at 8 workgroups (= 8 waves per SIMD), and a launch whose workgroup count is not a multiple
-// of 256 x 8 ends in a partial round that runs at a fraction of the chip's issue rate (cfg2: 4608 workgroups = 2.25 rounds of 2048;
-// the last 512 take 0.43 of a full round's time).  Capping at q = 6 makes the same launch exactly 3 full rounds of 1536.
-inline int d4gs_lds_pad_for_wgs_per_cu(const void *kernel, int q) {
-  if (q <= 0 || q >= 8) return 0;
-  hipFuncAttributes at;
-  if (hipFuncGetAttributes(&at, kernel) != hipSuccess) return 0;
-  const int lds_cu = 160 * 1024, granule = 1280;
-  const int need = ((lds_cu / (q + 1) + 1 + granule - 1) / granule) * granule;  // > LDS / (q + 1): q + 1 workgroups no longer fit
-  if ((long)need * q > lds_cu) return 0;
-  const int pad = need - (int)at.sharedSizeBytes;
-  return pad > 0 ? pad : 0;
+// D4gsIsect.n_isect is a CAPACITY: the host may size the lists from a guess and look at the real count afterwards (optimistic /
+// deferred sizing, engine.py).  n_dev = device {total, longest list}; when they exceed what the caller sized the lists for (cap,
+// max_hint) every stage that reads or writes the lists is a no-op - binning, the forward and the backward composite, the gather:
+// tile_offsets are computed from the TRUE counts and would index past the end of sorted_gid / isect_grad.
+__device__ __forceinline__ bool lists_overflowed(const int64_t *n_dev, int64_t cap, int64_t max_hint) {
+  return n_dev && (n_dev[0] > cap || (max_hint > 0 && n_dev[1] > max_hint));
 }
 
 #define D4GS_LAUNCH(name, kernel, grid, block, lds, stream, ...)            \

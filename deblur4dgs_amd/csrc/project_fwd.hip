@@ -269,7 +269,7 @@ k_project_fwd(const FwdArgs a) {
       if (total > 0) {  // (wave-uniform)
         xt_pre[tid] = inc - np;
         // conic of the BLURRED covariance = the geom record's; tau as tight_rect computes it (from the opacity the composite sees)
-        const float tau = __logf(255.f * (AA ? opeff : opac)) * 1.01f + 0.02f;
+        const float tau = D4GS_ALPHA_TAU(AA ? opeff : opac);
         xt_rec[tid][0] = make_float4(m2x, m2y, ca, cb);
         xt_rec[tid][1] = make_float4(cc, tau, __int_as_float(x0 | (y0 << 16)), __int_as_float(w));
         xt_mask[tid][0] = 0u, xt_mask[tid][1] = 0u;

@@ -20,7 +20,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "composite.h"
 
 namespace {
 
@@ -63,17 +63,27 @@ struct RasterBwdArgs {
 #define D4GS_TRACE_END(n_)
 #endif
 
-// The forward stage skips its work when the device-side intersection count exceeds what the caller sized the lists for
-// (optimistic / deferred sizing, engine.py).  The backward must not touch those lists either: tile_offsets are computed from
-// the TRUE counts and would index past the end of sorted_gid / isect_grad.
-__device__ __forceinline__ bool lists_overflowed(const int64_t *n_dev, int64_t cap, int64_t max_hint) {
-  return n_dev && (n_dev[0] > cap || (max_hint > 0 && n_dev[1] > max_hint));
-}
-
-
-__device__ __forceinline__ int xcd_remap_b(int b, int n_blocks) {
-  const int per = (n_blocks + 7) >> 3;
-  return (b & 7) * per + (b >> 3);
+// A pixel's prologue, from what was loaded - the forward's alpha `al` and final transmittance `Tfin`, the image gradient vo[] and the
+// alpha gradient `v_al` - to what the replay carries: vo[D] becomes the gradient of the RAW depth sum where the forward divided by
+// max(alpha, 1e-10) (a.ed; the division's other half goes to v_al), and the returned va = T_final (v_al - <background, vo>): both
+// terms of a splat's alpha gradient that do not depend on the splats behind it carry T_final * ra.
+// (No contraction, as in the product kernel's body.  Variant A is compiled with contraction and used to state this inline: through
+// this function its background dot rounds as the product's does.)
+template <int D, bool DEPTH>
+__device__ __forceinline__ float bwd_pixel_prologue(const RasterBwdArgs &a, size_t pix, float al, float Tfin, float v_al, float *vo) {
+#pragma clang fp contract(off)
+  if (DEPTH && a.ed) {  // out_d = raw_d / max(alpha, 1e-10)
+    const float den = fmaxf(al, 1e-10f);
+    const float vd = vo[D];
+    if (al >= 1e-10f) v_al -= vd * a.out[pix * (D + 1) + D] / den;  // raw_d / den^2 = out_d / den
+    vo[D] = vd / den;
+  }
+  float bgdot = 0.f;
+  if (a.background) {
+#pragma unroll
+    for (int c = 0; c < D; c++) bgdot += a.background[c] * vo[c];
+  }
+  return Tfin * (v_al - bgdot);
 }
 
 __device__ __forceinline__ int wave_max_i(int v) {
@@ -119,11 +129,8 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
   // >= 16 channels (the reference's 17-channel training renders): 4 waves per SIMD instead of 3 (round 4).  The kernel's time goes
   // with 1 / occupancy and its workgroup needed 50.4 KB of LDS and 140 VGPRs; an 8-hit `fac` tile (the MFMA's other 8 columns idle:
   // twice the matrix instructions per hit), the staged boxes as 4 x f16 and an even slab stride bring it to 40.6 KB / 113 VGPRs
-  // without scratch: refdefault's backward 1 066 -> 1 023 us, cfg2 with 17 channels 1 315 -> 1 258 (D4GS_BWD16_4W=0: the old shape).
-#ifndef D4GS_BWD16_4W
-#define D4GS_BWD16_4W 1
-#endif
-  constexpr bool W4 = D4GS_BWD16_4W && D >= 16;
+  // without scratch: refdefault's backward 1 066 -> 1 023 us, cfg2 with 17 channels 1 315 -> 1 258.
+  constexpr bool W4 = D >= 16;
   constexpr int NB = 64;  // splats per batch
   // With >= 16 colour channels the colour gradients V_c[j] = sum_p vo[c][p] * fac[p][j] of channels 0..15 leave the
   // VALU: they are a [16 ch x 64 px] x [64 px x 16 hits] product, A = this quadrant's image gradient (fixed for the
@@ -157,7 +164,7 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
   // over shader engines / CUs aliases with: measured, half of the CUs received only empty workgroups.)
   const int per_xcd = (n_tiles + 7) >> 3, bi = blockIdx.x >> 3;
   const int seg = SEG ? bi / per_xcd : 0;
-  const int t = SEG ? (blockIdx.x & 7) * per_xcd + (bi - seg * per_xcd) : xcd_remap_b(blockIdx.x, n_tiles);
+  const int t = SEG ? (blockIdx.x & 7) * per_xcd + (bi - seg * per_xcd) : xcd_remap(blockIdx.x, n_tiles);
   if (t >= n_tiles || seg >= D4GS_SEG_MAX) return;
   int start = a.tile_offsets[t], end = a.tile_offsets[t + 1];
   if constexpr (SEG) {  // from here on [start, end) is this workgroup's segment of the list
@@ -207,18 +214,7 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
       for (int c = 0; c < NCH; c++) vo[c] = vp[c];
       v_al = a.v_alphas ? a.v_alphas[pix] : 0.f;
     }
-    if (DEPTH && a.ed) {
-      const float den = fmaxf(al, 1e-10f);
-      const float vd = vo[D];
-      if (al >= 1e-10f) v_al -= vd * a.out[pix * NCH + D] / den;
-      vo[D] = vd / den;
-    }
-    float bgdot = 0.f;
-    if (a.background) {
-#pragma unroll
-      for (int c = 0; c < D; c++) bgdot += a.background[c] * vo[c];
-    }
-    va = Tfin * (v_al - bgdot);
+    va = bwd_pixel_prologue<D, DEPTH>(a, pix, al, Tfin, v_al, vo);
     T = Tfin;
     if constexpr (SEG) {
       if (last >= end) {  // contributors behind this segment: take over at its back boundary (slot seg + 1; slot 0 = final state)
@@ -236,9 +232,6 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
   // ... and of each of the quadrant's four 4x4 blocks (round 5): a staged splat is replayed only if its box reaches a block that still
   // has a contributor at or behind it.  The replays this prunes lit no lane (the pixels inside the box were all saturated in front
   // of the splat, the others fail the alpha test), so the rows are the same bit for bit.
-#ifndef D4GS_BWD_BLOCK_LAST
-#define D4GS_BWD_BLOCK_LAST 1
-#endif
   int wq = whi;  // after xor 1, 2 (x within the block) and 8, 16 (y within the block): the lane's own block
 #pragma unroll
   for (int o = 1; o <= 16; o = o == 2 ? 8 : o << 1) wq = max(wq, __shfl_xor(wq, o));
@@ -316,14 +309,8 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
         const float4 q0 = gp[0], q1 = gp[1];
         sg0[tid] = q0;
         sg1[tid] = stage_conic(q1.x, q1.y, q1.z, __builtin_amdgcn_rcpf(q0.z));
-        const float tau = __logf(255.f * q0.z) * 1.01f + 0.02f;
-        const float det = q1.x * q1.z - q1.y * q1.y;
-        const float idet = 1.f / det;
-        float ex = -1.f, ey = -1.f;
-        if (tau > 0.f && det > 0.f) {
-          ex = sqrtf(2.f * tau * q1.z * idet) + 1e-3f;
-          ey = sqrtf(2.f * tau * q1.x * idet) + 1e-3f;
-        }
+        const float tau = D4GS_ALPHA_TAU(q0.z);
+        D4GS_TIGHT_EXTENTS(ex, ey, tau, q1.x, q1.y, q1.z)
         if constexpr (W4)
           sbox[tid] = ex < 0.f ? d4gs_pack_box(1e30f, -1e30f, 1e30f, -1e30f)
                                : d4gs_pack_box(q0.x - ex - tx0f, q0.x + ex - tx0f, q0.y - ey - ty0f, q0.y + ey - ty0f);
@@ -342,14 +329,8 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
         }
       }
     }
-#ifndef D4GS_BWD_ZERO128
-#define D4GS_BWD_ZERO128 1
-#endif
-    if constexpr (D4GS_BWD_ZERO128) {  // 16 bytes per store (4 * NB * RP floats = 64 RP float4)
-      for (int z = tid; z < NB * RP; z += 256) reinterpret_cast<float4 *>(sgrad)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-      for (int z = tid; z < 4 * NB * RP; z += 256) sgrad[z] = 0.f;
-    }
+    // 16 bytes per store (4 * NB * RP floats = 64 RP float4)
+    for (int z = tid; z < NB * RP; z += 256) reinterpret_cast<float4 *>(sgrad)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
     const int nb = min(NB, bh - start + 1);
 #pragma unroll
@@ -360,28 +341,21 @@ __device__ __forceinline__ void raster_bwd_q_body(const RasterBwdArgs &a) {
         float4 bx;
         if constexpr (W4) bx = d4gs_unpack_box(sbox[jj]);
         else bx = sbox[jj];
-        if constexpr (D4GS_BWD_BLOCK_LAST) {
-          const int cur = bh - jj;
-          const bool X0 = (bx.x <= qlx + 3.f) && (bx.y >= qlx), X1 = (bx.x <= qhx) && (bx.y >= qlx + 4.f);
-          const bool Y0 = (bx.z <= qly + 3.f) && (bx.w >= qly), Y1 = (bx.z <= qhy) && (bx.w >= qly + 4.f);
-          hit = (X0 && Y0 && cur <= wq0) || (X1 && Y0 && cur <= wq1) || (X0 && Y1 && cur <= wq2) || (X1 && Y1 && cur <= wq3);
-        } else {
-          hit = (bx.x <= qhx) && (bx.y >= qlx) && (bx.z <= qhy) && (bx.w >= qly);
-        }
+        const int cur = bh - jj;
+        const bool X0 = (bx.x <= qlx + 3.f) && (bx.y >= qlx), X1 = (bx.x <= qhx) && (bx.y >= qlx + 4.f);
+        const bool Y0 = (bx.z <= qly + 3.f) && (bx.w >= qly), Y1 = (bx.z <= qhy) && (bx.w >= qly + 4.f);
+        hit = (X0 && Y0 && cur <= wq0) || (X1 && Y0 && cur <= wq1) || (X0 && Y1 && cur <= wq2) || (X1 && Y1 && cur <= wq3);
       }
       unsigned long long m = __ballot(hit);
       while (m) {
         const int j = k * 64 + (__ffsll((long long)m) - 1);
         m &= m - 1;
         const int cur = bh - j;
-#ifndef D4GS_BWD_PIN_ADDR
-#define D4GS_BWD_PIN_ADDR 1
-#endif
         // narrow kernels: the staged records' byte offset in ONE pinned VGPR for all three reads (the compiler re-materialised it from
         // the scalar for the read behind the early-out): 627 -> 619 us on cfg2.  (The 17-channel kernel got SLOWER with it, and with g0
         // as one 16-byte read instead of 12 + 4: 888 -> 926 us on refdefault - it keeps the plain indexing.)
         int jb = j * 16;
-        if constexpr (D4GS_BWD_PIN_ADDR && MC == 0) asm volatile("" : "+v"(jb));
+        if constexpr (MC == 0) asm volatile("" : "+v"(jb));
         const float4 g0 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sg0) + jb);
         const float4 g1 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sg1) + jb);
         const float dx = g0.x - pxf, dy = g0.y - pyf;
@@ -497,11 +471,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
   raster_bwd_q_body<D, DEPTH, false, ABS>(a);
 }
 template <int D, bool DEPTH, bool ABS = false>
-__global__ void __launch_bounds__(256)
-#if defined(D4GS_BWD16_4W) && D4GS_BWD16_4W
-__attribute__((amdgpu_waves_per_eu(D >= 16 ? 4 : 1, D >= 16 ? 4 : 10)))
-#endif
-k_raster_bwd_q(const RasterBwdArgs a) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D >= 16 ? 4 : 1, D >= 16 ? 4 : 10))) k_raster_bwd_q(const RasterBwdArgs a) {
   raster_bwd_q_body<D, DEPTH, false, ABS>(a);
 }
 // the same two over (tile, depth segment) workgroups
@@ -901,14 +871,8 @@ int launch_bwd(RasterBwdArgs &a, GatherArgs &ga, const GatherAA &gaa, int64_t n_
       if constexpr (D <= 5) D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_qs8<D, DEPTH, ABS>), dim3(sblocks), dim3(256), 0, stream, a);
       else D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_qs<D, DEPTH, ABS>), dim3(sblocks), dim3(256), 0, stream, a);
     } else if (n_isect > 0) {
-      static const int q_env = getenv("D4GS_BWD_Q") ? atoi(getenv("D4GS_BWD_Q")) : 0;  // A/B hook: workgroups per CU
-      if constexpr (D <= 5) {
-        const int pad = d4gs_lds_pad_for_wgs_per_cu((const void *)k_raster_bwd_q8<D, DEPTH, ABS>, q_env);
-        D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_q8<D, DEPTH, ABS>), dim3(blocks), dim3(256), pad, stream, a);
-      } else {
-        const int pad = d4gs_lds_pad_for_wgs_per_cu((const void *)k_raster_bwd_q<D, DEPTH, ABS>, q_env);
-        D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_q<D, DEPTH, ABS>), dim3(blocks), dim3(256), pad, stream, a);
-      }
+      if constexpr (D <= 5) D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_q8<D, DEPTH, ABS>), dim3(blocks), dim3(256), 0, stream, a);
+      else D4GS_LAUNCH("k_raster_bwd_q", (k_raster_bwd_q<D, DEPTH, ABS>), dim3(blocks), dim3(256), 0, stream, a);
     }
   }
   int rc = d4gs_check_launch("k_raster_bwd");

@@ -18,7 +18,7 @@
 // splats) land on the same XCD so the gathered records hit that XCD's L2.
 #include <stdlib.h>
 
-#include "common.h"
+#include "composite.h"
 
 namespace {
 
@@ -56,11 +56,6 @@ struct RasterFwdArgs {
 #define D4GS_TCLK(v_)
 #define D4GS_TADD(acc_, a_, b_)
 #endif
-
-__device__ __forceinline__ int xcd_remap(int b, int n_blocks) {
-  const int per = (n_blocks + 7) >> 3;
-  return (b & 7) * per + (b >> 3);
-}
 
 #ifdef D4GS_VARIANTS
 #include "variants/raster_fwd_variants.inc"
@@ -120,22 +115,15 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
   // per element either way.  Lane i of a quad reads float4 i of the staged record (channels 4 i .. 4 i + 3) - ONE 16-byte LDS read
   // instead of four (the 64-byte record read by every lane was 2/3 of the step's LDS return traffic) - and MFMA m takes its
   // component m: accm[m][i] = channel 4 i + m.
-#ifndef D4GS_FWD_MFMA
-#define D4GS_FWD_MFMA 1
-#endif
-  constexpr bool MF = D4GS_FWD_MFMA && D == 16;
-  // One-record colours, unsegmented lists (round 5): slot 0 of every batch is a NULL record (opacity 0, empty box) and a batch stages
+  constexpr bool MF = D == 16;
+  // One colour record, none (DV = 0: the depth-only kernels), or the matrix-pipe accumulators (round 6): the four-steps-per-read loop
+  // below; other wide records keep the one-byte loop (registers).
+  constexpr bool NARROW = DV <= 1 || D == 16;
+  // The narrow loop's kernels, unsegmented lists (round 5): slot 0 of every batch is a NULL record (opacity 0, empty box) and a batch stages
   // FB - 1 splats into slots 1 .. FB - 1.  The rows' lists start out as zeros, so the steps the lock-step loop runs past a row's own
   // count composite the null record - no per-step "is this row still active" compare.  (Segment boundaries are multiples of the
   // batch size: the segmented variants keep FB splats per batch and the compare.)
-#ifndef D4GS_FWD_NULL0
-#define D4GS_FWD_NULL0 1
-#endif
-#ifndef D4GS_FWD_WIDE4
-#define D4GS_FWD_WIDE4 1  // the matrix-pipe kernel also takes the four-steps-per-read loop and the null record (round 6)
-#endif
-  constexpr bool LIKE_NARROW = DV <= 1 || (MF && D4GS_FWD_WIDE4);  // (DV = 0: the depth-only kernels, no colour record at all)
-  constexpr bool NULL0 = D4GS_FWD_NULL0 && LIKE_NARROW && !SEG;
+  constexpr bool NULL0 = NARROW && !SEG;
   constexpr int FBE = NULL0 ? FB - 1 : FB;  // splats per batch
   __shared__ float4 sg0[FB];
   __shared__ float4 sg1[FB];
@@ -148,7 +136,7 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
   unsigned long long _ts = 0, _tl = 0, _tc = 0, _ti = 0;
   const unsigned long long _c0 = __builtin_amdgcn_s_memtime();  // shader clock (wall_clock64 = the constant 100 MHz one)
 #endif
-  if (a.n_dev && (a.n_dev[0] > a.cap || (a.max_hint > 0 && a.n_dev[1] > a.max_hint))) return;
+  if (lists_overflowed(a.n_dev, a.cap, a.max_hint)) return;
   const int n_tiles_s = a.tw * a.th;
   const int n_tiles = a.S * n_tiles_s;
   const int t = xcd_remap(blockIdx.x, n_tiles);
@@ -228,13 +216,7 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
       sg0[tid] = q0;
       const float tau = d4gs_alpha_tau(q0.z);
       sg1[tid] = stage_conic(q1.x, q1.y, q1.z, tau * 1.4426950408889634f);  // (w: the block filter's threshold; splat_sigma2 does not read it)
-      const float det = q1.x * q1.z - q1.y * q1.y;
-      const float idet = 1.f / det;
-      float ex = -1.f, ey = -1.f;
-      if (tau > 0.f && det > 0.f) {
-        ex = sqrtf(2.f * tau * q1.z * idet) + 1e-3f;
-        ey = sqrtf(2.f * tau * q1.x * idet) + 1e-3f;
-      }
+      D4GS_TIGHT_EXTENTS(ex, ey, tau, q1.x, q1.y, q1.z)
       sbox[tid] = ex < 0.f ? BoxT<PB>::pack(1e30f, -1e30f, 1e30f, -1e30f) : BoxT<PB>::pack(q0.x - ex - tx0f, q0.x + ex - tx0f, q0.y - ey - ty0f, q0.y + ey - ty0f);
       const float4 *cp = reinterpret_cast<const float4 *>(a.ctab + (size_t)gid * DP);
 #pragma unroll
@@ -252,7 +234,6 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
     // The wave's four lists start out as zeros (one 16-byte store per lane and batch): the composite loop reads list bytes past a
     // row's count (no divergent branch in it) and takes them as they are - staged splat 0 exists in every batch, a stale index could
     // point at a never-staged record (NaN * 0) - instead of replacing them lane by lane in every step.
-    constexpr bool NARROW = LIKE_NARROW;  // one colour record (or the matrix-pipe accumulators): the four-steps-per-read loop below; other wide records keep the one-byte loop (regs)
     if constexpr (NARROW) {
       if (lane * 16 < 4 * FB) reinterpret_cast<uint4 *>(wlist)[lane] = make_uint4(0u, 0u, 0u, 0u);
       __builtin_amdgcn_wave_barrier();
@@ -355,10 +336,7 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
       T = valid ? nT : T;
       last16 = valid ? j16 : last16;
     };
-#ifndef D4GS_FWD_LIST4
-#define D4GS_FWD_LIST4 1
-#endif
-    if constexpr (D4GS_FWD_LIST4 && NARROW) {
+    if constexpr (NARROW) {
       // Four list positions per LDS read (the rows' lists start on 4-byte boundaries, FB is a multiple of 4): one address add and one read
       // per four steps; up to three steps past the longest list run with no row active.  Measured against the one-byte loop (cfg2,
       // profiles/r05_ab_fwd_list4.txt): 267 -> 238 us; with wide records the four unrolled steps cost the occupancy (17 channels:
@@ -483,15 +461,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
 }
 // (D = 16, the matrix-pipe accumulators with the four-steps-per-read loop: asked for 6 waves per SIMD the kernel fits 76 VGPRs without
 // scratch; left alone the compiler takes 96 + 16 -> 4 waves)
-#ifndef D4GS_FWD_WIDE_WAVES
-#define D4GS_FWD_WIDE_WAVES 6
-#endif
 template <int D, bool DEPTH>
-__global__ void __launch_bounds__(256)
-#if D4GS_FWD_WIDE_WAVES > 0
-__attribute__((amdgpu_waves_per_eu(D == 16 ? D4GS_FWD_WIDE_WAVES : 1, D == 16 ? D4GS_FWD_WIDE_WAVES : 10)))
-#endif
-k_raster_fwd_r(const RasterFwdArgs a) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 16 ? 6 : 1, D == 16 ? 6 : 10))) k_raster_fwd_r(const RasterFwdArgs a) {
   raster_fwd_r_body<D, DEPTH>(a);
 }
 // the same two, also storing the segment-boundary states (few-tile launches; the kernels above stay as they are)
@@ -500,11 +471,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
   raster_fwd_r_body<D, DEPTH, true>(a);
 }
 template <int D, bool DEPTH>
-__global__ void __launch_bounds__(256)
-#if D4GS_FWD_WIDE_WAVES > 0
-__attribute__((amdgpu_waves_per_eu(D == 16 ? D4GS_FWD_WIDE_WAVES : 1, D == 16 ? D4GS_FWD_WIDE_WAVES : 10)))
-#endif
-k_raster_fwd_rs(const RasterFwdArgs a) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 16 ? 6 : 1, D == 16 ? 6 : 10))) k_raster_fwd_rs(const RasterFwdArgs a) {
   raster_fwd_r_body<D, DEPTH, true>(a);
 }
 
@@ -531,14 +498,8 @@ int launch_fwd(const RasterFwdArgs &a, hipStream_t stream) {
     else D4GS_LAUNCH("k_raster_fwd_r", (k_raster_fwd_rs<D, DEPTH>), dim3(blocks), dim3(256), 0, stream, a);
     return d4gs_check_launch("k_raster_fwd_r");
   }
-  static const int q_env = getenv("D4GS_FWD_Q") ? atoi(getenv("D4GS_FWD_Q")) : 0;  // A/B hook: workgroups per CU
-  if constexpr (D <= 4) {
-    const int pad = d4gs_lds_pad_for_wgs_per_cu((const void *)k_raster_fwd_r8<D, DEPTH>, q_env);
-    D4GS_LAUNCH("k_raster_fwd_r", (k_raster_fwd_r8<D, DEPTH>), dim3(blocks), dim3(256), pad, stream, a);
-  } else {
-    const int pad = d4gs_lds_pad_for_wgs_per_cu((const void *)k_raster_fwd_r<D, DEPTH>, q_env);
-    D4GS_LAUNCH("k_raster_fwd_r", (k_raster_fwd_r<D, DEPTH>), dim3(blocks), dim3(256), pad, stream, a);
-  }
+  if constexpr (D <= 4) D4GS_LAUNCH("k_raster_fwd_r", (k_raster_fwd_r8<D, DEPTH>), dim3(blocks), dim3(256), 0, stream, a);
+  else D4GS_LAUNCH("k_raster_fwd_r", (k_raster_fwd_r<D, DEPTH>), dim3(blocks), dim3(256), 0, stream, a);
   return d4gs_check_launch("k_raster_fwd_r");
 }
 

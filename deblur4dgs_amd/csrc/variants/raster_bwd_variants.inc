@@ -17,7 +17,7 @@ __global__ void __launch_bounds__(64) k_raster_bwd(const RasterBwdArgs a) {
   if (lists_overflowed(a.n_dev, a.cap, a.max_hint)) return;
   const int n_tiles_s = a.tw * a.th;
   const int n_tiles = a.S * n_tiles_s;
-  const int t = xcd_remap_b(blockIdx.x, n_tiles);
+  const int t = xcd_remap(blockIdx.x, n_tiles);
   if (t >= n_tiles) return;
   const int start = a.tile_offsets[t], end = a.tile_offsets[t + 1];
   if (end <= start) return;
@@ -49,19 +49,7 @@ __global__ void __launch_bounds__(64) k_raster_bwd(const RasterBwdArgs a) {
       const float *vp = a.v_out + pix * NCH;
 #pragma unroll
       for (int c = 0; c < NCH; c++) vo[p][c] = vp[c];
-      float v_al = a.v_alphas ? a.v_alphas[pix] : 0.f;
-      if (DEPTH && a.ed) {  // out_d = raw_d / max(alpha, 1e-10)
-        const float den = fmaxf(al, 1e-10f);
-        const float vd = vo[p][D];
-        if (al >= 1e-10f) v_al -= vd * a.out[pix * NCH + D] / den;  // raw_d / den^2 = out_d / den
-        vo[p][D] = vd / den;
-      }
-      float bgdot = 0.f;
-      if (a.background) {
-#pragma unroll
-        for (int c = 0; c < D; c++) bgdot += a.background[c] * vo[p][c];
-      }
-      va[p] = Tfin[p] * (v_al - bgdot);  // both terms carry T_final * ra
+      va[p] = bwd_pixel_prologue<D, DEPTH>(a, pix, al, Tfin[p], a.v_alphas ? a.v_alphas[pix] : 0.f, vo[p]);
       hi = max(hi, last[p]);
     }
     T[p] = Tfin[p];
@@ -202,7 +190,7 @@ __global__ void __launch_bounds__(256) k_raster_bwd_m(const RasterBwdArgs a) {
   if (lists_overflowed(a.n_dev, a.cap, a.max_hint)) return;
   const int n_tiles_s = a.tw * a.th;
   const int n_tiles = a.S * n_tiles_s;
-  const int t = xcd_remap_b(blockIdx.x, n_tiles);
+  const int t = xcd_remap(blockIdx.x, n_tiles);
   if (t >= n_tiles) return;
   const int start = a.tile_offsets[t], end = a.tile_offsets[t + 1];
   if (end <= start) return;
@@ -228,19 +216,7 @@ __global__ void __launch_bounds__(256) k_raster_bwd_m(const RasterBwdArgs a) {
     const float *vp = a.v_out + pix * NCH;
 #pragma unroll
     for (int c = 0; c < NCH; c++) vo[c] = vp[c];
-    float v_al = a.v_alphas ? a.v_alphas[pix] : 0.f;
-    if (DEPTH && a.ed) {
-      const float den = fmaxf(al, 1e-10f);
-      const float vd = vo[D];
-      if (al >= 1e-10f) v_al -= vd * a.out[pix * NCH + D] / den;
-      vo[D] = vd / den;
-    }
-    float bgdot = 0.f;
-    if (a.background) {
-#pragma unroll
-      for (int c = 0; c < D; c++) bgdot += a.background[c] * vo[c];
-    }
-    va = Tfin * (v_al - bgdot);
+    va = bwd_pixel_prologue<D, DEPTH>(a, pix, al, Tfin, a.v_alphas ? a.v_alphas[pix] : 0.f, vo);
     T = Tfin;
   }
 #pragma unroll
@@ -350,14 +326,8 @@ __global__ void __launch_bounds__(256) k_raster_bwd_m(const RasterBwdArgs a) {
         const float4 q0 = gp[0], q1 = gp[1];
         sg0[tid] = q0;
         sg1[tid] = stage_conic(q1.x, q1.y, q1.z, __builtin_amdgcn_rcpf(q0.z));
-        const float tau = __logf(255.f * q0.z) * 1.01f + 0.02f;
-        const float det = q1.x * q1.z - q1.y * q1.y;
-        const float idet = 1.f / det;
-        float ex = -1.f, ey = -1.f;
-        if (tau > 0.f && det > 0.f) {
-          ex = sqrtf(2.f * tau * q1.z * idet) + 1e-3f;
-          ey = sqrtf(2.f * tau * q1.x * idet) + 1e-3f;
-        }
+        const float tau = D4GS_ALPHA_TAU(q0.z);
+        D4GS_TIGHT_EXTENTS(ex, ey, tau, q1.x, q1.y, q1.z)
         sbox[tid] = ex < 0.f ? make_float4(1e30f, -1e30f, 1e30f, -1e30f)
                              : make_float4(q0.x - ex, q0.x + ex, q0.y - ey, q0.y + ey);
         const float4 *cp = reinterpret_cast<const float4 *>(a.ctab + (size_t)gid * DP);

@@ -1,6 +1,54 @@
 // Non-default forward composites, compiled only with -DD4GS_VARIANTS (tests/libd4gs_variants.so): kept as A/B references -
 // `test_forward_variants_bitwise_equal` checks them bit for bit against the shipped k_raster_fwd_r.  Included inside
 // raster_fwd.hip's anonymous namespace.
+// ---- what variants A and B share: the per-pair arithmetic and the pixel write-out, in the product kernel's operation order (so the
+// three stay bit-identical).  How pixels map to lanes and which pairs are looked at is each variant's own.  The product kernel
+// (raster_fwd_r_body) keeps its own statement of these in its two loops: every shared form tried changed the code of instantiations
+// that no benchmark workload times (profiles/refactor_composite_isa.txt). ----
+// alpha of staged splat (g0 = centre, opacity, depth; g1 = stage_conic) at pixel centre (pxf, pyf) and the transmittance behind it.
+// The pair counts iff sigma >= 0 and alpha >= 1/255; it saturates the pixel (and is NOT composited) iff nT <= 1e-4.
+__device__ __forceinline__ void fwd_pair(const float4 g0, const float4 g1, float pxf, float pyf, float T, float &sigma, float &alpha, float &nT) {
+#pragma clang fp contract(off)
+  const float dx = g0.x - pxf, dy = g0.y - pyf;
+  sigma = splat_sigma2(g1, dx, dy);  // sigma * log2(e)
+  alpha = fminf(0.999f, g0.z * __builtin_amdgcn_exp2f(-sigma));
+  nT = T * (1.f - alpha);
+}
+// A pair's effect on its pixel once `valid` is decided (it counts, the pixel was not saturated and does not saturate with it):
+// acc[c] = fma(colour[c], vis, acc[c]) over the D channels of the staged colour record `rec` ((D + 3) / 4 float4) and the depth
+// channel, vis = alpha T (0 for an invalid pair), the new transmittance, and `at` as the pixel's last contributor.
+template <int D, bool DEPTH>
+__device__ __forceinline__ void fwd_commit(bool valid, float alpha, float nT, const float4 *rec, float depth, int at, float &T, int &last, float *acc) {
+#pragma clang fp contract(off)
+  const float vis = valid ? alpha * T : 0.f;
+#pragma unroll
+  for (int v = 0; v < (D + 3) / 4; v++) {
+    const float4 c4 = rec[v];
+    if (v * 4 < D) acc[v * 4] = __builtin_fmaf(c4.x, vis, acc[v * 4]);
+    if (v * 4 + 1 < D) acc[v * 4 + 1] = __builtin_fmaf(c4.y, vis, acc[v * 4 + 1]);
+    if (v * 4 + 2 < D) acc[v * 4 + 2] = __builtin_fmaf(c4.z, vis, acc[v * 4 + 2]);
+    if (v * 4 + 3 < D) acc[v * 4 + 3] = __builtin_fmaf(c4.w, vis, acc[v * 4 + 3]);
+  }
+  if (DEPTH) acc[D] = __builtin_fmaf(depth, vis, acc[D]);
+  T = valid ? nT : T;
+  last = valid ? at : last;
+}
+// The pixel's outputs: alpha, final transmittance, last contributor (list index), the channels over the background, and the depth
+// channel - divided by max(alpha, 1e-10) for the expected depth (a.ed).
+template <int D, bool DEPTH>
+__device__ __forceinline__ void fwd_write_pixel(const RasterFwdArgs &a, int s, int x, int y, float T, int last, const float *acc) {
+#pragma clang fp contract(off)
+  const size_t pix = ((size_t)s * a.height + y) * a.width + x;
+  const float al = 1.f - T;
+  a.alphas[pix] = al;
+  a.final_T[pix] = T;
+  a.last_ids[pix] = last;
+  float *o = a.out + pix * (D + (DEPTH ? 1 : 0));
+#pragma unroll
+  for (int c = 0; c < D; c++) o[c] = acc[c] + (a.background ? T * a.background[c] : 0.f);
+  if (DEPTH) o[D] = a.ed ? acc[D] / fmaxf(al, 1e-10f) : acc[D];
+}
+
 // Variant A: one wave64 per 16x16 tile, 2x2 pixels per lane.
 template <int D, bool DEPTH>
 __global__ void __launch_bounds__(64) k_raster_fwd(const RasterFwdArgs a) {
@@ -12,7 +60,7 @@ __global__ void __launch_bounds__(64) k_raster_fwd(const RasterFwdArgs a) {
   __shared__ float4 sg1[64];
   __shared__ float4 scol[64 * DV];
 
-  if (a.n_dev && (a.n_dev[0] > a.cap || (a.max_hint > 0 && a.n_dev[1] > a.max_hint))) return;
+  if (lists_overflowed(a.n_dev, a.cap, a.max_hint)) return;
   const int n_tiles_s = a.tw * a.th;
   const int n_tiles = a.S * n_tiles_s;
   const int t = xcd_remap(blockIdx.x, n_tiles);
@@ -58,28 +106,15 @@ __global__ void __launch_bounds__(64) k_raster_fwd(const RasterFwdArgs a) {
     for (int j = 0; j < nb; j++) {
       if ((j & 15) == 0 && j && __all(done[0] && done[1] && done[2] && done[3])) break;
       const float4 g0 = sg0[j], g1 = sg1[j];
-      float col[DP];
-#pragma unroll
-      for (int v = 0; v < DV; v++) {
-        const float4 c4 = scol[j * DV + v];
-        col[v * 4] = c4.x, col[v * 4 + 1] = c4.y, col[v * 4 + 2] = c4.z, col[v * 4 + 3] = c4.w;
-      }
 #pragma unroll
       for (int p = 0; p < 4; p++) {
-        const float dx = g0.x - pxf[p], dy = g0.y - pyf[p];
-        const float sigma = splat_sigma2(g1, dx, dy);  // sigma * log2(e)
-        const float alpha = fminf(0.999f, g0.z * __builtin_amdgcn_exp2f(-sigma));
+        float sigma, alpha, nT;
+        fwd_pair(g0, g1, pxf[p], pyf[p], T[p], sigma, alpha, nT);
         bool valid = !done[p] && (sigma >= 0.f) && (alpha >= (1.f / 255.f));
-        const float nT = T[p] * (1.f - alpha);
         const bool stop = valid && (nT <= 1e-4f);
         done[p] = done[p] || stop;
         valid = valid && !stop;
-        const float vis = valid ? alpha * T[p] : 0.f;
-#pragma unroll
-        for (int c = 0; c < D; c++) acc[p][c] = __builtin_fmaf(col[c], vis, acc[p][c]);
-        if (DEPTH) acc[p][D] = __builtin_fmaf(g0.w, vis, acc[p][D]);
-        T[p] = valid ? nT : T[p];
-        last[p] = valid ? (b + j) : last[p];
+        fwd_commit<D, DEPTH>(valid, alpha, nT, scol + j * DV, g0.w, b + j, T[p], last[p], acc[p]);
       }
     }
   }
@@ -87,17 +122,7 @@ __global__ void __launch_bounds__(64) k_raster_fwd(const RasterFwdArgs a) {
 #pragma unroll
   for (int p = 0; p < 4; p++) {
     const int x = x0 + (p & 1), y = y0 + (p >> 1);
-    if (x < a.width && y < a.height) {
-      const size_t pix = ((size_t)s * a.height + y) * a.width + x;
-      const float al = 1.f - T[p];
-      a.alphas[pix] = al;
-      a.final_T[pix] = T[p];
-      a.last_ids[pix] = last[p];
-      float *o = a.out + pix * NCH;
-#pragma unroll
-      for (int c = 0; c < D; c++) o[c] = acc[p][c] + (a.background ? T[p] * a.background[c] : 0.f);
-      if (DEPTH) o[D] = a.ed ? acc[p][D] / fmaxf(al, 1e-10f) : acc[p][D];
-    }
+    if (x < a.width && y < a.height) fwd_write_pixel<D, DEPTH>(a, s, x, y, T[p], last[p], acc[p]);
   }
 }
 
@@ -121,7 +146,7 @@ __global__ void __launch_bounds__(256) k_raster_fwd_q(const RasterFwdArgs a) {
   __shared__ float4 sbox[FB];
   __shared__ float4 scol[FB * DV];
 
-  if (a.n_dev && (a.n_dev[0] > a.cap || (a.max_hint > 0 && a.n_dev[1] > a.max_hint))) return;
+  if (lists_overflowed(a.n_dev, a.cap, a.max_hint)) return;
   const int n_tiles_s = a.tw * a.th;
   const int n_tiles = a.S * n_tiles_s;
   const int t = xcd_remap(blockIdx.x, n_tiles);
@@ -153,15 +178,8 @@ __global__ void __launch_bounds__(256) k_raster_fwd_q(const RasterFwdArgs a) {
       const float4 q0 = gp[0], q1 = gp[1];
       sg0[tid] = q0;
       sg1[tid] = stage_conic(q1.x, q1.y, q1.z, 0.f);
-      // tight box: sigma <= tau, tau = ln(255 opacity) (+ margins); Sigma = conic^-1
-      const float tau = __logf(255.f * q0.z) * 1.01f + 0.02f;
-      const float det = q1.x * q1.z - q1.y * q1.y;
-      const float idet = 1.f / det;
-      float ex = -1.f, ey = -1.f;
-      if (tau > 0.f && det > 0.f) {
-        ex = sqrtf(2.f * tau * q1.z * idet) + 1e-3f;
-        ey = sqrtf(2.f * tau * q1.x * idet) + 1e-3f;
-      }
+      const float tau = D4GS_ALPHA_TAU(q0.z);
+      D4GS_TIGHT_EXTENTS(ex, ey, tau, q1.x, q1.y, q1.z)
       sbox[tid] = ex < 0.f ? make_float4(1e30f, -1e30f, 1e30f, -1e30f) : make_float4(q0.x - ex, q0.x + ex, q0.y - ey, q0.y + ey);
       const float4 *cp = reinterpret_cast<const float4 *>(a.ctab + (size_t)gid * DP);
 #pragma unroll
@@ -189,26 +207,13 @@ __global__ void __launch_bounds__(256) k_raster_fwd_q(const RasterFwdArgs a) {
         const int j = k * 64 + (__ffsll((long long)m) - 1);
         m &= m - 1;
         const float4 g0 = sg0[j], g1 = sg1[j];
-        const float dx = g0.x - pxf, dy = g0.y - pyf;
-        const float sigma = splat_sigma2(g1, dx, dy);  // sigma * log2(e)
-        const float alpha = fminf(0.999f, g0.z * __builtin_amdgcn_exp2f(-sigma));
+        float sigma, alpha, nT;
+        fwd_pair(g0, g1, pxf, pyf, T, sigma, alpha, nT);
         bool valid = !done && (sigma >= 0.f) && (alpha >= (1.f / 255.f));
-        const float nT = T * (1.f - alpha);
         const bool stop = valid && (nT <= 1e-4f);
         done = done || stop;
         valid = valid && !stop;
-        const float vis = valid ? alpha * T : 0.f;
-#pragma unroll
-        for (int v = 0; v < DV; v++) {
-          const float4 c4 = scol[j * DV + v];
-          if (v * 4 < D) acc[v * 4] = __builtin_fmaf(c4.x, vis, acc[v * 4]);
-          if (v * 4 + 1 < D) acc[v * 4 + 1] = __builtin_fmaf(c4.y, vis, acc[v * 4 + 1]);
-          if (v * 4 + 2 < D) acc[v * 4 + 2] = __builtin_fmaf(c4.z, vis, acc[v * 4 + 2]);
-          if (v * 4 + 3 < D) acc[v * 4 + 3] = __builtin_fmaf(c4.w, vis, acc[v * 4 + 3]);
-        }
-        if (DEPTH) acc[D] = __builtin_fmaf(g0.w, vis, acc[D]);
-        T = valid ? nT : T;
-        last = valid ? (b + j) : last;
+        fwd_commit<D, DEPTH>(valid, alpha, nT, scol + j * DV, g0.w, b + j, T, last, acc);
         if ((++cnt & 15) == 0 && __all(done)) {
           m = 0;
           wdone = true;
@@ -217,15 +222,5 @@ __global__ void __launch_bounds__(256) k_raster_fwd_q(const RasterFwdArgs a) {
     }
   }
 
-  if (inside) {
-    const size_t pix = ((size_t)s * a.height + y) * a.width + x;
-    const float al = 1.f - T;
-    a.alphas[pix] = al;
-    a.final_T[pix] = T;
-    a.last_ids[pix] = last;
-    float *o = a.out + pix * NCH;
-#pragma unroll
-    for (int c = 0; c < D; c++) o[c] = acc[c] + (a.background ? T * a.background[c] : 0.f);
-    if (DEPTH) o[D] = a.ed ? acc[D] / fmaxf(al, 1e-10f) : acc[D];
-  }
+  if (inside) fwd_write_pixel<D, DEPTH>(a, s, x, y, T, last, acc);
 }

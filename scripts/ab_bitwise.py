@@ -1,4 +1,5 @@
-"""Two builds of libd4gs.so give the same bits in every loss and metric that sums in a fixed order (csrc/reduce.h) - and take the same time.
+"""Two builds of libd4gs.so give the same bits in every loss and metric that sums in a fixed order (csrc/reduce.h) and in the
+rasterizer's forward and backward - and the losses take the same time.
 
     python scripts/ab_bitwise.py PARENT.so [NEW.so] [--times] [--rounds 2] [--out FILE]
 
@@ -11,7 +12,8 @@ Digests (the default): each child runs seeded cases through the public entry poi
 trimmed_l1_loss, compute_gradient_loss, track_losses, motion_regularizers, masked_image_metrics with and without SSIM, the aligned-L1
 path of pwcnet, spherical harmonics forward and backward with a view-origin gradient - forward and backward, at two sizes: a smallest
 shape of the loss's GPU test and one whose count of block partials exceeds 256 (aligned L1 caps its partials at 128 per pair: that
-size), and prints the sha256 of every output and gradient.  The script fails if a digest differs between the libraries.
+size), and prints the sha256 of every output and gradient.  The rasterizer's cases (_raster_cases) follow, at 6 000 splats on 200 x 120
+and 30 000 on 320 x 200.  The script fails if a digest differs between the libraries.
 
 --times: the losses at their own benchmarks' sizes (scripts/bench_photometric.py, bench_metrics.py, bench_trimmed.py, bench_aligned.py's
 frame and pair count for the aligned L1 alone, bench_sh.py's first configuration, the regularizers at the size of
@@ -152,11 +154,83 @@ def _cases():
             "masked_image_metrics psnr only": lambda s: metrics(s, False), "aligned_l1": aligned, "sh fwd+bwd with origin": sh}
 
 
+def _raster_cases():
+    """rasterization() forward + backward - every output and every leaf gradient - over the composite kernels' instantiations: channel
+    counts on both of the forward's loops and on the matrix-pipe kernels, depth modes, absgrad, antialiased, depth segments, lazy lists,
+    exact tiles; and one one-call frame of S = 4 sub-samples, whose backward folds the blend's adjoint into the composite's prologue.
+    The composite backward sums in a fixed order (tests/test_gpu_rasterization.py: test_backward_is_deterministic)."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from deblur4dgs_amd.exposure import render_exposure
+    from deblur4dgs_amd.rasterization import rasterization
+    from deblur4dgs_amd.synth import make_scene
+    from tests.util import static_inputs
+
+    dev = "cuda:0"
+    shapes = {"small": dict(N=6000, W=200, H=120, seed=77, scale_mul=3.0), "large": dict(N=30000, W=320, H=200, seed=55, scale_mul=2.5)}
+
+    def raster(mode, D, bg=False, env=None, **kw):
+        def make(size):
+            sh = shapes[size]
+            inp = {k: v.to(dev) for k, v in static_inputs(**sh, D=max(D, 1)).items()}
+            W, H = sh["W"], sh["H"]
+            g = torch.Generator().manual_seed(11)
+            nch = D + (mode != "RGB")
+            wc, wa = torch.randn(1, H, W, nch, generator=g).to(dev), torch.randn(1, H, W, 1, generator=g).to(dev)
+            back = torch.linspace(0.2, 0.9, D)[None].to(dev) if bg else None
+
+            def run():
+                leaves = [inp[k].clone().requires_grad_() for k in ("means", "quats", "scales", "opac", "colors", "V")]
+                old = {k: os.environ.get(k) for k in (env or {})}
+                os.environ.update(env or {})  # (the library reads these per call)
+                try:
+                    rc, ra, info = rasterization(*leaves[:5], leaves[5][None], inp["K"][None], W, H, backgrounds=back, render_mode=mode, **kw)
+                    ((rc * wc).sum() + (ra * wa).sum()).backward()
+                    torch.cuda.synchronize()
+                finally:
+                    for k, v in old.items():
+                        os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
+                grads = [x.grad for x in leaves if x.grad is not None]  # (depth only: the colours are not composited)
+                extra = [info["means2d"].absgrad] if kw.get("absgrad") else []
+                return [rc.detach(), ra.detach(), info["last_ids"]] + grads + extra
+            return run
+        return make
+
+    def frame(size):
+        N, G, K_, S, W, H = {"small": (600, 400, 3, 4, 64, 48), "large": (5000, 3000, 4, 4, 160, 96)}[size]
+        sc = make_scene(N, G, K_, S, W, H, seed=31)
+        names = ("means", "quats", "scales", "opacities", "colors", "motion_coefs", "rots", "transls", "times", "RTs", "viewmat")
+        K = sc["K"].to(dev)
+        g = torch.Generator().manual_seed(7)
+        wb, wa = torch.randn(H, W, 4, generator=g).to(dev), torch.randn(H, W, generator=g).to(dev)
+
+        def run():
+            L = {k: sc[k].to(dev).clone().requires_grad_() for k in names}
+            r = render_exposure(*(L[k] for k in names[:5]), 3, *(L[k] for k in names[5:]), K, W, H, background=torch.linspace(0.2, 0.9, 3).to(dev),
+                                return_depth=True, blend=True, fused=True)
+            assert r["state"].frame_io
+            ((r["blended"] * wb).sum() + (r["acc"] * wa).sum()).backward()  # gradients on the blended frame only: the folded adjoint
+            torch.cuda.synchronize()
+            return [r["blended"].detach(), r["acc"].detach(), r["renders"].detach(), r["alphas"].detach()] + [L[k].grad for k in names]
+        return run
+
+    seg = {"D4GS_SEG": "1"}
+    return {"raster RGB 1": raster("RGB", 1), "raster RGB+ED 3 bg": raster("RGB+ED", 3, bg=True), "raster RGB 4": raster("RGB", 4),
+            "raster RGB+D 5": raster("RGB+D", 5), "raster RGB 8": raster("RGB", 8), "raster RGB+ED 16": raster("RGB+ED", 16),
+            "raster ED": raster("ED", 0), "raster RGB+ED 3 absgrad": raster("RGB+ED", 3, absgrad=True),
+            "raster RGB+ED 3 antialiased": raster("RGB+ED", 3, rasterize_mode="antialiased"),
+            "raster RGB+ED 3 segments": raster("RGB+ED", 3, env=seg), "raster RGB+ED 16 segments": raster("RGB+ED", 16, env=seg),
+            "raster RGB+ED 3 lazy_sort": raster("RGB+ED", 3, lazy_sort=True), "raster RGB+ED 3 exact_tiles": raster("RGB+ED", 3, exact_tiles=True),
+            "frame S=4 one call": frame}
+
+
 def child(times, iters, windows):
     import torch
 
     assert torch.cuda.is_available(), "ab_bitwise.py runs on the GPU"
-    for name, make in _cases().items():
+    cases = _cases() if times else {**_cases(), **_raster_cases()}  # (the composites are timed by bench.py, not here)
+    for name, make in cases.items():
         if not times:
             for size in ("small", "large"):
                 outs = make(size)()
