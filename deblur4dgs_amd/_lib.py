@@ -124,6 +124,8 @@ EXPORTS = (
     "d4gs_aligned_l1_blocks", "d4gs_aligned_l1_fwd", "d4gs_aligned_l1_bwd",
     "d4gs_motion_regs_workspace_bytes", "d4gs_motion_regs_fwd", "d4gs_motion_regs_bwd",
     "d4gs_metrics_blocks", "d4gs_masked_metrics",
+    "d4gs_dilate_mask", "d4gs_area_keep_map_elems", "d4gs_area_keep_blocks", "d4gs_area_keep_fwd", "d4gs_area_keep_bwd",
+    "d4gs_mse_blocks", "d4gs_mse_fwd", "d4gs_mse_bwd",
 )
 
 # Appended to ABI 305 after A/B libraries of older trees were built.  The product library must have them (as every export; build()
@@ -236,6 +238,16 @@ def lib() -> C.CDLL:
         L.d4gs_metrics_blocks.argtypes = [i32] * 4
         L.d4gs_metrics_blocks.restype = C.c_int64
         L.d4gs_masked_metrics.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.d4gs_dilate_mask.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+        for q in (L.d4gs_area_keep_map_elems, L.d4gs_area_keep_blocks):
+            q.argtypes = [i32] * 5
+            q.restype = C.c_int64
+        L.d4gs_area_keep_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.d4gs_area_keep_bwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
+        L.d4gs_mse_blocks.argtypes = [C.c_int64]
+        L.d4gs_mse_blocks.restype = C.c_int64
+        L.d4gs_mse_fwd.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+        L.d4gs_mse_bwd.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
         if L.d4gs_version() != VERSION:
             raise RuntimeError(f"libd4gs.so version {L.d4gs_version()} != {VERSION} (stale build?)")
         _lib = L

@@ -19,6 +19,11 @@ and projects them, the selection runs for the 2-D term only, one kernel scatters
 `motion_regularizers` is what is left of that function beyond the render (flow3d/trainer.py:691-728): the smoothness of the motion
 bases, the smoothness of every foreground track, the acceleration along the viewing ray and the variance of the raw scales, in one
 call forward and one backward on the pose kernels (`csrc/motion_regs.hip`).
+
+`dilate_mask`, `sharp_keep_loss` and `coverage_loss` are the passes of those two functions that the reference writes as plain torch
+ops: `nn.MaxPool2d(9, 1, 4)` on the foreground mask (trainer.py:120,388,575,901), the area-reduced masked L1 between the sharp
+sub-sample and the blurry target (:736-760) and `F.mse_loss` on the accumulated alpha (:621-631) (`csrc/image_terms.hip`, DESIGN.md
+section 22).
 """
 from __future__ import annotations
 
@@ -396,3 +401,129 @@ def scene_motion_regularizers(model, ts, w2cs, **kw):
         loss += w_smooth_bases * sb + w_smooth_tracks * st + w_z_accel * za + w_scale_var * sv"""
     fg, mb = model.fg.params, model.motion_bases.params
     return motion_regularizers(fg["means"], fg["motion_coefs"], mb["rots"], mb["transls"], fg["scales"], ts, w2cs, **kw)
+
+
+_CPU = "deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor"
+
+
+def _mask_bhw(masks, name="masks"):
+    """-> (B, H, W) of a [B,H,W] or [B,H,W,1] tensor."""
+    if not torch.is_tensor(masks) or masks.dim() not in (3, 4) or (masks.dim() == 4 and masks.shape[-1] != 1) or masks.numel() == 0:
+        raise ValueError(f"{name} {tuple(masks.shape) if torch.is_tensor(masks) else type(masks)}: expected a non-empty [B,H,W] or [B,H,W,1]")
+    return tuple(masks.shape[:3])
+
+
+def dilate_mask(masks, kernel_size: int = 9, return_complement: bool = False):
+    """`nn.MaxPool2d(kernel_size, stride=1, padding=kernel_size // 2)` on a [B,H,W] or [B,H,W,1] mask (flow3d/trainer.py:120): every
+    pixel becomes the maximum of its kernel_size x kernel_size window clipped to the image, bit for bit.  -> fp32, shaped like
+    `masks`; with return_complement also `1 - dilated` from the same pass, the mask of the static depth losses (trainer.py:397,413).
+    Masks are data: the result carries no gradient.  An even kernel_size has no centre and raises ValueError."""
+    k = int(kernel_size)
+    if k != kernel_size or k < 1 or k % 2 == 0:
+        raise ValueError(f"kernel_size={kernel_size}: must be a positive odd integer")
+    B, H, W = _mask_bhw(masks)
+    if not masks.is_cuda:
+        raise RuntimeError(_CPU)
+    m = _f32(masks)
+    out = torch.empty_like(m)
+    comp = torch.empty_like(m) if return_complement else None
+    L.check(L.lib().d4gs_dilate_mask(_p(m), B, H, W, k // 2, _p(out), _p(comp), C.c_void_p(L.raw_stream(m.device.index))), "d4gs_dilate_mask")
+    return (out, comp) if return_complement else out
+
+
+class _SharpKeepFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, mask, reduced, factor):
+        B, H, W, Cc = pred.shape
+        p, t, m = _f32(pred), _f32(target), _f32(mask).reshape(B, H, W)
+        lib = L.lib()
+        dims = (B, H, W, Cc, factor)
+        n_map, nb = lib.d4gs_area_keep_map_elems(*dims), lib.d4gs_area_keep_blocks(*dims)
+        if n_map == 0:
+            raise RuntimeError(f"sharp_keep_loss: unsupported size {tuple(pred.shape)} (H, W <= 32768, at most 2^31 - 1 elements)")
+        gmap = torch.empty(n_map, device=p.device, dtype=torch.float32)
+        partials = torch.empty(nb, device=p.device, dtype=torch.float64)
+        out = torch.empty(1, device=p.device, dtype=torch.float32)
+        stream = C.c_void_p(L.raw_stream(p.device.index))
+        L.check(lib.d4gs_area_keep_fwd(_p(p), _p(m), _p(t), int(reduced), *dims, _p(gmap), _p(partials), _p(out), stream), "d4gs_area_keep_fwd")
+        ctx.save_for_backward(gmap)
+        ctx.args = (dims, pred.dtype)
+        return out.reshape(())  # (nothing else holds `out`: no clone)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v_loss):
+        gmap, = ctx.saved_tensors
+        (B, H, W, Cc, factor), dtype = ctx.args
+        v = v_loss.detach().float().reshape(1).contiguous()
+        v_pred = torch.empty(B, H, W, Cc, device=gmap.device, dtype=torch.float32)
+        stream = C.c_void_p(L.raw_stream(gmap.device.index))
+        L.check(L.lib().d4gs_area_keep_bwd(_p(gmap), _p(v), B, H, W, Cc, factor, _p(v_pred), stream), "d4gs_area_keep_bwd")
+        return v_pred.to(dtype), None, None, None, None
+
+
+def sharp_keep_loss(pred_sharp, target, masks, factor: int = 4):
+    """The reference's `loss_keep` (flow3d/trainer.py:736-760): `F.l1_loss(area(pred_sharp) * area(masks), area(target) * area(masks))`
+    with area(x) = `F.interpolate(x, scale_factor=1 / factor, mode="area")`.  pred_sharp [B,H,W,C] channel-last, masks [B,H,W] or
+    [B,H,W,1]; target is the full-size [B,H,W,C] image (the `batch4 is None` branch) or the already reduced [B,H//factor,W//factor,C]
+    one (the other branch), told apart by shape; with factor == 1 the two coincide and the target is used as it is.  factor is 1, 2,
+    4 or 8; H < factor or W < factor (torch: an empty tensor and a NaN loss) raises ValueError.  Differentiable w.r.t. pred_sharp
+    only; sign(0) = 0 as in `F.l1_loss`."""
+    if factor not in (1, 2, 4, 8):
+        raise ValueError(f"factor={factor}: must be 1, 2, 4 or 8")
+    if not torch.is_tensor(pred_sharp) or pred_sharp.dim() != 4 or pred_sharp.numel() == 0:
+        raise ValueError(f"pred_sharp {tuple(pred_sharp.shape) if torch.is_tensor(pred_sharp) else type(pred_sharp)}: expected a non-empty [B,H,W,C]")
+    B, H, W, Cc = pred_sharp.shape
+    if _mask_bhw(masks) != (B, H, W):
+        raise ValueError(f"masks {tuple(masks.shape)} does not match pred_sharp {tuple(pred_sharp.shape)}")
+    if H < factor or W < factor:
+        raise ValueError(f"H={H}, W={W} below factor={factor}: the reduced image is empty")
+    if not torch.is_tensor(target) or tuple(target.shape) not in ((B, H, W, Cc), (B, H // factor, W // factor, Cc)):
+        raise ValueError(f"target {tuple(target.shape) if torch.is_tensor(target) else type(target)}: expected {(B, H, W, Cc)} or the reduced "
+                         f"{(B, H // factor, W // factor, Cc)}")
+    for x in (pred_sharp, target, masks):
+        if not x.is_cuda:
+            raise RuntimeError(_CPU)
+    reduced = tuple(target.shape) == (B, H // factor, W // factor, Cc)  # (factor == 1: both; a 1 x 1 window's mean is the value)
+    return _SharpKeepFn.apply(pred_sharp, target, masks, reduced, int(factor))
+
+
+class _CoverageFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, acc, target):
+        a = _f32(acc)
+        t = None if target is None else _f32(target)
+        n = a.numel()
+        lib = L.lib()
+        nb = lib.d4gs_mse_blocks(n)
+        if nb == 0:
+            raise RuntimeError(f"coverage_loss: {n} elements (at most 2^31 - 1)")
+        partials = torch.empty(nb, device=a.device, dtype=torch.float64)
+        out = torch.empty(1, device=a.device, dtype=torch.float32)
+        L.check(lib.d4gs_mse_fwd(_p(a), _p(t), n, _p(partials), _p(out), C.c_void_p(L.raw_stream(a.device.index))), "d4gs_mse_fwd")
+        ctx.save_for_backward(a, *(() if t is None else (t,)))
+        ctx.dtype = acc.dtype
+        return out.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v_loss):
+        a, *rest = ctx.saved_tensors
+        t = rest[0] if rest else None
+        v = v_loss.detach().float().reshape(1).contiguous()
+        v_acc = torch.empty_like(a)
+        L.check(L.lib().d4gs_mse_bwd(_p(a), _p(t), _p(v), a.numel(), _p(v_acc), C.c_void_p(L.raw_stream(a.device.index))), "d4gs_mse_bwd")
+        return v_acc.to(ctx.dtype), None
+
+
+def coverage_loss(acc, target=None):
+    """`F.mse_loss(acc, target)` on the accumulated alpha (flow3d/trainer.py:621-631).  acc [B,H,W,1] or [B,H,W]; target=None is the
+    all-ones target of a scene with a background model, otherwise `masks[..., None]` (any tensor with acc's number of elements).
+    Differentiable w.r.t. acc only; the gradient is exactly 0 where acc == target."""
+    if not torch.is_tensor(acc) or acc.dim() not in (3, 4) or (acc.dim() == 4 and acc.shape[-1] != 1) or acc.numel() == 0:
+        raise ValueError(f"acc {tuple(acc.shape) if torch.is_tensor(acc) else type(acc)}: expected a non-empty [B,H,W] or [B,H,W,1]")
+    if target is not None and (not torch.is_tensor(target) or _mask_bhw(target, "target") != tuple(acc.shape[:3])):
+        raise ValueError(f"target {tuple(target.shape)} does not match acc {tuple(acc.shape)}")
+    if not acc.is_cuda or (target is not None and not target.is_cuda):
+        raise RuntimeError(_CPU)
+    return _CoverageFn.apply(acc, target)

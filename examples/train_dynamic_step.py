@@ -18,6 +18,11 @@ With --motion-regs the step also carries the four regularizers of the trainer th
 motion bases, smooth foreground tracks, small acceleration along the viewing ray, the variance of the raw scales;
 deblur4dgs_amd.losses.scene_motion_regularizers); `--motion-regs torch` evaluates them the way the reference
 writes them, in eager torch on the pose API (a timing comparator: torch.linalg.inv waits for the device, so it cannot be captured).
+With --image-losses the step carries the remaining image-sized passes of the trainer (deblur4dgs_amd.losses):
+the foreground mask dilated by a 9 x 9 max-pool (trainer.py:120) masks a second photometric term of the dynamic render and, as its
+complement, one of the static render (:388-392,575-580) - and, with --depth-losses, the static depth losses (:397,413); the
+sharp-keep loss ties the middle sub-sample to the blurry target at quarter resolution (:736-747); the coverage term pulls the
+accumulated alpha to one (:624-626).
 It exists to show the seam in a real autograd + optimizer loop:
 
     python examples/train_dynamic_step.py --steps 20
@@ -25,6 +30,7 @@ It exists to show the seam in a real autograd + optimizer loop:
     python examples/train_dynamic_step.py --graph --hip-adam --consistency-loss
     python examples/train_dynamic_step.py --graph --hip-adam --track-losses
     python examples/train_dynamic_step.py --graph --hip-adam --motion-regs
+    python examples/train_dynamic_step.py --graph --hip-adam --image-losses
 """
 from __future__ import annotations
 
@@ -39,8 +45,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from deblur4dgs_amd import engine  # noqa: E402
 from deblur4dgs_amd.control import ControlCfg, accumulate_from_model, cull_step, densify_step, spatial_order_step  # noqa: E402
-from deblur4dgs_amd.losses import (compute_gradient_loss, masked_l1_loss, photometric_loss, scene_motion_regularizers,  # noqa: E402
-                                   track_losses as hip_track_losses)
+from deblur4dgs_amd.losses import (compute_gradient_loss, coverage_loss, dilate_mask, masked_l1_loss, photometric_loss,  # noqa: E402
+                                   scene_motion_regularizers, sharp_keep_loss, track_losses as hip_track_losses)
 from deblur4dgs_amd.pwcnet import PWCNet, exposure_consistency_loss  # noqa: E402
 from deblur4dgs_amd.scene_model import GaussianParams, MotionBases, SceneModel  # noqa: E402
 from deblur4dgs_amd.synth import make_scene  # noqa: E402
@@ -119,7 +125,7 @@ def torch_motion_regularizers(model, ts, w2cs):
 
 def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, fused_stats=True, deferred=True,
           graph=False, hip_adam=False, seed=0, step_events=None, depth_losses=False, consistency_loss=False, track_losses=False,
-          n_tracks=4096, motion_regs=False, **kw):
+          n_tracks=4096, motion_regs=False, image_losses=False, **kw):
     """fused_stats: the densification statistics come out of the rasterizer's backward (attach_control_stats) instead
     of a pass over `_current_xys[i].grad`; deferred: no render waits for its intersection count on the host
     (`deferred_size_check`), the counts are verified once per step; graph: the three renders, the loss and the whole
@@ -137,7 +143,10 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
     path, which captures; "torch": the reference's formulation in eager torch, which waits for the device and does not;
     motion_regs: add the reference's smooth-bases, smooth-tracks, z-acceleration and scale-variance regularizers with its weights
     (configs.py: 0.1, 2, 1, 0.01) for the step's frame and camera - True: one HIP call each way, which captures; "torch": the
-    reference's wording in eager torch (torch_motion_regularizers), which does not."""
+    reference's wording in eager torch (torch_motion_regularizers), which does not; image_losses: add the dilated-mask photometric
+    terms of the dynamic and the static render (w_rgb 1), the sharp-keep loss (weight 1) and the coverage term (w_mask 1), and hand
+    the depth losses the complement of the dilated mask - the mask is dilated inside the step, as the reference does, and the
+    step still captures."""
     assert not graph or (fused_stats and deferred), "graph capture needs the sync-free step"
     assert track_losses in (False, True, "torch") and not (graph and track_losses == "torch"), "the torch form cannot be captured"
     assert motion_regs in (False, True, "torch") and not (graph and motion_regs == "torch"), "the torch form cannot be captured"
@@ -149,13 +158,16 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
         tgt_model, _ = build(W=W, H=H, dev=dev, seed=seed + 1, **kw)
         tgt_dyn = tgt_model.render(3, w2c, K, (W, H), mode="blury")["img"]
         tgt_sta = tgt_model.render(3, w2c, K, (W, H), bg_only=True, mode="blury")["img"]
-        if depth_losses:  # the perturbed scene also supplies the depth of the `mid` frame and the foreground mask
+        if depth_losses:  # the perturbed scene also supplies the depth of the `mid` frame
             tgt_mid = tgt_model.render(3, w2c, K, (W, H), bg_only=True, return_depth=True, mode="mid")
             tgt_disp = 1.0 / (tgt_mid["depth"] + 1e-5)
+        if depth_losses or image_losses:  # and the foreground mask
             tgt_mask = (tgt_model.render(3, w2c, K, (W, H), return_mask=True, mode="blury")["mask"] > 0.5).float()
-            # outside the foreground mask (the reference dilates it first: trainer.py:388,397) and, the scene being synthetic, only
-            # where the target's background covers the pixel: a hole has depth 0, a disparity of 1e5
-            depth_masks = (1.0 - tgt_mask) * (tgt_mid["acc"] > 0.5).float()
+        if depth_losses:
+            # outside the foreground mask (with image_losses: outside the dilated one, inside the step) and, the scene being synthetic,
+            # only where the target's background covers the pixel: a hole has depth 0, a disparity of 1e5
+            depth_covered = (tgt_mid["acc"] > 0.5).float()
+            depth_masks = (1.0 - tgt_mask) * depth_covered
             depth_valid = depth_masks > 0.5
         if track_losses:  # supervision from the perturbed scene's own track points
             tgt_ts = torch.tensor([1.0, 2.0, 4.0, 5.0], device=dev)
@@ -208,10 +220,18 @@ def train(steps=20, dev="cuda:0", W=512, H=288, verbose=True, control_every=0, f
             loss = loss + 2.0 * l2d / max(H, W) + 0.1 * ldepth
         else:  # a stand-in that gives the track channels a gradient
             loss = loss + 1e-3 * out2["tracks_3d"].square().mean()
+        d_masks, d_valid = (depth_masks, depth_valid) if depth_losses else (None, None)
+        if image_losses:
+            dilated, outside = dilate_mask(tgt_mask, return_complement=True)  # trainer.py:388,575: MaxPool2d(9, 1, 4), and 1 - it
+            loss = loss + photometric_loss(out2["img"], tgt_dyn, mask=dilated) + photometric_loss(out1["img"], tgt_sta, mask=outside) + \
+                sharp_keep_loss(out2["pred_sharp_img"], tgt_dyn, tgt_mask) + 1.0 * coverage_loss(out2["acc"])
+            if depth_losses:  # trainer.py:397,413
+                d_masks = outside * depth_covered
+                d_valid = d_masks > 0.5
         if depth_losses:
             pred_disp = 1.0 / (out3["depth"] + 1e-5)
-            loss = loss + 0.5 * masked_l1_loss(pred_disp, tgt_disp, mask=depth_masks, quantile=0.98) + \
-                1.0 * compute_gradient_loss(pred_disp, tgt_disp, mask=depth_valid, quantile=0.95) + \
+            loss = loss + 0.5 * masked_l1_loss(pred_disp, tgt_disp, mask=d_masks, quantile=0.98) + \
+                1.0 * compute_gradient_loss(pred_disp, tgt_disp, mask=d_valid, quantile=0.95) + \
                 1.0 * masked_l1_loss(out2["mask"], tgt_mask, quantile=0.98)
         if consistency_loss:
             loss = loss + 2.0 * exposure_consistency_loss(out2["exposure_imgs"], alignnet)
@@ -324,8 +344,10 @@ if __name__ == "__main__":
     ap.add_argument("--motion-regs", nargs="?", const="hip", default=None, choices=("hip", "torch"),
                     help="the reference's smooth-bases, smooth-tracks, z-acceleration and scale-variance regularizers: HIP and "
                          "graph-capturable, or `torch`: the reference's eager formulation on the pose API (torch.linalg.inv)")
+    ap.add_argument("--image-losses", action="store_true",
+                    help="add the dilated-mask photometric terms, the sharp-keep loss and the coverage term (HIP, graph-capturable)")
     a = ap.parse_args()
     train(a.steps, control_every=a.control_every, fused_stats=not a.round1, deferred=not a.round1, graph=a.graph, hip_adam=a.hip_adam,
           depth_losses=a.depth_losses, consistency_loss=a.consistency_loss,
           track_losses={None: False, "hip": True, "torch": "torch"}[a.track_losses], n_tracks=a.tracks,
-          motion_regs={None: False, "hip": True, "torch": "torch"}[a.motion_regs])
+          motion_regs={None: False, "hip": True, "torch": "torch"}[a.motion_regs], image_losses=a.image_losses)

@@ -730,6 +730,45 @@ D4GS_API int64_t d4gs_metrics_blocks(int32_t M, int32_t B, int32_t H, int32_t W)
 D4GS_API int d4gs_masked_metrics(const float *pred, const float *target, const float *masks, int32_t M, int32_t B, int32_t H,
                                  int32_t W, int32_t want_ssim, double *partials, double *out, void *stream);
 
+/* Image terms (appended; D4GS_VERSION unchanged): the passes of Trainer.compute_dynamic_losses / compute_static_losses that the
+ * reference writes as plain torch ops.  Every tensor is fp32, contiguous, channel-last; nothing is read on the host, no atomics, every
+ * sum has a fixed order (bitwise reproducible), every launch is on `stream`.  D4GS_EINVAL, by host arithmetic alone and before any
+ * HIP call, for a NULL required pointer, a misaligned pointer, a size < 1 or beyond the grid, and what each entry names below.
+ *
+ * Dilation (nn.MaxPool2d(2r+1, stride 1, padding r); the reference's r is 4): mask, out [B,H,W];
+ *   out[b,y,x] = max of mask[b,y',x'] over |y' - y| <= r, |x' - x| <= r clipped to the image
+ * - max-pool's -inf padding, so a mask of all -1 dilates to -1.  Values are copied: bit-exact (NaN propagates as in torch; which of
+ * +0 and -0 a tie keeps is not specified).  out_complement, when not NULL, receives 1 - out in the same pass.  r >= 0 (r < 0:
+ * D4GS_EINVAL); B and ceil(H / 16) <= 65535, W <= 2^30.  No gradient: masks are data.
+ *
+ * Sharp-keep loss (flow3d/trainer.py:736-760: F.interpolate(scale_factor=1/factor, mode="area") of prediction, mask and target, then
+ * F.l1_loss): pred [B,H,W,C], mask [B,H,W], target [B,H,W,C] (target_reduced == 0) or already reduced [B,Ho,Wo,C] (!= 0), factor one
+ * of 1, 2, 4, 8, Ho = H / factor and Wo = W / factor rounded down.  Output window i along an axis of length L with Lo outputs covers
+ * [floor(i L / Lo), ceil((i + 1) L / Lo)) (torch's adaptive average pool: when factor does not divide L, windows differ in size and
+ * neighbours overlap by at most one row or column).  With abar the window mean of a (tbar = t for a reduced target):
+ *   out[0] = sum |pbar mbar - tbar mbar| / (B Ho Wo C)
+ * Window sums, the products and the total are in double.  map [d4gs_area_keep_map_elems] receives sign(pbar mbar - tbar mbar) * mbar /
+ * area(window) per output element, sign(0) = 0: all the backward reads.  partials: d4gs_area_keep_blocks doubles of scratch, 8-byte
+ * aligned.  Both queries return 0 for sizes the entry points refuse: a size < 1, a factor outside the set, H < factor or W < factor
+ * (torch returns an empty tensor and a NaN loss there), H or W > 32768, B H W C > 2^31 - 1.
+ * Backward: v_pred[b,y,x,c] = v_loss[0] * sum over the at most 2 x 2 windows that hold (y, x) of map / (B Ho Wo C) (v_loss: device
+ * scalar), a gather per input pixel.  Nothing flows to mask or target.
+ *
+ * Coverage (F.mse_loss): out[0] = mean over n elements of (a - t)^2, t == NULL: the constant 1; differences, squares and sums in
+ * double.  partials: d4gs_mse_blocks(n) doubles, 8-byte aligned (0: n < 1 or n > 2^31 - 1).  Backward: v_a = v_loss[0] * 2 (a - t) / n,
+ * exactly 0 where a == t. */
+D4GS_API int d4gs_dilate_mask(const float *mask, int32_t B, int32_t H, int32_t W, int32_t r, float *out, float *out_complement,
+                              void *stream);
+D4GS_API int64_t d4gs_area_keep_map_elems(int32_t B, int32_t H, int32_t W, int32_t C, int32_t factor); /* 0: illegal sizes */
+D4GS_API int64_t d4gs_area_keep_blocks(int32_t B, int32_t H, int32_t W, int32_t C, int32_t factor);    /* 0: illegal sizes */
+D4GS_API int d4gs_area_keep_fwd(const float *pred, const float *mask, const float *target, int32_t target_reduced, int32_t B, int32_t H,
+                                int32_t W, int32_t C, int32_t factor, float *map, double *partials, float *out, void *stream);
+D4GS_API int d4gs_area_keep_bwd(const float *map, const float *v_loss, int32_t B, int32_t H, int32_t W, int32_t C, int32_t factor,
+                                float *v_pred, void *stream);
+D4GS_API int64_t d4gs_mse_blocks(int64_t n); /* 0: illegal size */
+D4GS_API int d4gs_mse_fwd(const float *a, const float *t, int64_t n, double *partials, float *out, void *stream);
+D4GS_API int d4gs_mse_bwd(const float *a, const float *t, const float *v_loss, int64_t n, float *v_a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
