@@ -1,4 +1,7 @@
-"""ctypes binding of libd4gs.so (the C ABI declared in include/d4gs.h).
+"""ctypes binding of libd4gs.so, derived at import from include/d4gs.h: the header is the one statement of the C ABI.
+
+Appending an entry point, a struct or a constant means editing the header and nothing here (a new struct: one line of
+STRUCT_NAMES).  The type rules and the [host] / [device] marks are in `_ctype`; DESIGN.md section 23 has them as a table.
 
 The product path has NO fallback: if the HIP library is missing this module raises at first use, and every
 entry point raises RuntimeError on a non-zero return code with `d4gs_last_error()`.
@@ -7,126 +10,114 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("D4GS_LIB_PATH") or os.path.join(HERE, "libd4gs.so")  # override: A/B builds (scripts/)
+HEADER = os.path.join(HERE, "..", "include", "d4gs.h")
 
 F = C.c_void_p  # device pointers travel as void*
 
-
-class Dims(C.Structure):
-    _fields_ = [
-        ("N", C.c_int32), ("G", C.c_int32), ("K", C.c_int32), ("T", C.c_int32), ("S", C.c_int32), ("D", C.c_int32),
-        ("width", C.c_int32), ("height", C.c_int32), ("depth_mode", C.c_int32), ("flags", C.c_int32),
-        ("n_sigmoid", C.c_int32),
-        ("near_plane", C.c_float), ("far_plane", C.c_float), ("eps2d", C.c_float), ("radius_clip", C.c_float),
-    ]
-
-
-class ProjIn(C.Structure):
-    _fields_ = [(n, F) for n in ("means", "quats", "scales", "opacities", "colors", "motion_coefs", "rots", "transls",
-                                 "times", "RTs", "viewmat", "Kmat")]
-
-
-class ProjOut(C.Structure):
-    _fields_ = [(n, F) for n in ("means2d", "depths", "conics", "radii", "opac_act", "ctab", "geom", "tile_rects", "tiles_touched",
-                                 "isect_offsets", "lazy_ws", "tile_counts", "tile_offsets", "n_isect", "scan_ws", "blend_bases",
-                                 "tile_masks", "compensations")]
+# C name -> the name the package uses
+STRUCT_NAMES = {
+    "D4gsDims": "Dims", "D4gsProjIn": "ProjIn", "D4gsProjOut": "ProjOut", "D4gsIsect": "Isect", "D4gsRaster": "Raster",
+    "D4gsRasterGrads": "RasterGrads", "D4gsLeafGrads": "LeafGrads", "D4gsSizes": "Sizes", "D4gsPoses": "Poses",
+    "D4gsMoveModelParams": "MoveModelParams", "D4gsMoveModelOut": "MoveModelOut", "D4gsMoveModelGrads": "MoveModelGrads",
+    "D4gsFrameIO": "FrameIO", "D4gsFrameGrads": "FrameGrads", "D4gsShardBlend": "ShardBlend", "D4gsAdamRec": "AdamRec",
+}
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint8_t": C.c_uint8, "int8_t": C.c_int8,
+            "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_STARS = r"((?:\*\s*(?:const\b\s*)?)*)"  # `*`, `* const *`, ...: only the count matters
+_PARAM = re.compile(rf"(?:const\s+)?(\w+)\b\s*{_STARS}\b(\w+)\s*(?:@(host|device))?")
+_DECLARATOR = re.compile(rf"{_STARS}\b(\w+)\s*(?:\[(\d+)\])?")
+_FIELD = r"\s*([^;@{}]+?)\s*;((?:\s*@\w+)*)"  # one declaration (one or more declarators) and the marks of its inline comment
 
 
-class Isect(C.Structure):
-    _fields_ = [("n_isect", C.c_int64), ("max_tile_count", C.c_int64), ("near_target", C.c_int64)] + \
-               [(n, F) for n in ("keys", "gid_of_emit", "sorted_gid", "sorted_emit")]
+def _ctype(base, stars, mark, structs, text):
+    """The ctypes type of one parameter or field: `base` with `stars` levels of pointer and the declaration's mark."""
+    n = stars.count("*")
+    if base in structs:  # a descriptor travels by host pointer, unless it is marked as a table in device memory
+        if n == 1:
+            return C.c_void_p if mark == "device" else C.POINTER(structs[base])
+    elif n == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    elif n == 1 and base == "char":
+        return C.c_char_p
+    elif n == 1 and (base == "void" or base in _SCALARS):  # a device pointer, unless marked [host]
+        return C.POINTER(_SCALARS[base]) if mark == "host" and base != "void" else C.c_void_p
+    elif n == 2 and (base == "void" or base in _SCALARS):  # a host array of pointers
+        return C.POINTER(C.c_void_p)
+    raise ValueError(f"d4gs.h: cannot bind the type of `{text}`")
 
 
-class Raster(C.Structure):
-    _fields_ = [(n, F) for n in ("background", "render_colors", "render_alphas", "last_ids", "final_T", "seg_state")]
+def parse(text):
+    """-> (constants, structs, prototypes) of the header `text`: {name without D4GS_: int}, {Python name: ctypes.Structure},
+    {entry point: (restype, argtypes)}.  Strict: whatever is left of the header once every enum, struct and prototype has been
+    taken out, and every declaration that does not parse completely, raises ValueError with the offending text."""
+    def comment(m):  # an inline comment (code before it on its line) leaves its mark as a token; every other comment is blank
+        inline = text[text.rfind("\n", 0, m.start()) + 1:m.start()].strip()
+        found = re.search(r"\[(host|device)\]", m.group()) if inline else None
+        return f" @{found.group(1)} " if found else " "
+
+    code = re.sub(r"/\*.*?\*/", comment, text, flags=re.S)
+    constants = {k: int(v) for k, v in re.findall(r"^#define D4GS_(\w+)[ \t]+(-?\d+)[ \t]*$", code, flags=re.M)}
+    n_api, n_structs = len(re.findall(r"\bD4GS_API\b", code)) - 1, len(re.findall(r"\btypedef\s+struct\b", code))
+    code = re.sub(r"^[ \t]*#.*$", "", code, flags=re.M)
+    structs, by_c_name, prototypes = {}, {}, {}
+
+    def enum(m):
+        for item in filter(None, (x.strip() for x in m.group(1).split(","))):
+            e = re.fullmatch(r"D4GS_(\w+)\s*=\s*(-?\d+)", item)
+            if not e:
+                raise ValueError(f"d4gs.h: cannot parse the enumerator `{item}`")
+            constants[e.group(1)] = int(e.group(2))
+        return ""
+
+    def struct(m):
+        body, name = m.groups()
+        if name not in STRUCT_NAMES or not re.fullmatch(f"(?:{_FIELD})*\\s*", body):
+            raise ValueError(f"d4gs.h: cannot parse struct {name} (or it has no entry in STRUCT_NAMES): `{body.strip()}`")
+        fields = []
+        for decl, marks in re.findall(_FIELD, body):
+            d = re.fullmatch(r"(?:const\s+)?(\w+)\b\s*(.*)", decl, flags=re.S)
+            for one in d.group(2).split(",") if d else [""]:
+                f = _DECLARATOR.fullmatch(one.strip())
+                if not f:
+                    raise ValueError(f"d4gs.h: cannot parse the field `{decl}` of {name}")
+                t = _ctype(d.group(1), f.group(1), marks.strip()[1:] or None, by_c_name, decl)
+                fields.append((f.group(2), t * int(f.group(3)) if f.group(3) else t))
+        by_c_name[name] = structs[STRUCT_NAMES[name]] = type(STRUCT_NAMES[name], (C.Structure,), {"_fields_": fields})
+        return ""
+
+    def prototype(m):
+        ret, name, params = (x.strip() for x in m.groups())
+        restype = C.c_char_p if re.fullmatch(r"const\s+char\s*\*", ret) else None if ret == "void" else _SCALARS.get(ret)
+        if restype is None and ret != "void":
+            raise ValueError(f"d4gs.h: cannot bind the return type of `{m.group().strip()}`")
+        argtypes = None  # f(void): ctypes' default, as for a function that was never given argtypes
+        if params != "void":
+            found = [_PARAM.fullmatch(p.strip()) for p in params.split(",")]
+            if not all(found):
+                raise ValueError(f"d4gs.h: cannot parse a parameter of `{m.group().strip()}`")
+            argtypes = [_ctype(p.group(1), p.group(2), p.group(4), by_c_name, p.group()) for p in found]
+        prototypes[name] = (restype, argtypes)
+        return ""
+
+    code = re.sub(r"\benum\s*\{([^{}]*)\}\s*;", enum, code)
+    code = re.sub(r"\btypedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, code)
+    code = re.sub(r"\bD4GS_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", prototype, code)
+    if code.split() != ["extern", '"C"', "{", "}"] or len(prototypes) != n_api or len(structs) != n_structs:
+        raise ValueError(f"d4gs.h: {len(prototypes)} of {n_api} prototypes and {len(structs)} of {n_structs} structs parsed; "
+                         f"not understood: `{' '.join(code.split())}`")
+    return constants, structs, prototypes
 
 
-class RasterGrads(C.Structure):
-    _fields_ = [(n, F) for n in ("v_render_colors", "v_render_alphas", "isect_grad", "isect_live", "v_means2d", "v_conics",
-                                 "v_depths", "v_opac_act", "v_ctab", "stats_grad_norm_acc", "stats_vis_count",
-                                 "stats_max_radii")] + [("stats_batch_size", C.c_int32), ("stats_update_max_radii", C.c_int32), ("row_mode", C.c_int32),
-                                                        ("v_means2d_abs", F), ("stats_absgrad", C.c_int32)]
-
-
-class Sizes(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("means2d", "depths", "conics", "radii", "opac_act", "ctab", "geom", "tile_rects",
-                                         "tiles_touched", "isect_offsets", "tile_counts", "tile_offsets", "n_isect",
-                                         "scan_ws", "render_colors", "render_alphas", "last_ids", "final_T",
-                                         "isect_grad_row", "bwd_partials", "seg_state", "lazy_ws")] + \
-               [(n, C.c_int32) for n in ("tiles_x", "tiles_y", "channels")] + [("blend_bases", C.c_int64), ("tile_masks", C.c_int64),
-                                                                                                  ("compensations", C.c_int64)]
-
-
-class MoveModelParams(C.Structure):
-    _fields_ = [("w", F * 9), ("b", F * 9), ("time_params", F), ("n_time_params", C.c_int32)]
-
-
-class MoveModelOut(C.Structure):
-    _fields_ = [(n, F) for n in ("enc", "acts", "delta", "RTs", "jac", "times", "dtimes", "deltaT")]
-
-
-class MoveModelGrads(C.Structure):
-    _fields_ = [("v_w", F * 9), ("v_b", F * 9), ("v_time_params", F), ("v_delta", F), ("v_enc", F)]
-
-
-class LeafGrads(C.Structure):
-    _fields_ = [(n, F) for n in ("v_means", "v_quats", "v_scales", "v_opacities", "v_colors", "v_motion_coefs",
-                                 "v_rots", "v_transls", "v_times", "v_RTs", "v_viewmat", "partials")]
-
-
-class ShardBlend(C.Structure):
-    _fields_ = [("S_total", C.c_int32), ("S_local", C.c_int32), ("s_first", C.c_int32), ("s_stride", C.c_int32), ("C", C.c_int32),
-                ("n_pixels", C.c_int64), ("policy", C.POINTER(C.c_int32))]
-
-
-class FrameIO(C.Structure):
-    _fields_ = [(n, F) for n in ("blended", "acc", "renders", "alphas", "means2d", "radii", "n_isect", "background")] + \
-               [("policy", C.POINTER(C.c_int32)), ("near_target", C.c_int64), ("counts_pinned", F)]
-
-
-class FrameGrads(C.Structure):
-    _fields_ = [(n, F) for n in ("v_blended", "v_acc", "v_renders", "v_alphas", "v_means2d", "stats_grad_norm_acc",
-                                 "stats_vis_count", "stats_max_radii")] + \
-               [("stats_batch_size", C.c_int32), ("stats_update_max_radii", C.c_int32), ("row_mode", C.c_int32),
-                ("v_means2d_abs", F), ("stats_absgrad", C.c_int32)]
-
-
-class Poses(C.Structure):
-    _fields_ = [("means", F), ("quats", F), ("transforms", F), ("g_major", C.c_int32)]
-
-
-class AdamRec(C.Structure):
-    _fields_ = [(n, F) for n in ("param", "grad", "exp_avg", "exp_avg_sq", "step")] + [("n", C.c_int64)] + \
-               [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps")]
-
-
-RAW_PARAMS, RAW_COLORS, EXACT_CULL, LAZY_SORT, EXACT_TILES, ABSGRAD, ANTIALIASED = 1, 2, 4, 8, 16, 32, 64
-DEPTH_NONE, DEPTH_ED, DEPTH_D = 0, 1, 2
-ROWS_AUTO, ROWS_DENSE, ROWS_SPARSE = 0, 1, 2
-TILE = 16
-ADAM_CHUNK = 2048  # D4GS_ADAM_CHUNK
-VERSION = 305  # D4GS_VERSION of include/d4gs.h
-GEOM_STRIDE = 8
-
-EXPORTS = (
-    "d4gs_version", "d4gs_copy_counts", "d4gs_last_error", "d4gs_scan_ws_elems", "d4gs_bwd_partials_elems", "d4gs_project_fwd",
-    "d4gs_bin_sort", "d4gs_raster_fwd", "d4gs_raster_bwd", "d4gs_project_bwd", "d4gs_blend_fwd", "d4gs_blend_bwd",
-    "d4gs_points_fwd", "d4gs_points_bwd", "d4gs_poses_fwd", "d4gs_poses_bwd", "d4gs_forward", "d4gs_backward", "d4gs_forward_cpu", "d4gs_backward_cpu", "d4gs_frame_workspace_bytes", "d4gs_frame_workspace_bytes_fwd", "d4gs_blend_shard_partial_fwd", "d4gs_blend_shard_finish_fwd",
-    "d4gs_blend_shard_winner", "d4gs_blend_shard_bwd", "d4gs_control_stats", "d4gs_control_plan", "d4gs_gather_rows", "d4gs_camera_path_fwd", "d4gs_camera_path_bwd",
-    "d4gs_pose_encode", "d4gs_pose_encode_bwd", "d4gs_move_model_fwd", "d4gs_move_model_bwd",
-    "d4gs_photometric_blocks", "d4gs_photometric_maps_elems", "d4gs_photometric_fwd", "d4gs_photometric_bwd", "d4gs_sh_partials_elems", "d4gs_sh_fwd", "d4gs_sh_bwd", "d4gs_query_sizes", "d4gs_profile_enable", "d4gs_profile_collect", "d4gs_measure_peaks",
-    "d4gs_adam_blocks", "d4gs_adam_step", "d4gs_adam_set_grads", "d4gs_adam_step_cpu",
-    "d4gs_trimmed_scratch_words", "d4gs_masked_l1_fwd", "d4gs_masked_l1_bwd", "d4gs_trimmed_l1_fwd", "d4gs_trimmed_l1_bwd",
-    "d4gs_gradient_loss_fwd", "d4gs_gradient_loss_bwd", "d4gs_track_losses_fwd", "d4gs_track_losses_bwd",
-    "d4gs_correlation_fwd", "d4gs_correlation_bwd", "d4gs_backwarp_fwd", "d4gs_backwarp_bwd",
-    "d4gs_aligned_l1_blocks", "d4gs_aligned_l1_fwd", "d4gs_aligned_l1_bwd",
-    "d4gs_motion_regs_workspace_bytes", "d4gs_motion_regs_fwd", "d4gs_motion_regs_bwd",
-    "d4gs_metrics_blocks", "d4gs_masked_metrics",
-    "d4gs_dilate_mask", "d4gs_area_keep_map_elems", "d4gs_area_keep_blocks", "d4gs_area_keep_fwd", "d4gs_area_keep_bwd",
-    "d4gs_mse_blocks", "d4gs_mse_fwd", "d4gs_mse_bwd",
-)
+with open(HEADER) as _f:
+    CONSTANTS, STRUCTS, PROTOTYPES = parse(_f.read())
+# the package's names: VERSION, TILE, GEOM_STRIDE, ADAM_CHUNK, RAW_PARAMS ... ANTIALIASED, DEPTH_*, ROWS_*; Dims ... AdamRec
+globals().update(CONSTANTS)
+globals().update(STRUCTS)
+EXPORTS = tuple(PROTOTYPES)
 
 # Appended to ABI 305 after A/B libraries of older trees were built.  The product library must have them (as every export; build()
 # checks it too); a library named by D4GS_LIB_PATH is held only to the entry points its run calls, so a raster A/B library
@@ -134,6 +125,16 @@ EXPORTS = (
 APPENDED = ("d4gs_photometric_maps_elems",)
 
 _lib = None
+
+
+def bind(cdll: C.CDLL) -> C.CDLL:
+    """Give every entry point of the header its restype and argtypes on a loaded library."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if name in APPENDED and os.environ.get("D4GS_LIB_PATH") and not hasattr(cdll, name):
+            continue
+        fn = getattr(cdll, name)  # AttributeError if the symbol is missing
+        fn.restype, fn.argtypes = restype, argtypes
+    return cdll
 
 
 def lib() -> C.CDLL:
@@ -145,111 +146,9 @@ def lib() -> C.CDLL:
                 "Build it with `python -m deblur4dgs_amd.build` (hipcc, --offload-arch=gfx950)."
             )
         import torch  # noqa: F401  -- torch's bundled HIP runtime must be the one both sides use: load it first
-        L = C.CDLL(LIB_PATH)
-        for name in EXPORTS:
-            if not (name in APPENDED and os.environ.get("D4GS_LIB_PATH")):
-                getattr(L, name)  # AttributeError if the symbol is missing
-        L.d4gs_last_error.restype = C.c_char_p
-        L.d4gs_scan_ws_elems.restype = C.c_size_t
-        L.d4gs_scan_ws_elems.argtypes = [C.c_int64]
-        L.d4gs_bwd_partials_elems.restype = C.c_size_t
-        L.d4gs_bwd_partials_elems.argtypes = [C.POINTER(Dims)]
-        P = C.POINTER
-        vp = C.c_void_p
-        L.d4gs_copy_counts.argtypes = [vp, vp, vp]
-        L.d4gs_measure_peaks.argtypes = [vp, C.c_size_t, P(C.c_double), vp]
-        L.d4gs_project_fwd.argtypes = [P(Dims), P(ProjIn), P(ProjOut), vp]
-        L.d4gs_bin_sort.argtypes = [P(Dims), P(ProjOut), P(Isect), vp]
-        L.d4gs_raster_fwd.argtypes = [P(Dims), P(ProjOut), P(Isect), P(Raster), vp]
-        L.d4gs_raster_bwd.argtypes = [P(Dims), P(ProjOut), P(Isect), P(Raster), P(RasterGrads), vp]
-        L.d4gs_project_bwd.argtypes = [P(Dims), P(ProjIn), P(ProjOut), vp, vp, vp, vp, vp, P(LeafGrads), vp]
-        L.d4gs_points_fwd.argtypes = [P(Dims), P(ProjIn), vp, vp]
-        L.d4gs_points_bwd.argtypes = [P(Dims), P(ProjIn), vp, P(LeafGrads), vp]
-        L.d4gs_poses_fwd.argtypes = [P(Dims), P(ProjIn), P(Poses), vp]
-        L.d4gs_poses_bwd.argtypes = [P(Dims), P(ProjIn), P(Poses), P(LeafGrads), vp]
-        L.d4gs_blend_shard_partial_fwd.argtypes = [P(ShardBlend), vp, vp, vp, vp, vp]
-        L.d4gs_blend_shard_finish_fwd.argtypes = [P(ShardBlend), vp, vp, vp, vp, vp]
-        L.d4gs_blend_shard_winner.argtypes = [P(ShardBlend), vp, vp, vp, vp]
-        L.d4gs_blend_shard_bwd.argtypes = [P(ShardBlend), vp, vp, vp, vp, vp, vp]
-        L.d4gs_frame_workspace_bytes.argtypes = [P(Dims), C.c_int64]
-        L.d4gs_frame_workspace_bytes.restype = C.c_size_t
-        L.d4gs_frame_workspace_bytes_fwd.argtypes = [P(Dims), C.c_int64]
-        L.d4gs_frame_workspace_bytes_fwd.restype = C.c_size_t
-        L.d4gs_forward.argtypes = [P(Dims), P(ProjIn), P(FrameIO), vp, C.c_size_t, C.c_int64, C.c_int64, vp]
-        L.d4gs_backward.argtypes = [P(Dims), P(ProjIn), P(FrameIO), P(FrameGrads), P(LeafGrads), vp, C.c_size_t, C.c_int64,
-                                    C.c_int64, vp]
-        L.d4gs_forward_cpu.argtypes = [P(Dims), P(ProjIn), P(FrameIO)]
-        L.d4gs_backward_cpu.argtypes = [P(Dims), P(ProjIn), P(FrameIO), P(FrameGrads), P(LeafGrads)]
-        L.d4gs_control_stats.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
-        L.d4gs_control_plan.argtypes = [C.c_int32, vp, vp, vp, vp, vp]
-        L.d4gs_gather_rows.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, C.c_int64, C.c_int64, C.c_float, vp]
-        L.d4gs_camera_path_fwd.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, vp, vp, vp, vp]
-        L.d4gs_camera_path_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
-        L.d4gs_pose_encode.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp]
-        L.d4gs_pose_encode_bwd.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
-        L.d4gs_move_model_fwd.argtypes = [vp, C.c_int32, vp, C.c_int32, P(MoveModelParams), C.c_int32, C.c_int32, C.c_float,
-                                          C.c_int32, P(MoveModelOut), vp]
-        L.d4gs_move_model_bwd.argtypes = [P(MoveModelParams), P(MoveModelOut), vp, vp, vp, C.c_int32, C.c_int32,
-                                          P(MoveModelGrads), vp]
-        L.d4gs_query_sizes.argtypes = [P(Dims), P(Sizes)]
-        L.d4gs_photometric_blocks.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-        L.d4gs_photometric_blocks.restype = C.c_int64
-        if hasattr(L, "d4gs_photometric_maps_elems"):
-            L.d4gs_photometric_maps_elems.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-            L.d4gs_photometric_maps_elems.restype = C.c_int64
-        L.d4gs_photometric_fwd.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp,
-                                           vp, vp]
-        L.d4gs_photometric_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                           C.c_float, vp, vp]
-        L.d4gs_sh_partials_elems.argtypes = [C.c_int64]
-        L.d4gs_sh_partials_elems.restype = C.c_int64
-        L.d4gs_sh_fwd.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp]
-        L.d4gs_sh_bwd.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
-        L.d4gs_blend_fwd.argtypes = [C.c_int32, C.c_int64, C.c_int32, P(C.c_int32), vp, vp, vp, vp, vp]
-        L.d4gs_blend_bwd.argtypes = [C.c_int32, C.c_int64, C.c_int32, P(C.c_int32), vp, vp, vp, vp, vp, vp, vp]
-        L.d4gs_adam_blocks.argtypes = [C.c_int64]
-        L.d4gs_adam_blocks.restype = C.c_int64
-        L.d4gs_adam_step.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp]
-        L.d4gs_adam_set_grads.argtypes = [vp, C.c_int32, P(vp), vp]
-        L.d4gs_adam_step_cpu.argtypes = [P(AdamRec), C.c_int32]
-        L.d4gs_trimmed_scratch_words.argtypes = [C.c_int64, C.c_int32]
-        L.d4gs_trimmed_scratch_words.restype = C.c_int64
-        L.d4gs_masked_l1_fwd.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_float, vp, C.c_int64, vp, vp]
-        L.d4gs_masked_l1_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp, vp]
-        L.d4gs_trimmed_l1_fwd.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_float, vp, C.c_int64, vp, vp]
-        L.d4gs_trimmed_l1_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp]
-        L.d4gs_gradient_loss_fwd.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.c_int64, vp, vp]
-        L.d4gs_gradient_loss_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
-        L.d4gs_track_losses_fwd.argtypes = [vp] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_float, vp, C.c_int64, vp, vp]
-        L.d4gs_track_losses_bwd.argtypes = [vp] * 11 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_float, vp, vp]
-        i32 = C.c_int32
-        L.d4gs_correlation_fwd.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, vp]
-        L.d4gs_correlation_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, vp]
-        L.d4gs_backwarp_fwd.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-        L.d4gs_backwarp_bwd.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-        L.d4gs_aligned_l1_blocks.argtypes = [i32, i32]
-        L.d4gs_aligned_l1_blocks.restype = C.c_int64
-        L.d4gs_aligned_l1_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-        L.d4gs_aligned_l1_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-        L.d4gs_motion_regs_workspace_bytes.argtypes = [i32, i32, i32, i32]
-        L.d4gs_motion_regs_workspace_bytes.restype = C.c_size_t
-        L.d4gs_motion_regs_fwd.argtypes = [vp] * 7 + [i32] * 4 + [C.c_float, C.c_float, vp, C.c_size_t, vp, vp]
-        L.d4gs_motion_regs_bwd.argtypes = [vp] * 5 + [i32] * 4 + [C.c_float, C.c_float, vp, C.c_size_t, vp, P(LeafGrads), vp]
-        L.d4gs_metrics_blocks.argtypes = [i32] * 4
-        L.d4gs_metrics_blocks.restype = C.c_int64
-        L.d4gs_masked_metrics.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-        L.d4gs_dilate_mask.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
-        for q in (L.d4gs_area_keep_map_elems, L.d4gs_area_keep_blocks):
-            q.argtypes = [i32] * 5
-            q.restype = C.c_int64
-        L.d4gs_area_keep_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-        L.d4gs_area_keep_bwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
-        L.d4gs_mse_blocks.argtypes = [C.c_int64]
-        L.d4gs_mse_blocks.restype = C.c_int64
-        L.d4gs_mse_fwd.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
-        L.d4gs_mse_bwd.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
-        if L.d4gs_version() != VERSION:
-            raise RuntimeError(f"libd4gs.so version {L.d4gs_version()} != {VERSION} (stale build?)")
+        L = bind(C.CDLL(LIB_PATH))
+        if L.d4gs_version() != CONSTANTS["VERSION"]:
+            raise RuntimeError(f"libd4gs.so version {L.d4gs_version()} != {CONSTANTS['VERSION']} (stale build?)")
         _lib = L
     return _lib
 
@@ -265,6 +164,22 @@ def ptr(t):
         return None
     assert t.is_contiguous(), "d4gs expects contiguous tensors"
     return t.data_ptr()
+
+
+def vp(t):
+    """The same as a c_void_p, without the contiguity check (callers that made the tensor themselves)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def f32c(t):
+    """Detached, fp32, contiguous (None stays None): what an entry point reads."""
+    return None if t is None else t.detach().float().contiguous()
+
+
+def need_gpu(t, who: str, note: str = ""):
+    """The refusal of a CPU tensor, in `who`'s name."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{who} runs on an MI355X (ROCm) device only; got a CPU tensor{note}")
 
 
 def fill(struct, **tensors):
@@ -289,3 +204,8 @@ def raw_stream(index=None) -> int:
     if _RAW_STREAM:
         return _RAW_STREAM(index)
     return torch.cuda.current_stream(index).cuda_stream
+
+
+def stream_of(t):
+    """The current stream of tensor `t`'s device, as an entry point takes it."""
+    return C.c_void_p(raw_stream(t.device.index))

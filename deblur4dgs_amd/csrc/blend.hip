@@ -260,9 +260,6 @@ int d4gs_blend_fwd_impl(int32_t S, int64_t P, int32_t C, const int32_t *policy, 
   return d4gs_check_launch("k_blend_fwd");
 }
 
-int d4gs_blend_bwd_add_impl(int32_t S, int64_t P, int32_t C, const int32_t *policy, const float *renders, const float *out,
-                            const float *v_out, const float *v_acc, float *v_renders, float *v_alphas, const float *add_r,
-                            const float *add_a, hipStream_t stream, const int8_t *win = nullptr);
 int d4gs_blend_bwd_impl(int32_t S, int64_t P, int32_t C, const int32_t *policy, const float *renders, const float *out,
                         const float *v_out, const float *v_acc, float *v_renders, float *v_alphas, hipStream_t stream) {
   return d4gs_blend_bwd_add_impl(S, P, C, policy, renders, out, v_out, v_acc, v_renders, v_alphas, nullptr, nullptr, stream);

@@ -7,50 +7,6 @@
 
 #include "common.h"
 
-int d4gs_project_fwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsProjOut *, hipStream_t);
-int d4gs_bin_sort_impl(const D4gsDims *, const D4gsProjOut *, const D4gsIsect *, hipStream_t);
-int d4gs_raster_fwd_impl(const D4gsDims *, const D4gsProjOut *, const D4gsIsect *, const D4gsRaster *, hipStream_t);
-int d4gs_raster_bwd_impl(const D4gsDims *, const D4gsProjOut *, const D4gsIsect *, const D4gsRaster *,
-                         const D4gsRasterGrads *, const BlendAdj *, hipStream_t);
-int d4gs_project_bwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsProjOut *, const float *, const float *,
-                          const float *, const float *, const float *, const D4gsLeafGrads *, hipStream_t);
-int d4gs_poses_fwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsPoses *, hipStream_t);
-int d4gs_poses_bwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsPoses *, const D4gsLeafGrads *, hipStream_t);
-int d4gs_control_stats_impl(int32_t, int32_t, const float *, const int32_t *, int32_t, int32_t, int32_t, float *,
-                            int64_t *, float *, int32_t, hipStream_t);
-int d4gs_control_plan_impl(int32_t, const uint8_t *, const uint8_t *, int32_t *, int32_t *, hipStream_t);
-int d4gs_gather_rows_impl(const int32_t *, int64_t, int32_t, const float *, float *, int64_t, int64_t, float, hipStream_t);
-int d4gs_blend_fwd_impl(int32_t, int64_t, int32_t, const int32_t *, const float *, const float *, float *, float *, int8_t *,
-                        hipStream_t, const int64_t *n_isect = nullptr, int64_t *counts_pinned = nullptr);
-int d4gs_blend_bwd_impl(int32_t, int64_t, int32_t, const int32_t *, const float *, const float *, const float *,
-                        const float *, float *, float *, hipStream_t);
-
-int d4gs_blend_shard_impl(int, const D4gsShardBlend *, const void *, const void *, const void *, void *, void *, hipStream_t);
-
-int d4gs_pose_encode_impl(const float *, int32_t, const float *, int32_t, float *, hipStream_t);
-int d4gs_camera_path_fwd_impl(const float *, const float *, int32_t, const float *, int32_t, float, int32_t, float *,
-                              float *, float *, float *, float *, hipStream_t);
-int d4gs_camera_path_bwd_impl(const float *, const float *, const float *, const float *, const float *,
-                              const float *, int32_t, int32_t, int32_t, float *, float *, float *, hipStream_t);
-
-int d4gs_move_model_fwd_impl(const float *, int32_t, const float *, int32_t, const float *const *, const float *const *,
-                             int32_t, const float *, int32_t, float, int32_t, float *, float *, float *, float *, float *,
-                             float *, float *, float *, hipStream_t);
-int d4gs_move_model_bwd_impl(const float *, const float *, const float *, const float *, const float *const *,
-                             const float *const *, const float *, const float *, const float *, int32_t, int32_t, int32_t,
-                             float *, float *const *, float *const *, float *, float *, hipStream_t);
-int d4gs_pose_encode_bwd_impl(const float *, int32_t, const float *, int32_t, const float *, float *, float *, hipStream_t);
-
-int d4gs_photometric_fwd_impl(const float *, const float *, const float *, int32_t, int32_t, int32_t, float, float, float *,
-                              float *, float *, hipStream_t);
-int d4gs_photometric_bwd_impl(const float *, const float *, const float *, const float *, const float *, int32_t, int32_t,
-                              int32_t, float, float, float *, hipStream_t);
-
-int d4gs_sh_fwd_impl(int64_t, int32_t, int32_t, const float *, const float *, const float *, const uint8_t *, int32_t, float *,
-                     hipStream_t);
-int d4gs_sh_bwd_impl(int64_t, int32_t, int32_t, const float *, const float *, const float *, const uint8_t *, int32_t,
-                     const float *, float *, float *, float *, float *, hipStream_t);
-
 static thread_local char g_err[512] = "";
 
 // ---- per-kernel event profiler -------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/d4gs.h"
+#include "host.h"  // include/d4gs.h + the host functions that cross translation units
 
 #define D4GS_WAVE 64
 #define D4GS_MAX_K 32         // motion bases held in LDS per block
@@ -15,11 +15,6 @@
 #define D4GS_SSIM_WINDOW                                                                                                   \
   {0.00102838008447911, 0.007598758135239185, 0.03600077212843083, 0.10936068950970002, 0.2130055377112537, 0.26601172486179436, \
    0.2130055377112537,  0.10936068950970002,  0.03600077212843083, 0.007598758135239185, 0.00102838008447911}
-
-// host-side error plumbing (capi.cpp)
-void d4gs_set_error(const char *fmt, ...);
-int d4gs_check_launch(const char *what);
-
 
 // 3x3 row-major helpers -----------------------------------------------------------------------
 __device__ __forceinline__ void mat3_mul(const float *A, const float *B, float *C) {  // C = A B
@@ -373,10 +368,7 @@ __host__ __device__ __forceinline__ int d4gs_seg_len(int len) {
   const int per = (len + D4GS_SEG_UNIT * D4GS_SEG_MAX - 1) / (D4GS_SEG_UNIT * D4GS_SEG_MAX);
   return D4GS_SEG_UNIT * (per > 1 ? per : 1);
 }
-// floats of D4gsRaster.seg_state for one configuration (0: segments are not used for it)
-int64_t d4gs_seg_state_elems(const D4gsDims *d);
-// do the composite kernels of this launch use segments?  (the forward writes the boundary states, the backward replays by segment)
-bool d4gs_seg_on(const D4gsDims *d, const D4gsIsect *isect, const D4gsRaster *r);
+// (host side: d4gs_seg_state_elems and d4gs_seg_on, host.h)
 
 // ---- D4GS_LAZY_SORT: near / far partition of the tile lists (include/d4gs.h) ----------------------------------------
 // lazy_ws (int32): hist [T][NB] (tile, depth bucket) counts | near [T] keys in the near part | pivot [T] last near bucket |
@@ -409,26 +401,6 @@ __device__ __forceinline__ int d4gs_depth_bucket(float depth, uint32_t zmin_bits
   const int k = (int)((off * (uint64_t)nb) / span);
   return k < nb ? k : nb - 1;
 }
-
-// The exposure blend's adjoint (blend.hip k_blend_bwd) folded into the composite backward's prologue by the one-call path (frame.hip):
-// a pixel of sub-sample s takes v_blended / S on the mean channels, the whole of it on a max / min channel iff s is the first
-// sub-sample (of the first S - 1) whose value equals the blended one (k_blend_fwd leaves that index), and v_acc / S on alpha - k_blend_bwd's expressions, bit for bit.
-struct BlendAdj {
-  const float *v_blended;  // [H,W,channels] or NULL
-  const float *v_acc;      // [H,W] or NULL
-  const int8_t *win;       // [H,W,channels] max / min channels: the sub-sample the gradient goes to, -1 = the mean (k_blend_fwd)
-  uint64_t non_mean;       // bit c: channel c is a max / min channel
-};
-bool d4gs_lazy_on(const D4gsDims *d, const D4gsProjOut *out);
-int d4gs_lazy_pivot_launch(const D4gsDims *d, const D4gsProjOut *out, int64_t near_target, hipStream_t stream);
-int d4gs_lazy_far_sort(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect *isect, hipStream_t stream);
-// [S][K][16] time-blended bases (project_bwd.hip: k_bases_table), for callers of d4gs_project_bwd without D4gsProjOut.blend_bases
-int d4gs_bases_table_launch(const D4gsDims *dims, const D4gsProjIn *in, float *btab, hipStream_t stream);
-// Instances per lane of the 1024-lane blocks of k_count_tiles / k_emit (their chunks must agree): 4 - or 1 when 4 would leave
-// fewer blocks than CUs (one or two sub-samples of a few 100 k Gaussians: S = 1, N = 300 k gave 74 blocks for 256 CUs).
-int d4gs_chunk_per_thread(const D4gsDims *d);
-// > 0: the fused scan is in effect for this configuration and this is its chunk count per sub-sample (project_fwd.hip)
-int d4gs_fused_scan_chunks(const D4gsDims *d);
 
 // Optional per-kernel HIP-event profiler (off by default; used by bench.py for the roofline object).
 struct ProfScope {

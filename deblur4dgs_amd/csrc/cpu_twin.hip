@@ -20,9 +20,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../include/d4gs.h"
-
-void d4gs_set_error(const char *fmt, ...);
+#include "host.h"  // include/d4gs.h, d4gs_set_error
 
 namespace {
 

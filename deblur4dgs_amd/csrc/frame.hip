@@ -6,20 +6,6 @@
 // call and one workspace tensor instead of five calls and ~30 tensors per direction).
 #include "common.h"
 
-int d4gs_project_fwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsProjOut *, hipStream_t);
-int d4gs_bin_sort_impl(const D4gsDims *, const D4gsProjOut *, const D4gsIsect *, hipStream_t);
-int d4gs_raster_fwd_impl(const D4gsDims *, const D4gsProjOut *, const D4gsIsect *, const D4gsRaster *, hipStream_t);
-int d4gs_raster_bwd_impl(const D4gsDims *, const D4gsProjOut *, const D4gsIsect *, const D4gsRaster *,
-                         const D4gsRasterGrads *, const BlendAdj *, hipStream_t);
-int d4gs_project_bwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsProjOut *, const float *, const float *,
-                          const float *, const float *, const float *, const D4gsLeafGrads *, hipStream_t);
-int d4gs_blend_fwd_impl(int32_t, int64_t, int32_t, const int32_t *, const float *, const float *, float *, float *, int8_t *,
-                        hipStream_t, const int64_t *n_isect = nullptr, int64_t *counts_pinned = nullptr);
-int d4gs_copy_counts_impl(const int64_t *n_isect, int64_t *host_pinned, hipStream_t stream);
-int d4gs_check_absgrad(const char *who, const D4gsDims *d, const float *v_means2d_abs, int32_t stats_absgrad);
-int d4gs_blend_bwd_add_impl(int32_t, int64_t, int32_t, const int32_t *, const float *, const float *, const float *,
-                            const float *, float *, float *, const float *, const float *, hipStream_t, const int8_t *win = nullptr);
-
 namespace {
 
 struct Carve {

@@ -16,10 +16,6 @@
 #include "common.h"
 #include "reduce.h"
 
-int d4gs_poses_fwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsPoses *, hipStream_t);
-int d4gs_poses_bwd_impl(const D4gsDims *, const D4gsProjIn *, const D4gsPoses *, const D4gsLeafGrads *, hipStream_t);
-size_t d4gs_poses_bwd_partials_bound(const D4gsDims *);  // host arithmetic only: no device is asked
-
 namespace {
 
 constexpr int MB = REDUCE_NT;  // threads per block, all kernels: one lane per Gaussian / basis row

@@ -822,9 +822,7 @@ int d4gs_project_fwd_impl(const D4gsDims *dims, const D4gsProjIn *in, const D4gs
   a.th = (dims->height + D4GS_TILE - 1) / D4GS_TILE;
   const int64_t n_inst = (int64_t)dims->S * dims->N;
   const int64_t n_tiles = (int64_t)dims->S * a.tw * a.th;
-  size_t lds = 0;
-  if (dims->G > 0) lds = sizeof(float) * (((size_t)dims->S * dims->K * 9 + 3) & ~(size_t)3) +
-                         sizeof(float) * (size_t)dims->K * D4GS_PROJ_BLOCK;
+  const size_t lds = fwd_lds_bytes(dims);
   if (lds > 64 * 1024) {
     d4gs_set_error("S*K too large for the LDS-resident bases (S=%d K=%d)", dims->S, dims->K);
     return D4GS_EINVAL;

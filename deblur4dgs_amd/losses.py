@@ -33,20 +33,17 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
+from ._lib import f32c, need_gpu, stream_of, vp
 
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+_WHO = "deblur4dgs_amd.losses"  # the name a CPU tensor is refused under
 
 
 class PhotometricFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, gt, mask, w_l1, w_ssim):
-        if not pred.is_cuda:
-            raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+        need_gpu(pred, _WHO)
         B, H, W, Cc = pred.shape
-        p = pred.detach().float().contiguous()
-        g = gt.detach().float().contiguous()
+        p, g = f32c(pred), f32c(gt)
         m = None if mask is None else mask.detach().float().reshape(B, H, W).contiguous()
         lib = L.lib()
         if not hasattr(lib, "d4gs_photometric_maps_elems"):  # only an override library can lack it (_lib.APPENDED)
@@ -54,9 +51,9 @@ class PhotometricFn(torch.autograd.Function):
         nb = lib.d4gs_photometric_blocks(B, H, W)
         maps = torch.empty(lib.d4gs_photometric_maps_elems(B, H, W), device=p.device, dtype=torch.float32)
         scratch = torch.empty(2 * nb + 3, device=p.device, dtype=torch.float32)
-        stream = C.c_void_p(L.raw_stream(p.device.index))
-        L.check(lib.d4gs_photometric_fwd(_p(p), _p(g), _p(m), B, H, W, Cc, w_l1, w_ssim, _p(maps), _p(scratch),
-                                         _p(scratch[2 * nb:]), stream), "d4gs_photometric_fwd")
+        stream = stream_of(p)
+        L.check(lib.d4gs_photometric_fwd(vp(p), vp(g), vp(m), B, H, W, Cc, w_l1, w_ssim, vp(maps), vp(scratch),
+                                         vp(scratch[2 * nb:]), stream), "d4gs_photometric_fwd")
         ctx.keep = (p, g, m, maps)
         ctx.w = (float(w_l1), float(w_ssim))
         out = scratch[2 * nb:]
@@ -68,8 +65,8 @@ class PhotometricFn(torch.autograd.Function):
         B, H, W, Cc = p.shape
         v = v_loss.detach().float().reshape(1).contiguous()
         out = torch.empty_like(p)
-        stream = C.c_void_p(L.raw_stream(p.device.index))
-        L.check(L.lib().d4gs_photometric_bwd(_p(p), _p(g), _p(m), _p(maps), _p(v), B, H, W, Cc, ctx.w[0], ctx.w[1], _p(out),
+        stream = stream_of(p)
+        L.check(L.lib().d4gs_photometric_bwd(vp(p), vp(g), vp(m), vp(maps), vp(v), B, H, W, Cc, ctx.w[0], ctx.w[1], vp(out),
                                              stream), "d4gs_photometric_bwd")
         return out, None, None, None, None
 
@@ -79,10 +76,6 @@ def photometric_loss(pred, gt, mask=None, w_l1: float = 0.8, w_ssim: float = 0.2
     (the reference's `imgs` and masks are data)."""
     loss, l1, ssim = PhotometricFn.apply(pred, gt, mask, float(w_l1), float(w_ssim))
     return (loss, l1.detach(), ssim.detach()) if return_terms else loss
-
-
-def _f32(t):
-    return t.detach().float().contiguous()
 
 
 def _check_quantile(quantile, upper_open):
@@ -104,8 +97,7 @@ class _TrimmedL1Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, gt, mask, normalize, quantile):
-        if not pred.is_cuda:
-            raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+        need_gpu(pred, _WHO)
         if pred.shape != gt.shape or pred.dim() < 1:
             raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have the same shape, at least 1-D")
         D = pred.shape[-1]
@@ -114,20 +106,20 @@ class _TrimmedL1Fn(torch.autograd.Function):
         n = pred.numel() // D
         if n == 0:
             raise ValueError("no elements (torch.quantile of an empty tensor raises too)")
-        p, g = _f32(pred), _f32(gt)
+        p, g = f32c(pred), f32c(gt)
         m = None
         if mask is not None:
             if mask.numel() != n:
                 raise ValueError(f"mask {tuple(mask.shape)} does not match the {tuple(pred.shape[:-1])} elements of pred")
-            m = _f32(mask).reshape(n)
+            m = f32c(mask).reshape(n)
         lib = L.lib()
         scratch, words = _scratch(n, 1, p.device)
         out = torch.empty(8, device=p.device, dtype=torch.float32)
-        stream = C.c_void_p(L.raw_stream(p.device.index))
+        stream = stream_of(p)
         if m is None:
-            L.check(lib.d4gs_trimmed_l1_fwd(_p(p), _p(g), n, D, quantile, _p(scratch), words, _p(out), stream), "d4gs_trimmed_l1_fwd")
+            L.check(lib.d4gs_trimmed_l1_fwd(vp(p), vp(g), n, D, quantile, vp(scratch), words, vp(out), stream), "d4gs_trimmed_l1_fwd")
         else:
-            L.check(lib.d4gs_masked_l1_fwd(_p(p), _p(g), _p(m), n, D, int(bool(normalize)), quantile, _p(scratch), words, _p(out), stream),
+            L.check(lib.d4gs_masked_l1_fwd(vp(p), vp(g), vp(m), n, D, int(bool(normalize)), quantile, vp(scratch), words, vp(out), stream),
                     "d4gs_masked_l1_fwd")
         ctx.keep = (p, g, m, scratch, out)
         ctx.args = (n, D, quantile, pred.shape, pred.dtype)
@@ -139,12 +131,12 @@ class _TrimmedL1Fn(torch.autograd.Function):
         n, D, quantile, shape, dtype = ctx.args
         v = v_loss.detach().float().reshape(1).contiguous()
         v_pred = torch.empty_like(p)
-        stream = C.c_void_p(L.raw_stream(p.device.index))
+        stream = stream_of(p)
         lib = L.lib()
         if m is None:
-            L.check(lib.d4gs_trimmed_l1_bwd(_p(p), _p(g), _p(scratch), _p(out), _p(v), n, D, _p(v_pred), stream), "d4gs_trimmed_l1_bwd")
+            L.check(lib.d4gs_trimmed_l1_bwd(vp(p), vp(g), vp(scratch), vp(out), vp(v), n, D, vp(v_pred), stream), "d4gs_trimmed_l1_bwd")
         else:
-            L.check(lib.d4gs_masked_l1_bwd(_p(p), _p(g), _p(m), _p(scratch), _p(out), _p(v), n, D, quantile, _p(v_pred), stream),
+            L.check(lib.d4gs_masked_l1_bwd(vp(p), vp(g), vp(m), vp(scratch), vp(out), vp(v), n, D, quantile, vp(v_pred), stream),
                     "d4gs_masked_l1_bwd")
         return v_pred.reshape(shape).to(dtype), None, None, None, None
 
@@ -152,8 +144,7 @@ class _TrimmedL1Fn(torch.autograd.Function):
 class _GradientLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, gt, mask, quantile):
-        if not pred.is_cuda:
-            raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+        need_gpu(pred, _WHO)
         if pred.dim() == 4 and pred.shape[-1] != 1:
             raise NotImplementedError(f"compute_gradient_loss: {pred.shape[-1]} channels (one is supported: [B,H,W] or [B,H,W,1])")
         if pred.dim() not in (3, 4) or pred.shape != gt.shape:
@@ -163,11 +154,11 @@ class _GradientLossFn(torch.autograd.Function):
             raise ValueError("no pixels")
         if mask.numel() != B * H * W:
             raise ValueError(f"mask {tuple(mask.shape)} does not match [B,H,W] = {(B, H, W)}")
-        p, g, m = _f32(pred), _f32(gt), _f32(mask).reshape(B, H, W)
+        p, g, m = f32c(pred), f32c(gt), f32c(mask).reshape(B, H, W)
         scratch, words = _scratch(B * H * W, 2, p.device)
         out = torch.empty(8, device=p.device, dtype=torch.float32)
-        stream = C.c_void_p(L.raw_stream(p.device.index))
-        L.check(L.lib().d4gs_gradient_loss_fwd(_p(p), _p(g), _p(m), B, H, W, quantile, _p(scratch), words, _p(out), stream),
+        stream = stream_of(p)
+        L.check(L.lib().d4gs_gradient_loss_fwd(vp(p), vp(g), vp(m), B, H, W, quantile, vp(scratch), words, vp(out), stream),
                 "d4gs_gradient_loss_fwd")
         ctx.keep = (p, g, m, scratch, out)
         ctx.args = (B, H, W, pred.shape, pred.dtype)
@@ -179,8 +170,8 @@ class _GradientLossFn(torch.autograd.Function):
         B, H, W, shape, dtype = ctx.args
         v = v_loss.detach().float().reshape(1).contiguous()
         v_pred = torch.empty_like(p)
-        stream = C.c_void_p(L.raw_stream(p.device.index))
-        L.check(L.lib().d4gs_gradient_loss_bwd(_p(p), _p(g), _p(m), _p(scratch), _p(out), _p(v), B, H, W, _p(v_pred), stream),
+        stream = stream_of(p)
+        L.check(L.lib().d4gs_gradient_loss_bwd(vp(p), vp(g), vp(m), vp(scratch), vp(out), vp(v), B, H, W, vp(v_pred), stream),
                 "d4gs_gradient_loss_bwd")
         return v_pred.reshape(shape).to(dtype), None, None, None
 
@@ -213,13 +204,13 @@ class _TrackLossesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tracks_3d, pix, rows, vis, weights, tgt_2d, tgt_depth, Ks, quantile):
         n_pixels, N = tracks_3d.numel() // (3 * tracks_3d.shape[-2]), tracks_3d.shape[-2]
-        t = _f32(tracks_3d)
+        t = f32c(tracks_3d)
         n = pix.numel()
         scratch, words = _scratch(n, 2, t.device)
         out = torch.empty(8, device=t.device, dtype=torch.float32)
-        stream = C.c_void_p(L.raw_stream(t.device.index))
-        L.check(L.lib().d4gs_track_losses_fwd(_p(t), _p(pix), _p(rows), _p(vis), _p(weights), _p(tgt_2d), _p(tgt_depth), _p(Ks), n_pixels, N,
-                                              Ks.shape[0], n, quantile, _p(scratch), words, _p(out), stream), "d4gs_track_losses_fwd")
+        stream = stream_of(t)
+        L.check(L.lib().d4gs_track_losses_fwd(vp(t), vp(pix), vp(rows), vp(vis), vp(weights), vp(tgt_2d), vp(tgt_depth), vp(Ks), n_pixels, N,
+                                              Ks.shape[0], n, quantile, vp(scratch), words, vp(out), stream), "d4gs_track_losses_fwd")
         ctx.keep = (t, pix, rows, vis, weights, tgt_2d, tgt_depth, Ks, scratch, out)
         ctx.args = (n_pixels, N, n, quantile, tracks_3d.shape, tracks_3d.dtype)
         return out[5].clone(), out[6].clone()
@@ -230,9 +221,9 @@ class _TrackLossesFn(torch.autograd.Function):
         n_pixels, N, n, quantile, shape, dtype = ctx.args
         v = torch.stack([v_2d.detach().float().reshape(()), v_depth.detach().float().reshape(())])
         v_tracks = torch.empty_like(t)  # zeroed by the entry point, on the stream
-        stream = C.c_void_p(L.raw_stream(t.device.index))
-        L.check(L.lib().d4gs_track_losses_bwd(_p(t), _p(pix), _p(rows), _p(vis), _p(weights), _p(tgt_2d), _p(tgt_depth), _p(Ks), _p(scratch),
-                                              _p(out), _p(v), n_pixels, N, Ks.shape[0], n, quantile, _p(v_tracks), stream),
+        stream = stream_of(t)
+        L.check(L.lib().d4gs_track_losses_bwd(vp(t), vp(pix), vp(rows), vp(vis), vp(weights), vp(tgt_2d), vp(tgt_depth), vp(Ks), vp(scratch),
+                                              vp(out), vp(v), n_pixels, N, Ks.shape[0], n, quantile, vp(v_tracks), stream),
                 "d4gs_track_losses_bwd")
         return (v_tracks.reshape(shape).to(dtype),) + (None,) * 8
 
@@ -276,8 +267,7 @@ def track_losses(tracks_3d, query_tracks_2d, target_Ks, target_tracks_2d, target
     q = _check_quantile(quantile, upper_open=True)
     if not torch.is_tensor(tracks_3d) or tracks_3d.dim() != 5 or tracks_3d.shape[-1] != 3:
         raise ValueError("tracks_3d must be a [B,H,W,N,3] tensor")
-    if not tracks_3d.is_cuda:
-        raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+    need_gpu(tracks_3d, _WHO)
     B, H, W, N, _ = tracks_3d.shape
     if B * H * W * N == 0:
         raise ValueError(f"tracks_3d {tuple(tracks_3d.shape)} is empty")
@@ -295,8 +285,7 @@ def track_losses(tracks_3d, query_tracks_2d, target_Ks, target_tracks_2d, target
             if tuple(x.shape) != want:
                 raise ValueError(f"{name}[{b}] {tuple(x.shape)} must be {want} (N = {N} target frames, {P} queries)")
         for x in (queries[b], Ks[b], tgt2d[b], visibles[b], depths[b]):
-            if not x.is_cuda:
-                raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+            need_gpu(x, _WHO)
         xy = queries[b].detach().to(torch.int64)  # truncated, as the reference's query_pixels
         x, y = xy[:, 0], xy[:, 1]
         inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
@@ -311,31 +300,30 @@ def track_losses(tracks_3d, query_tracks_2d, target_Ks, target_tracks_2d, target
     if not torch.is_tensor(w) or w.dim() not in (1, 2) or w.shape[0] != n:
         raise ValueError(f"track_weights {tuple(w.shape) if torch.is_tensor(w) else type(w)} must be [{n}], [{n},1] or [{n},M]: one row per "
                          "(batch entry, target frame, query)")
-    if not w.is_cuda:
-        raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
-    w = _f32(w)
+    need_gpu(w, _WHO)
+    w = f32c(w)
     if w.dim() == 2:
         w = w.sum(-1)
     vis = torch.cat([v.detach().reshape(-1) != 0 for v in visibles]).to(torch.uint8).contiguous()
-    return _TrackLossesFn.apply(tracks_3d, pix, rows, vis, w.contiguous(), _f32(torch.cat([t.reshape(-1, 2) for t in tgt2d])),
-                                _f32(torch.cat([d.reshape(-1) for d in depths])), _f32(torch.cat(Ks).reshape(-1, 9)), q)
+    return _TrackLossesFn.apply(tracks_3d, pix, rows, vis, w.contiguous(), f32c(torch.cat([t.reshape(-1, 2) for t in tgt2d])),
+                                f32c(torch.cat([d.reshape(-1) for d in depths])), f32c(torch.cat(Ks).reshape(-1, 9)), q)
 
 
 class _MotionRegsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, motion_coefs, rots, transls, scales, ts, w2cs, weight_rot, weight_transl):
         G, K, T, B = means.shape[0], rots.shape[0], rots.shape[1], ts.shape[0]
-        leaves = tuple(_f32(x) for x in (means, motion_coefs, scales, rots, transls))
-        t, w = _f32(ts), _f32(w2cs)
+        leaves = tuple(f32c(x) for x in (means, motion_coefs, scales, rots, transls))
+        t, w = f32c(ts), f32c(w2cs)
         lib = L.lib()
         nbytes = lib.d4gs_motion_regs_workspace_bytes(G, K, T, B)
         if nbytes == 0:
             raise RuntimeError(f"motion_regularizers: unsupported size G={G} K={K} T={T} B={B} (K <= 32, 9 B G <= 2^31 - 1)")
         ws = torch.empty(nbytes, device=means.device, dtype=torch.uint8)
         out = torch.empty(4, device=means.device, dtype=torch.float32)
-        stream = C.c_void_p(L.raw_stream(means.device.index))
-        L.check(lib.d4gs_motion_regs_fwd(*[_p(x) for x in leaves], _p(t), _p(w), G, K, T, B, weight_rot, weight_transl, _p(ws), nbytes,
-                                         _p(out), stream), "d4gs_motion_regs_fwd")
+        stream = stream_of(means)
+        L.check(lib.d4gs_motion_regs_fwd(*[vp(x) for x in leaves], vp(t), vp(w), G, K, T, B, weight_rot, weight_transl, vp(ws), nbytes,
+                                         vp(out), stream), "d4gs_motion_regs_fwd")
         ctx.save_for_backward(*leaves, ws)  # version-checked: a leaf changed in place before the backward raises
         ctx.args = (G, K, T, B, weight_rot, weight_transl, nbytes, tuple(x.dtype for x in (means, motion_coefs, rots, transls, scales)))
         return out[0].clone(), out[1].clone(), out[2].clone(), out[3].clone()
@@ -348,9 +336,9 @@ class _MotionRegsFn(torch.autograd.Function):
         v = torch.stack([x.detach().float().reshape(()) for x in (v_sb, v_st, v_za, v_sv)])
         g = dict(v_means=torch.empty_like(means), v_motion_coefs=torch.empty_like(coefs), v_scales=torch.empty_like(scales),
                  v_rots=torch.empty_like(rots), v_transls=torch.empty_like(transls))
-        stream = C.c_void_p(L.raw_stream(means.device.index))
-        L.check(L.lib().d4gs_motion_regs_bwd(_p(means), _p(coefs), _p(scales), _p(rots), _p(transls), G, K, T, B, weight_rot, weight_transl,
-                                             _p(ws), nbytes, _p(v), C.byref(L.fill(L.LeafGrads(), **g)), stream), "d4gs_motion_regs_bwd")
+        stream = stream_of(means)
+        L.check(L.lib().d4gs_motion_regs_bwd(vp(means), vp(coefs), vp(scales), vp(rots), vp(transls), G, K, T, B, weight_rot, weight_transl,
+                                             vp(ws), nbytes, vp(v), C.byref(L.fill(L.LeafGrads(), **g)), stream), "d4gs_motion_regs_bwd")
         outs = (g["v_means"], g["v_motion_coefs"], g["v_rots"], g["v_transls"], g["v_scales"])
         return tuple(o.to(dt) if need else None for o, dt, need in zip(outs, dtypes, ctx.needs_input_grad[:5])) + (None,) * 4
 
@@ -389,8 +377,7 @@ def motion_regularizers(means, motion_coefs, rots, transls, scales, ts, w2cs, *,
     if B == 0 or w2cs.shape[0] != B:
         raise ValueError(f"{B} times and {w2cs.shape[0]} cameras: one w2c per entry of ts, at least one")
     for x in (means, motion_coefs, rots, transls, scales, ts, w2cs):
-        if not x.is_cuda:
-            raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+        need_gpu(x, _WHO)
     return _MotionRegsFn.apply(means, motion_coefs, rots, transls, scales, ts, w2cs, float(weight_rot), float(weight_transl))
 
 
@@ -401,9 +388,6 @@ def scene_motion_regularizers(model, ts, w2cs, **kw):
         loss += w_smooth_bases * sb + w_smooth_tracks * st + w_z_accel * za + w_scale_var * sv"""
     fg, mb = model.fg.params, model.motion_bases.params
     return motion_regularizers(fg["means"], fg["motion_coefs"], mb["rots"], mb["transls"], fg["scales"], ts, w2cs, **kw)
-
-
-_CPU = "deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor"
 
 
 def _mask_bhw(masks, name="masks"):
@@ -422,12 +406,11 @@ def dilate_mask(masks, kernel_size: int = 9, return_complement: bool = False):
     if k != kernel_size or k < 1 or k % 2 == 0:
         raise ValueError(f"kernel_size={kernel_size}: must be a positive odd integer")
     B, H, W = _mask_bhw(masks)
-    if not masks.is_cuda:
-        raise RuntimeError(_CPU)
-    m = _f32(masks)
+    need_gpu(masks, _WHO)
+    m = f32c(masks)
     out = torch.empty_like(m)
     comp = torch.empty_like(m) if return_complement else None
-    L.check(L.lib().d4gs_dilate_mask(_p(m), B, H, W, k // 2, _p(out), _p(comp), C.c_void_p(L.raw_stream(m.device.index))), "d4gs_dilate_mask")
+    L.check(L.lib().d4gs_dilate_mask(vp(m), B, H, W, k // 2, vp(out), vp(comp), stream_of(m)), "d4gs_dilate_mask")
     return (out, comp) if return_complement else out
 
 
@@ -435,7 +418,7 @@ class _SharpKeepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, mask, reduced, factor):
         B, H, W, Cc = pred.shape
-        p, t, m = _f32(pred), _f32(target), _f32(mask).reshape(B, H, W)
+        p, t, m = f32c(pred), f32c(target), f32c(mask).reshape(B, H, W)
         lib = L.lib()
         dims = (B, H, W, Cc, factor)
         n_map, nb = lib.d4gs_area_keep_map_elems(*dims), lib.d4gs_area_keep_blocks(*dims)
@@ -444,8 +427,8 @@ class _SharpKeepFn(torch.autograd.Function):
         gmap = torch.empty(n_map, device=p.device, dtype=torch.float32)
         partials = torch.empty(nb, device=p.device, dtype=torch.float64)
         out = torch.empty(1, device=p.device, dtype=torch.float32)
-        stream = C.c_void_p(L.raw_stream(p.device.index))
-        L.check(lib.d4gs_area_keep_fwd(_p(p), _p(m), _p(t), int(reduced), *dims, _p(gmap), _p(partials), _p(out), stream), "d4gs_area_keep_fwd")
+        stream = stream_of(p)
+        L.check(lib.d4gs_area_keep_fwd(vp(p), vp(m), vp(t), int(reduced), *dims, vp(gmap), vp(partials), vp(out), stream), "d4gs_area_keep_fwd")
         ctx.save_for_backward(gmap)
         ctx.args = (dims, pred.dtype)
         return out.reshape(())  # (nothing else holds `out`: no clone)
@@ -457,8 +440,8 @@ class _SharpKeepFn(torch.autograd.Function):
         (B, H, W, Cc, factor), dtype = ctx.args
         v = v_loss.detach().float().reshape(1).contiguous()
         v_pred = torch.empty(B, H, W, Cc, device=gmap.device, dtype=torch.float32)
-        stream = C.c_void_p(L.raw_stream(gmap.device.index))
-        L.check(L.lib().d4gs_area_keep_bwd(_p(gmap), _p(v), B, H, W, Cc, factor, _p(v_pred), stream), "d4gs_area_keep_bwd")
+        stream = stream_of(gmap)
+        L.check(L.lib().d4gs_area_keep_bwd(vp(gmap), vp(v), B, H, W, Cc, factor, vp(v_pred), stream), "d4gs_area_keep_bwd")
         return v_pred.to(dtype), None, None, None, None
 
 
@@ -482,8 +465,7 @@ def sharp_keep_loss(pred_sharp, target, masks, factor: int = 4):
         raise ValueError(f"target {tuple(target.shape) if torch.is_tensor(target) else type(target)}: expected {(B, H, W, Cc)} or the reduced "
                          f"{(B, H // factor, W // factor, Cc)}")
     for x in (pred_sharp, target, masks):
-        if not x.is_cuda:
-            raise RuntimeError(_CPU)
+        need_gpu(x, _WHO)
     reduced = tuple(target.shape) == (B, H // factor, W // factor, Cc)  # (factor == 1: both; a 1 x 1 window's mean is the value)
     return _SharpKeepFn.apply(pred_sharp, target, masks, reduced, int(factor))
 
@@ -491,8 +473,8 @@ def sharp_keep_loss(pred_sharp, target, masks, factor: int = 4):
 class _CoverageFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, acc, target):
-        a = _f32(acc)
-        t = None if target is None else _f32(target)
+        a = f32c(acc)
+        t = None if target is None else f32c(target)
         n = a.numel()
         lib = L.lib()
         nb = lib.d4gs_mse_blocks(n)
@@ -500,7 +482,7 @@ class _CoverageFn(torch.autograd.Function):
             raise RuntimeError(f"coverage_loss: {n} elements (at most 2^31 - 1)")
         partials = torch.empty(nb, device=a.device, dtype=torch.float64)
         out = torch.empty(1, device=a.device, dtype=torch.float32)
-        L.check(lib.d4gs_mse_fwd(_p(a), _p(t), n, _p(partials), _p(out), C.c_void_p(L.raw_stream(a.device.index))), "d4gs_mse_fwd")
+        L.check(lib.d4gs_mse_fwd(vp(a), vp(t), n, vp(partials), vp(out), stream_of(a)), "d4gs_mse_fwd")
         ctx.save_for_backward(a, *(() if t is None else (t,)))
         ctx.dtype = acc.dtype
         return out.reshape(())
@@ -512,7 +494,7 @@ class _CoverageFn(torch.autograd.Function):
         t = rest[0] if rest else None
         v = v_loss.detach().float().reshape(1).contiguous()
         v_acc = torch.empty_like(a)
-        L.check(L.lib().d4gs_mse_bwd(_p(a), _p(t), _p(v), a.numel(), _p(v_acc), C.c_void_p(L.raw_stream(a.device.index))), "d4gs_mse_bwd")
+        L.check(L.lib().d4gs_mse_bwd(vp(a), vp(t), vp(v), a.numel(), vp(v_acc), stream_of(a)), "d4gs_mse_bwd")
         return v_acc.to(ctx.dtype), None
 
 
@@ -524,6 +506,6 @@ def coverage_loss(acc, target=None):
         raise ValueError(f"acc {tuple(acc.shape) if torch.is_tensor(acc) else type(acc)}: expected a non-empty [B,H,W] or [B,H,W,1]")
     if target is not None and (not torch.is_tensor(target) or _mask_bhw(target, "target") != tuple(acc.shape[:3])):
         raise ValueError(f"target {tuple(target.shape)} does not match acc {tuple(acc.shape)}")
-    if not acc.is_cuda or (target is not None and not target.is_cuda):
-        raise RuntimeError(_CPU)
+    for x in (acc,) if target is None else (acc, target):
+        need_gpu(x, _WHO)
     return _CoverageFn.apply(acc, target)

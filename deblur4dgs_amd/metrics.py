@@ -15,12 +15,12 @@ backbone weights are not part of this project; importing the name raises an Impo
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 
 from . import _lib as L
+from ._lib import f32c, need_gpu, stream_of, vp
 
 __all__ = ["masked_image_metrics", "compute_psnr", "mPSNR", "mSSIM", "PCK", "ValidationMetrics"]
 
@@ -32,32 +32,23 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _f32(t):
-    return t.detach().float().contiguous()
-
-
 def masked_image_metrics(preds, targets, masks=None, ssim: bool = True):
     """preds, targets [B,H,W,3]; masks None (ones), [B,H,W] (M = 1) or [M,B,H,W], a trailing axis of 1 allowed.
     -> (sse, mask_sum, ssim): float64 device tensors [M,B] - the sum of ((pred - target) * mask)^2 over pixels and channels, the sum of
     the mask, and the mean of the masked SSIM map (None when `ssim` is False; H, W >= 11 otherwise).  Any float dtype and stride is
     accepted.  Runs on the current stream, reads nothing on the host, and its outputs never require a gradient."""
-    if not preds.is_cuda:
-        raise RuntimeError("deblur4dgs_amd.losses runs on an MI355X (ROCm) device only; got a CPU tensor")
+    need_gpu(preds, "deblur4dgs_amd.losses")  # (the name this refusal has always carried)
     if preds.dim() != 4 or preds.shape[-1] != 3 or targets.shape != preds.shape:
         raise ValueError(f"preds and targets must both be [B,H,W,3], got {tuple(preds.shape)} and {tuple(targets.shape)}")
     B, H, W, _ = preds.shape
-    p, t = _f32(preds), _f32(targets)
+    p, t = f32c(preds), f32c(targets)
     m, M = None, 1
     if masks is not None:
         if masks.dim() >= 4 and masks.shape[-1] == 1 and tuple(masks.shape[-4:-1]) == (B, H, W):
             masks = masks[..., 0]
         if masks.dim() not in (3, 4) or tuple(masks.shape[-3:]) != (B, H, W):
             raise ValueError(f"masks must be [B,H,W] or [M,B,H,W] (a trailing 1 allowed) for images {tuple(preds.shape)}, got {tuple(masks.shape)}")
-        m = _f32(masks.to(p.device))
+        m = f32c(masks.to(p.device))
         M = m.shape[0] if m.dim() == 4 else 1
     lib = L.lib()
     nb = lib.d4gs_metrics_blocks(M, B, H, W)
@@ -65,8 +56,8 @@ def masked_image_metrics(preds, targets, masks=None, ssim: bool = True):
         raise ValueError(f"masked_image_metrics: sizes M={M} B={B} H={H} W={W} are empty or beyond the grid")
     scratch = torch.empty(3 * nb + 3 * M * B, device=p.device, dtype=torch.float64)
     out = scratch[3 * nb:]
-    L.check(lib.d4gs_masked_metrics(_p(p), _p(t), _p(m), M, B, H, W, int(bool(ssim)), _p(scratch), _p(out),
-                                    C.c_void_p(L.raw_stream(p.device.index))), "d4gs_masked_metrics")
+    L.check(lib.d4gs_masked_metrics(vp(p), vp(t), vp(m), M, B, H, W, int(bool(ssim)), vp(scratch), vp(out),
+                                    stream_of(p)), "d4gs_masked_metrics")
     out = out.view(M, B, 3)
     return out[..., 0].clone(), out[..., 1].clone(), (out[..., 2].clone() if ssim else None)
 

@@ -23,26 +23,12 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
+from ._lib import need_gpu, stream_of as _stream, vp as _p  # tests reach the two through this module
+
 P_input_ch = 6 * (1 + 2 * 5)  # 66 (move_model.py:12-63: include_input + 5 log-sampled frequencies)
 
 
-def _need_gpu(t: torch.Tensor):
-    if not t.is_cuda:
-        raise RuntimeError("deblur4dgs_amd.MoveModel runs on an MI355X (ROCm) device only; got a CPU tensor "
-                           "(no CPU fallback)")
-
-
 # ------------------------------------------------------------------ fused HIP path (csrc/camera.hip)
-def _stream(t):
-    from . import _lib as L
-
-    return C.c_void_p(L.raw_stream(t.device.index))
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 def pose_encode(R, T):
     """preprocessPose + positional embedding of one pose in one launch: R [3,3] (any row stride), T [3,1] -> [1,66]."""
     from . import _lib as L
@@ -199,7 +185,7 @@ class MoveModel(nn.Module):
     def forward_start_end_mid(self, info, num_cameras=10, mode="uniform", stage="second"):
         """-> RTs [S,3,4] camera deltas, times [1,S] exposure times, deltaT [1,1] (move_model.py:138-166)."""
         R, T, time = info["R"], info["T"], info["timestep"]
-        _need_gpu(R)
+        need_gpu(R, "deblur4dgs_amd.MoveModel", " (no CPU fallback)")
         assert mode == "uniform", "the only mode the reference calls (scene_model.py:254,272)"
         assert num_cameras > 1, "S == 1 divides by S - 1 = 0 upstream (move_model.py:154); render() always passes 11"
         return MoveModelFn.apply(R.float(), T.float(), num_cameras, int(time), float(time), stage == "first",
@@ -209,7 +195,7 @@ class MoveModel(nn.Module):
         """The two head outputs and the signed exposure half-widths (move_model.py:112-135).  The render path does not
         call this (forward_start_end_mid is one fused launch); it exists for the reference's module interface and reads
         the head outputs back from the same fused forward."""
-        _need_gpu(R)
+        need_gpu(R, "deblur4dgs_amd.MoveModel", " (no CPU fallback)")
         from . import _lib as L
 
         if torch.is_grad_enabled() and (R.requires_grad or T.requires_grad or any(p.requires_grad for p in self.parameters())):

@@ -25,7 +25,6 @@ import torch
 from . import _lib as L
 
 _REC = C.sizeof(L.AdamRec)
-_NO_CPU = "deblur4dgs_amd.optim runs on an MI355X (ROCm) device only; got a CPU tensor (no CPU fallback)"
 
 
 def _blocks(n: int) -> int:
@@ -142,8 +141,7 @@ class AdamGroup:
         capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
         items = []
         for h in self.handles:
-            if not _param(h)[1].is_cuda:
-                raise RuntimeError(_NO_CPU)
+            L.need_gpu(_param(h)[1], "deblur4dgs_amd.optim", " (no CPU fallback)")
             rec = _record(h, create=not capturing)
             if rec is None:
                 if capturing and _param(h)[1].grad is not None:
@@ -164,7 +162,7 @@ class AdamGroup:
                 raise RuntimeError("AdamGroup: an lr changed since the last eager step(); call sync() before the capture")
             if items and (grads != self._grads or self._stale):  # gradients born inside this capture: a captured kernel carries their pointers
                 ptrs = (C.c_void_p * len(items))(*[g or None for g in grads])
-                L.check(L.lib().d4gs_adam_set_grads(self._table.data_ptr(), len(items), ptrs, self._stream()), "d4gs_adam_set_grads")
+                L.check(L.lib().d4gs_adam_set_grads(self._table.data_ptr(), len(items), ptrs, L.stream_of(self._table)), "d4gs_adam_set_grads")
                 self._stale = True  # on the device the pointers arrive with the first replay; an eager sync() uploads before that
         elif grads == self._grads and hyper == self._hyper and not self._stale:
             return
@@ -172,9 +170,6 @@ class AdamGroup:
         self._keep = [(p, g, st["exp_avg"], st["exp_avg_sq"], st["step"]) for h, p, g, st, hy in items]  # what the table points at
         if not capturing:
             self._upload(items)
-
-    def _stream(self):
-        return C.c_void_p(L.raw_stream(self._device.index))
 
     def _rebuild(self, items, structure):
         self._structure, self._index = structure, {id(it[0]): i for i, it in enumerate(items)}
@@ -226,7 +221,7 @@ class AdamGroup:
         lib, n = L.lib(), len(self._counts)
         if only is None:
             L.check(lib.d4gs_adam_step(self._table.data_ptr(), n, self._prefix.data_ptr(), self._prefix_host[-1],
-                                       self._block_steps.data_ptr(), self._stream()), "d4gs_adam_step")
+                                       self._block_steps.data_ptr(), L.stream_of(self._table)), "d4gs_adam_step")
             return
         i = self._index.get(id(only))
         if i is None:
@@ -234,7 +229,7 @@ class AdamGroup:
                 raise ValueError("this handle does not belong to the group")
             return  # neither state nor gradient yet
         L.check(lib.d4gs_adam_step(self._table.data_ptr() + i * _REC, 1, self._single.data_ptr() + 8 * i, self._counts[i],
-                                   self._block_steps.data_ptr() + 4 * self._prefix_host[i], self._stream()), "d4gs_adam_step")
+                                   self._block_steps.data_ptr() + 4 * self._prefix_host[i], L.stream_of(self._table)), "d4gs_adam_step")
 
     @torch.no_grad()
     def step(self):

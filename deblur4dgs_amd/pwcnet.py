@@ -13,44 +13,27 @@ one loss kernel; nothing in it waits on the host, so a step that holds it can be
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 from torch import nn
 
 from . import _lib as L
+from ._lib import f32c, need_gpu, stream_of, vp
 
 NEIGHBOURS = 81  # the 9 x 9 search window of the cost volume
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _f32(t):
-    return t.detach().float().contiguous()
-
-
-def _need_gpu(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"deblur4dgs_amd.pwcnet.{what} runs on an MI355X (ROCm) device only; got a CPU tensor")
-
-
-def _stream(t):
-    return C.c_void_p(L.raw_stream(t.device.index))
 
 
 class _CorrelationFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, first, second, slope):
-        _need_gpu(first, "correlation")
+        need_gpu(first, "deblur4dgs_amd.pwcnet.correlation")
         if first.dim() != 4 or first.shape != second.shape:
             raise ValueError(f"first {tuple(first.shape)} and second {tuple(second.shape)} must both be [B,C,H,W]")
         B, Cc, H, W = first.shape
-        f, s = _f32(first), _f32(second)
+        f, s = f32c(first), f32c(second)
         out = torch.empty(B, NEIGHBOURS, H, W, device=f.device, dtype=torch.float32)
-        L.check(L.lib().d4gs_correlation_fwd(_p(f), _p(s), B, Cc, H, W, slope, _p(out), _stream(f)), "d4gs_correlation_fwd")
+        L.check(L.lib().d4gs_correlation_fwd(vp(f), vp(s), B, Cc, H, W, slope, vp(out), stream_of(f)), "d4gs_correlation_fwd")
         ctx.keep = (f, s, out if slope != 1.0 else None)
         ctx.args = (slope, first.dtype, second.dtype)
         return out
@@ -60,10 +43,10 @@ class _CorrelationFn(torch.autograd.Function):
         f, s, out = ctx.keep
         slope, dt_first, dt_second = ctx.args
         B, Cc, H, W = f.shape
-        v = _f32(v_out)
+        v = f32c(v_out)
         v_first = torch.empty_like(f) if ctx.needs_input_grad[0] else None
         v_second = torch.empty_like(s) if ctx.needs_input_grad[1] else None
-        L.check(L.lib().d4gs_correlation_bwd(_p(f), _p(s), _p(out), _p(v), B, Cc, H, W, slope, _p(v_first), _p(v_second), _stream(f)),
+        L.check(L.lib().d4gs_correlation_bwd(vp(f), vp(s), vp(out), vp(v), B, Cc, H, W, slope, vp(v_first), vp(v_second), stream_of(f)),
                 "d4gs_correlation_bwd")
         return (None if v_first is None else v_first.to(dt_first)), (None if v_second is None else v_second.to(dt_second)), None
 
@@ -78,16 +61,16 @@ def correlation(first, second, negative_slope: float = 1.0):
 class _BackwarpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, flow):
-        _need_gpu(inp, "backwarp")
+        need_gpu(inp, "deblur4dgs_amd.pwcnet.backwarp")
         if inp.dim() != 4 or flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] != inp.shape[0] or flow.shape[2:] != inp.shape[2:]:
             raise ValueError(f"input {tuple(inp.shape)} must be [B,C,H,W] and flow {tuple(flow.shape)} [B,2,H,W]")
         B, Cc, H, W = inp.shape
         if H < 2 or W < 2:
             raise ValueError(f"backwarp: H={H}, W={W} (each must be at least 2: the flow is scaled by W / (W - 1))")
-        x, fl = _f32(inp), _f32(flow)
+        x, fl = f32c(inp), f32c(flow)
         out = torch.empty_like(x)
         mask = torch.empty(B, 1, H, W, device=x.device, dtype=torch.float32)
-        L.check(L.lib().d4gs_backwarp_fwd(_p(x), _p(fl), B, Cc, H, W, _p(out), _p(mask), _stream(x)), "d4gs_backwarp_fwd")
+        L.check(L.lib().d4gs_backwarp_fwd(vp(x), vp(fl), B, Cc, H, W, vp(out), vp(mask), stream_of(x)), "d4gs_backwarp_fwd")
         ctx.keep = (fl,)
         ctx.args = (inp.shape, inp.dtype)
         ctx.mark_non_differentiable(mask)
@@ -97,9 +80,9 @@ class _BackwarpFn(torch.autograd.Function):
     def backward(ctx, v_out, _v_mask):
         fl, = ctx.keep
         (B, Cc, H, W), dtype = ctx.args
-        v = _f32(v_out)
+        v = f32c(v_out)
         v_in = torch.empty_like(v)
-        L.check(L.lib().d4gs_backwarp_bwd(_p(fl), _p(v), B, Cc, H, W, _p(v_in), _stream(v)), "d4gs_backwarp_bwd")
+        L.check(L.lib().d4gs_backwarp_bwd(vp(fl), vp(v), B, Cc, H, W, vp(v_in), stream_of(v)), "d4gs_backwarp_bwd")
         return v_in.to(dtype), None
 
 
@@ -123,7 +106,7 @@ get_backwarp = backwarp  # the reference's name
 class _AlignedL1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, flow, target, mask):
-        _need_gpu(pred, "aligned_l1")
+        need_gpu(pred, "deblur4dgs_amd.pwcnet.aligned_l1")
         if pred.dim() != 4 or pred.shape[1] != 3 or target.shape != pred.shape:
             raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} must both be [P,3,H,W]")
         P, _, H, W = pred.shape
@@ -135,12 +118,12 @@ class _AlignedL1Fn(torch.autograd.Function):
         if mask is not None:
             if mask.numel() != P * H * W:
                 raise ValueError(f"mask {tuple(mask.shape)} must hold one value per pair and pixel: [P,H,W] or [P,1,H,W]")
-            m = _f32(mask).reshape(P, H, W)
-        p, fl, t = _f32(pred), _f32(flow), _f32(target)
+            m = f32c(mask).reshape(P, H, W)
+        p, fl, t = f32c(pred), f32c(flow), f32c(target)
         lib = L.lib()
         partials = torch.empty(P * lib.d4gs_aligned_l1_blocks(H, W), device=p.device, dtype=torch.float64)
         losses = torch.empty(P, device=p.device, dtype=torch.float32)
-        L.check(lib.d4gs_aligned_l1_fwd(_p(p), _p(fl), _p(t), _p(m), P, H, W, _p(partials), _p(losses), _stream(p)), "d4gs_aligned_l1_fwd")
+        L.check(lib.d4gs_aligned_l1_fwd(vp(p), vp(fl), vp(t), vp(m), P, H, W, vp(partials), vp(losses), stream_of(p)), "d4gs_aligned_l1_fwd")
         ctx.keep = (p, fl, t, m)
         ctx.args = (pred.dtype, target.dtype)
         return losses
@@ -149,10 +132,10 @@ class _AlignedL1Fn(torch.autograd.Function):
     def backward(ctx, v_losses):
         p, fl, t, m = ctx.keep
         P, _, H, W = p.shape
-        v = _f32(v_losses).reshape(P)
+        v = f32c(v_losses).reshape(P)
         v_pred = torch.empty_like(p)
         v_target = torch.empty_like(t) if ctx.needs_input_grad[2] else None
-        L.check(L.lib().d4gs_aligned_l1_bwd(_p(p), _p(fl), _p(t), _p(m), _p(v), P, H, W, _p(v_pred), _p(v_target), _stream(p)),
+        L.check(L.lib().d4gs_aligned_l1_bwd(vp(p), vp(fl), vp(t), vp(m), vp(v), P, H, W, vp(v_pred), vp(v_target), stream_of(p)),
                 "d4gs_aligned_l1_bwd")
         return v_pred.to(ctx.args[0]), None, (None if v_target is None else v_target.to(ctx.args[1])), None
 

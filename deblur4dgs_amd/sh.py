@@ -7,19 +7,10 @@ Masked entries, and entries whose direction has zero length (gsplat: NaN), give 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib as L
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _f32c(t):
-    return None if t is None else t.detach().to(torch.float32).contiguous()
+from ._lib import f32c, need_gpu, stream_of, vp
 
 
 class SHFn(torch.autograd.Function):
@@ -28,17 +19,16 @@ class SHFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, degree, points, origin, coeffs, masks, clamp):
-        if not points.is_cuda:
-            raise RuntimeError("deblur4dgs_amd.sh runs on an MI355X (ROCm) device only; got a CPU tensor (no CPU fallback)")
+        need_gpu(points, "deblur4dgs_amd.sh", " (no CPU fallback)")
         for t in (origin, coeffs, masks):
             if t is not None and t.device != points.device:
                 raise RuntimeError(f"deblur4dgs_amd.sh: every tensor must be on {points.device}, got one on {t.device}")
-        p, o, c = _f32c(points), _f32c(origin), _f32c(coeffs)
+        p, o, c = f32c(points), f32c(origin), f32c(coeffs)
         N, K = c.shape[0], c.shape[1]
         rgb = torch.empty(N, 3, device=p.device, dtype=torch.float32)
         if N > 0:
-            stream = C.c_void_p(L.raw_stream(p.device.index))
-            L.check(L.lib().d4gs_sh_fwd(N, K, degree, _p(p), _p(o), _p(c), _p(masks), int(clamp), _p(rgb), stream),
+            stream = stream_of(p)
+            L.check(L.lib().d4gs_sh_fwd(N, K, degree, vp(p), vp(o), vp(c), vp(masks), int(clamp), vp(rgb), stream),
                     "d4gs_sh_fwd")
         ctx.keep = (p, o, c, masks)
         ctx.cfg = (degree, int(clamp), points.dtype, None if origin is None else origin.dtype, coeffs.dtype)
@@ -58,9 +48,9 @@ class SHFn(torch.autograd.Function):
             v_o = (torch.empty if N > 0 else torch.zeros)(3, device=dev, dtype=torch.float32)
         if N > 0 and (need_p or need_o or need_c):
             partials = torch.empty(L.lib().d4gs_sh_partials_elems(N), device=dev, dtype=torch.float32) if need_o else None
-            stream = C.c_void_p(L.raw_stream(dev.index))
-            L.check(L.lib().d4gs_sh_bwd(N, K, degree, _p(p), _p(o), _p(c), _p(masks), clamp, _p(_f32c(v_rgb)), _p(v_c),
-                                        _p(v_p), _p(v_o), _p(partials), stream), "d4gs_sh_bwd")
+            stream = stream_of(p)
+            L.check(L.lib().d4gs_sh_bwd(N, K, degree, vp(p), vp(o), vp(c), vp(masks), clamp, vp(f32c(v_rgb)), vp(v_c),
+                                        vp(v_p), vp(v_o), vp(partials), stream), "d4gs_sh_bwd")
         cast = lambda g, dt: None if g is None else g.to(dt)  # noqa: E731
         return None, cast(v_p, p_dtype), cast(v_o, o_dtype), cast(v_c, c_dtype), None, None
 

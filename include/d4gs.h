@@ -12,7 +12,12 @@
  * ctypes / pybind binding of this path binds (see INTEGRATION.md for the stub).
  *
  * Conventions
- *  - plain C, no torch types; every pointer is a DEVICE pointer unless marked [host].
+ *  - plain C, no torch types.  A descriptor struct (`const D4gsDims *dims`, `D4gsSizes *sizes`, ...) is passed as a HOST pointer,
+ *    unless its parameter is marked [device].  Every other pointer, parameter or struct field, is a DEVICE pointer unless it is
+ *    marked [host] (the CPU twins say so of all of theirs in their own paragraph).  The marks are read by machine: this header is
+ *    the one statement of the ABI, and deblur4dgs_amd/_lib.py derives the ctypes binding from it.  A mark
+ *    counts where it stands in the inline comment of its own declaration - after a parameter and before its comma, or after a
+ *    field's semicolon on the same line; block comments above a declaration are prose.
  *  - the library never allocates, frees or synchronises: outputs and scratch are caller-provided,
  *    every call only enqueues work on `stream` (a hipStream_t passed as void*).
  *  - return 0 on success, negative D4GS_E* on error; message via d4gs_last_error() (thread-local).
@@ -569,12 +574,13 @@ D4GS_API int64_t d4gs_adam_blocks(int64_t n);
 /* table [n_records], block_prefix [n_records + 1] and block_steps [n_blocks]: device memory (table 8-byte, the others 4-byte
  * aligned).  n_records == 0 launches nothing.  D4GS_EINVAL for a NULL or misaligned argument or a negative count; what the
  * records hold cannot be checked from the host - the kernel itself never touches an element at or beyond `n`. */
-D4GS_API int d4gs_adam_step(const D4gsAdamRec *table, int32_t n_records, const int32_t *block_prefix, int32_t n_blocks,
-                            float *block_steps, void *stream);
+D4GS_API int d4gs_adam_step(const D4gsAdamRec *table /* [device] */, int32_t n_records, const int32_t *block_prefix,
+                            int32_t n_blocks, float *block_steps, void *stream);
 /* table[r].grad = grads[r] for r < n_records, by kernels that carry the pointers as ARGUMENTS (64 per launch): the one way to
  * point a device table at gradient tensors that were born inside a stream capture - a captured copy from host memory would be
  * read again at every replay.  grads [host] [n_records]. */
-D4GS_API int d4gs_adam_set_grads(D4gsAdamRec *table, int32_t n_records, const float *const *grads, void *stream);
+D4GS_API int d4gs_adam_set_grads(D4gsAdamRec *table /* [device] */, int32_t n_records, const float *const *grads /* [host] */,
+                                 void *stream);
 /* CPU twin: the same per-element function on HOST pointers (table and everything it points to), one thread, no stream, no block
  * tables (t = *step + 1).  Never a fallback.  Validates every record: D4GS_EINVAL for a NULL param / exp_avg / exp_avg_sq /
  * step, a pointer that is not 4-byte aligned, or n < 0. */

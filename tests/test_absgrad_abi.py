@@ -57,8 +57,6 @@ def test_query_sizes_row_width(lib):
         assert lib.d4gs_query_sizes(C.byref(d), C.byref(z)) == 0 and z.isect_grad_row == 6 + nch
         d.flags = L.ABSGRAD
         assert lib.d4gs_query_sizes(C.byref(d), C.byref(z)) == 0 and z.isect_grad_row == 8 + nch
-    lib.d4gs_frame_workspace_bytes.restype = C.c_size_t
-    lib.d4gs_frame_workspace_bytes.argtypes = [C.POINTER(L.Dims), C.c_int64]
     d0 = L.Dims(N=1000, S=2, D=3, width=64, height=48, depth_mode=1)
     d1 = L.Dims(N=1000, S=2, D=3, width=64, height=48, depth_mode=1, flags=L.ABSGRAD)
     cap = 100000
@@ -106,8 +104,6 @@ def test_one_call_backward_rejects_inconsistent_absgrad_arguments(lib, flag, ext
     from deblur4dgs_amd import _lib as L
 
     d, pin, io, leaf = _frame_args(L.ABSGRAD if flag else 0)
-    lib.d4gs_frame_workspace_bytes.restype = C.c_size_t
-    lib.d4gs_frame_workspace_bytes.argtypes = [C.POINTER(L.Dims), C.c_int64]
     ws = lib.d4gs_frame_workspace_bytes(C.byref(d), 1000)
     fg = L.FrameGrads(v_renders=FAKE, v_means2d=FAKE, **extra)
     assert lib.d4gs_backward(C.byref(d), C.byref(pin), C.byref(io), C.byref(fg), C.byref(leaf), C.c_void_p(FAKE), ws, 1000, 0,

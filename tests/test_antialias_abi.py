@@ -15,12 +15,7 @@ from tests.test_absgrad_abi import FAKE, ROOT, _fields, _frame_args, _raster_bwd
 def lib():
     from deblur4dgs_amd import _lib as L
 
-    lib = L.lib()
-    lib.d4gs_last_error.restype = C.c_char_p
-    for fn in (lib.d4gs_frame_workspace_bytes, lib.d4gs_frame_workspace_bytes_fwd):
-        fn.restype = C.c_size_t
-        fn.argtypes = [C.POINTER(L.Dims), C.c_int64]
-    return lib
+    return L.lib()
 
 
 def test_flag_value_and_appended_fields():

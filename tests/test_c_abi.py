@@ -11,9 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def lib():
-    from deblur4dgs_amd import build
+    from deblur4dgs_amd import _lib, build
 
-    return C.CDLL(build.build())
+    return _lib.bind(C.CDLL(build.build()))  # a raw handle with the header's signatures
 
 
 def _declared():
@@ -49,7 +49,6 @@ def test_version_and_error_paths(lib):
     from deblur4dgs_amd import _lib as L
 
     assert lib.d4gs_version() == 305
-    lib.d4gs_last_error.restype = C.c_char_p
     assert lib.d4gs_project_fwd(None, None, None, None) == -1  # D4GS_EINVAL, no HIP call made
     assert b"NULL" in lib.d4gs_last_error()
     d = L.Dims(N=10, G=20, K=1, T=1, S=1, D=3, width=16, height=16)  # G > N
@@ -64,7 +63,6 @@ def test_raster_bwd_rejects_misaligned_scratch_before_any_hip_call(lib):
     the host (fake addresses - nothing is dereferenced before the validation)."""
     from deblur4dgs_amd import _lib as L
 
-    lib.d4gs_last_error.restype = C.c_char_p
     d = L.Dims(N=10, G=0, K=0, T=0, S=1, D=3, width=16, height=16)
     fake = 0x10000
     pout = L.ProjOut(**{n: fake for n, _ in L.ProjOut._fields_})
@@ -84,7 +82,6 @@ def test_exact_tiles_and_alignment_contracts_are_checked_before_any_hip_call(lib
     and written as 16-byte words by d4gs_project_fwd / d4gs_project_bwd.  Both are host-side D4GS_EINVAL (fake addresses)."""
     from deblur4dgs_amd import _lib as L
 
-    lib.d4gs_last_error.restype = C.c_char_p
     fake = 0x10000
     d = L.Dims(N=10, G=0, K=0, T=0, S=1, D=3, width=16, height=16, flags=L.EXACT_CULL | L.EXACT_TILES)
     pout = L.ProjOut(**{**{n: fake for n, _ in L.ProjOut._fields_}, "tile_masks": 0})
@@ -115,7 +112,6 @@ def test_last_error_is_thread_local(lib):
 
     from deblur4dgs_amd import _lib as L
 
-    lib.d4gs_last_error.restype = C.c_char_p
     bar = threading.Barrier(3)
     seen = {}
 
@@ -141,27 +137,13 @@ def test_last_error_is_thread_local(lib):
 
 
 def test_struct_layouts_match_header():
-    """ctypes mirrors must have exactly the fields of the C structs, in order."""
-    from deblur4dgs_amd import _lib as L
+    """The binding's structs have the layout the COMPILER gives the header's: size of every struct, offset and width of every field,
+    all 16 structs (tests/test_abi_binding.py holds the probe).  Until the binding was derived from the header this test compared field
+    names of 7 hand-written mirrors with the header's; on a derived binding that compares the header with itself, and the probe is
+    strictly stronger: it also pins types and padding."""
+    from tests.test_abi_binding import check_struct_layouts
 
-    src = open(os.path.join(ROOT, "include", "d4gs.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-    def fields(name):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src, re.S).group(1)
-        out = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            decl = re.sub(r"^(const\s+)?(float|int32_t|int64_t|uint64_t|uint8_t|void)\s*", "", decl)
-            out += [x.strip().lstrip("*").strip() for x in decl.split(",")]
-        return out
-
-    for cname, cls in (("D4gsDims", L.Dims), ("D4gsProjIn", L.ProjIn), ("D4gsProjOut", L.ProjOut),
-                       ("D4gsIsect", L.Isect), ("D4gsRaster", L.Raster), ("D4gsRasterGrads", L.RasterGrads),
-                       ("D4gsLeafGrads", L.LeafGrads)):
-        assert fields(cname) == [f[0] for f in cls._fields_], cname
+    check_struct_layouts()
 
 
 def test_product_never_imports_oracle():
@@ -177,7 +159,6 @@ def test_query_sizes_is_a_pure_host_call(lib):
     """d4gs_query_sizes (the workspace query of SURVEY 8b) needs no GPU: element counts of every caller-owned buffer."""
     from deblur4dgs_amd import _lib as L
 
-    lib.d4gs_query_sizes.argtypes = [C.POINTER(L.Dims), C.POINTER(L.Sizes)]
     d = L.Dims(N=1000, G=400, K=6, T=24, S=8, D=3, width=100, height=50, depth_mode=L.DEPTH_ED)
     z = L.Sizes()
     assert lib.d4gs_query_sizes(C.byref(d), C.byref(z)) == 0
@@ -189,9 +170,6 @@ def test_query_sizes_is_a_pure_host_call(lib):
     assert (z.tile_counts, z.tile_offsets, z.n_isect) == (2 * 8 * tw * th, 8 * tw * th + 1, 4)
     assert z.render_colors == 8 * 50 * 100 * 4 and z.render_alphas == z.last_ids == z.final_T == 8 * 50 * 100
     assert z.isect_grad_row == 6 + 4
-    lib.d4gs_scan_ws_elems.restype = C.c_size_t
-    lib.d4gs_scan_ws_elems.argtypes = [C.c_int64]
-    lib.d4gs_bwd_partials_elems.restype = C.c_size_t
     assert z.scan_ws == lib.d4gs_scan_ws_elems(SN) and z.bwd_partials == lib.d4gs_bwd_partials_elems(C.byref(d))
     bad = L.Dims(N=10, G=20, K=1, T=1, S=1, D=3, width=16, height=16)
     assert lib.d4gs_query_sizes(C.byref(bad), C.byref(z)) == -1 and lib.d4gs_query_sizes(C.byref(d), None) == -1
@@ -200,21 +178,14 @@ def test_query_sizes_is_a_pure_host_call(lib):
 def test_one_call_entry_points_validate_before_any_hip_call(lib):
     from deblur4dgs_amd import _lib as L
 
-    lib.d4gs_last_error.restype = C.c_char_p
-    lib.d4gs_frame_workspace_bytes.restype = C.c_size_t
-    lib.d4gs_frame_workspace_bytes.argtypes = [C.POINTER(L.Dims), C.c_int64]
     d = L.Dims(N=1000, G=0, K=0, T=0, S=2, D=3, width=64, height=48, depth_mode=1)
     small, big = lib.d4gs_frame_workspace_bytes(C.byref(d), 0), lib.d4gs_frame_workspace_bytes(C.byref(d), 100000)
     assert 0 < small < big and small % 256 == 0 and big - small >= 100000 * (8 + 12 + 4 * 10)  # keys, ids, gradient rows
     assert lib.d4gs_frame_workspace_bytes(C.byref(L.Dims(N=-1, S=1, D=3, width=8, height=8)), 0) == 0
-    lib.d4gs_forward.argtypes = [C.POINTER(L.Dims), C.POINTER(L.ProjIn), C.POINTER(L.FrameIO), C.c_void_p, C.c_size_t, C.c_int64,
-                                 C.c_int64, C.c_void_p]
     fake = 0x10000
     pin = L.ProjIn(**{n: fake for n, _ in L.ProjIn._fields_})
     io = L.FrameIO(**{n: fake for n in ("renders", "alphas", "means2d", "radii", "n_isect")})
     # the forward alone needs only the prefix of the workspace in front of the backward's scratch (validation / viewer renders)
-    lib.d4gs_frame_workspace_bytes_fwd.restype = C.c_size_t
-    lib.d4gs_frame_workspace_bytes_fwd.argtypes = [C.POINTER(L.Dims), C.c_int64]
     fwd_small = lib.d4gs_frame_workspace_bytes_fwd(C.byref(d), 0)
     assert 0 < fwd_small < small and fwd_small % 256 == 0
     assert small - fwd_small >= 4 * (2 * 64 * 48 * 5 + 2 * 1000 * 4)  # at least the image-gradient stack and the per-instance rows

@@ -17,9 +17,7 @@ G, K, T, B = 100, 5, 8, 2
 def lib():
     from deblur4dgs_amd import _lib as L
 
-    lib = L.lib()
-    lib.d4gs_last_error.restype = C.c_char_p
-    return lib
+    return L.lib()
 
 
 def test_new_symbols_are_declared_bound_and_exported_and_the_version_is_305(lib):

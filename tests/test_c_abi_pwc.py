@@ -7,20 +7,9 @@ import pytest
 
 @pytest.fixture(scope="module")
 def lib():
-    from deblur4dgs_amd import build
+    from deblur4dgs_amd import _lib, build
 
-    L = C.CDLL(build.build())
-    L.d4gs_last_error.restype = C.c_char_p
-    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-    L.d4gs_correlation_fwd.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp]
-    L.d4gs_correlation_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
-    L.d4gs_backwarp_fwd.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    L.d4gs_backwarp_bwd.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    L.d4gs_aligned_l1_blocks.argtypes = [i32, i32]
-    L.d4gs_aligned_l1_blocks.restype = C.c_int64
-    L.d4gs_aligned_l1_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    L.d4gs_aligned_l1_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    return L
+    return _lib.bind(C.CDLL(build.build()))
 
 
 A = 0x10000  # a fake, aligned device address

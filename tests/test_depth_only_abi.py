@@ -13,12 +13,7 @@ from tests.test_absgrad_abi import FAKE, _frame_args, _raster_bwd_args
 def lib():
     from deblur4dgs_amd import _lib as L
 
-    lib = L.lib()
-    lib.d4gs_last_error.restype = C.c_char_p
-    for fn in (lib.d4gs_frame_workspace_bytes, lib.d4gs_frame_workspace_bytes_fwd):
-        fn.restype = C.c_size_t
-        fn.argtypes = [C.POINTER(L.Dims), C.c_int64]
-    return lib
+    return L.lib()
 
 
 def _dims(depth_mode, flags=0, **kw):

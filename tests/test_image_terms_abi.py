@@ -32,9 +32,7 @@ DOUBLES = {("d4gs_area_keep_fwd", 10), ("d4gs_mse_fwd", 3)}  # the 8-byte aligne
 def lib():
     from deblur4dgs_amd import _lib as L
 
-    lib = L.lib()
-    lib.d4gs_last_error.restype = C.c_char_p
-    return lib
+    return L.lib()
 
 
 def put(fn, i, v):

@@ -1,7 +1,6 @@
 """The trimmed losses without a GPU: the fp64 restatement the GPU tests compare against (tests/trimmed_ref.py) is pinned to values
 recorded from the reference's own functions (tests/golden/trimmed_losses.npz, written by tests/golden/gen_trimmed_losses.py), and
 the new C entry points validate their arguments before any GPU call."""
-import ctypes as C
 import importlib.util
 import math
 import os
@@ -100,7 +99,6 @@ def test_scratch_query(lib):
 
 def test_bad_arguments_return_einval_before_any_gpu_call(lib):
     """Fake addresses: nothing is dereferenced or launched before the validation (this runs without a GPU)."""
-    lib.d4gs_last_error.restype = C.c_char_p
     fake, n = 0x10000, 100
     words = lib.d4gs_trimmed_scratch_words(n, 1)
     nan, inf = float("nan"), float("inf")
