@@ -2,6 +2,7 @@
 
 Appending an entry point, a struct or a constant means editing the header and nothing here (a new struct: one line of
 STRUCT_NAMES).  The type rules and the [host] / [device] marks are in `_ctype`; DESIGN.md section 23 has them as a table.
+Prototypes under D4GS_API are PROTOTYPES / EXPORTS; the scene-initialisation block under D4GS_INIT_API is INIT_PROTOTYPES.
 
 The product path has NO fallback: if the HIP library is missing this module raises at first use, and every
 entry point raises RuntimeError on a non-zero return code with `d4gs_last_error()`.
@@ -50,10 +51,12 @@ def _ctype(base, stars, mark, structs, text):
     raise ValueError(f"d4gs.h: cannot bind the type of `{text}`")
 
 
-def parse(text):
+def parse(text, init=None):
     """-> (constants, structs, prototypes) of the header `text`: {name without D4GS_: int}, {Python name: ctypes.Structure},
     {entry point: (restype, argtypes)}.  Strict: whatever is left of the header once every enum, struct and prototype has been
-    taken out, and every declaration that does not parse completely, raises ValueError with the offending text."""
+    taken out, and every declaration that does not parse completely, raises ValueError with the offending text.
+    `prototypes` is the D4GS_API table.  The declarations under D4GS_INIT_API (scene initialisation) are read
+    by the same rules, counted in the same way, and land in the dict `init` when one is given."""
     def comment(m):  # an inline comment (code before it on its line) leaves its mark as a token; every other comment is blank
         inline = text[text.rfind("\n", 0, m.start()) + 1:m.start()].strip()
         found = re.search(r"\[(host|device)\]", m.group()) if inline else None
@@ -62,8 +65,9 @@ def parse(text):
     code = re.sub(r"/\*.*?\*/", comment, text, flags=re.S)
     constants = {k: int(v) for k, v in re.findall(r"^#define D4GS_(\w+)[ \t]+(-?\d+)[ \t]*$", code, flags=re.M)}
     n_api, n_structs = len(re.findall(r"\bD4GS_API\b", code)) - 1, len(re.findall(r"\btypedef\s+struct\b", code))
+    n_init = max(len(re.findall(r"\bD4GS_INIT_API\b", code)) - 1, 0)  # (a header without the block: none)
     code = re.sub(r"^[ \t]*#.*$", "", code, flags=re.M)
-    structs, by_c_name, prototypes = {}, {}, {}
+    structs, by_c_name, prototypes, init = {}, {}, {}, {} if init is None else init
 
     def enum(m):
         for item in filter(None, (x.strip() for x in m.group(1).split(","))):
@@ -89,7 +93,7 @@ def parse(text):
         by_c_name[name] = structs[STRUCT_NAMES[name]] = type(STRUCT_NAMES[name], (C.Structure,), {"_fields_": fields})
         return ""
 
-    def prototype(m):
+    def prototype(m, table=prototypes):
         ret, name, params = (x.strip() for x in m.groups())
         restype = C.c_char_p if re.fullmatch(r"const\s+char\s*\*", ret) else None if ret == "void" else _SCALARS.get(ret)
         if restype is None and ret != "void":
@@ -100,20 +104,24 @@ def parse(text):
             if not all(found):
                 raise ValueError(f"d4gs.h: cannot parse a parameter of `{m.group().strip()}`")
             argtypes = [_ctype(p.group(1), p.group(2), p.group(4), by_c_name, p.group()) for p in found]
-        prototypes[name] = (restype, argtypes)
+        table[name] = (restype, argtypes)
         return ""
 
     code = re.sub(r"\benum\s*\{([^{}]*)\}\s*;", enum, code)
     code = re.sub(r"\btypedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, code)
     code = re.sub(r"\bD4GS_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", prototype, code)
+    code = re.sub(r"\bD4GS_INIT_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, init), code)
+    if len(init) != n_init:
+        raise ValueError(f"d4gs.h: {len(init)} of {n_init} D4GS_INIT_API prototypes parsed; not understood: `{' '.join(code.split())}`")
     if code.split() != ["extern", '"C"', "{", "}"] or len(prototypes) != n_api or len(structs) != n_structs:
         raise ValueError(f"d4gs.h: {len(prototypes)} of {n_api} prototypes and {len(structs)} of {n_structs} structs parsed; "
                          f"not understood: `{' '.join(code.split())}`")
     return constants, structs, prototypes
 
 
+INIT_PROTOTYPES = {}  # the D4GS_INIT_API block: scene_init.py's entry points, bound like the rest
 with open(HEADER) as _f:
-    CONSTANTS, STRUCTS, PROTOTYPES = parse(_f.read())
+    CONSTANTS, STRUCTS, PROTOTYPES = parse(_f.read(), INIT_PROTOTYPES)
 # the package's names: VERSION, TILE, GEOM_STRIDE, ADAM_CHUNK, RAW_PARAMS ... ANTIALIASED, DEPTH_*, ROWS_*; Dims ... AdamRec
 globals().update(CONSTANTS)
 globals().update(STRUCTS)
@@ -129,8 +137,8 @@ _lib = None
 
 def bind(cdll: C.CDLL) -> C.CDLL:
     """Give every entry point of the header its restype and argtypes on a loaded library."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        if name in APPENDED and os.environ.get("D4GS_LIB_PATH") and not hasattr(cdll, name):
+    for name, (restype, argtypes) in {**PROTOTYPES, **INIT_PROTOTYPES}.items():
+        if (name in APPENDED or name in INIT_PROTOTYPES) and os.environ.get("D4GS_LIB_PATH") and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)  # AttributeError if the symbol is missing
         fn.restype, fn.argtypes = restype, argtypes

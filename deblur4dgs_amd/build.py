@@ -30,7 +30,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 # cycles for two operations against 2.5 for one) and parks ~40 duplicated operands in VGPR pairs: 256 + 30 registers instead of 128
 FILE_FLAGS = {"project_bwd.hip": ["-fno-slp-vectorize"],
               # raster_fwd: the four unrolled composite steps per list read pair up into v_pk_* math behind a dozen v_mov shuffles
-              "raster_fwd.hip": ["-fno-slp-vectorize"]}
+              "raster_fwd.hip": ["-fno-slp-vectorize"],
+              # scene_init: k_knn's two queries per lane pair up into v_pk_add / v_pk_mul behind three v_mov per candidate
+              "scene_init.hip": ["-fno-slp-vectorize"]}
 
 
 def _cuid(src: str) -> str:

@@ -775,6 +775,67 @@ D4GS_API int64_t d4gs_mse_blocks(int64_t n); /* 0: illegal size */
 D4GS_API int d4gs_mse_fwd(const float *a, const float *t, int64_t n, double *partials, float *out, void *stream);
 D4GS_API int d4gs_mse_bwd(const float *a, const float *t, const float *v_loss, int64_t n, float *v_a, void *stream);
 
+/* Scene initialisation (appended; D4GS_VERSION unchanged): what flow3d/init_utils.py needs from cupy, cuML and sklearn to turn 3-D
+ * tracks and static points into a first scene.  The block is declared under a macro of its own: D4GS_API stays the table of the
+ * frame, its losses and its metrics (the binding keeps it as EXPORTS), D4GS_INIT_API is the one-off preprocessing
+ * (INIT_PROTOTYPES); both are exported, parsed by the same strict rules and bound by the same call.  Every pointer below is DEVICE
+ * memory; tensors are contiguous; nothing is read on the host, no atomics, every launch is on `stream`, and every result is bitwise
+ * reproducible from run to run.  D4GS_EINVAL, by host arithmetic alone and before any HIP call, for a NULL required pointer, a
+ * misaligned pointer, a size < 1 or beyond the limits each entry names.
+ *
+ * Track features (batched_interp_masked, init_utils.py:594-654, and the velocity directions of :571-574): xyz [G,T,3] fp32, visible
+ * [G,T] uint8 (non-zero = visible).  xyz_interp [G,T,3] (may be NULL): per track and coordinate np.interp over the visible frames -
+ * linear between neighbouring visible frames, constant before the first and after the last - evaluated in double and rounded once; a
+ * visible frame's value is copied bit for bit.  Two deviations from the reference: a track WITHOUT a visible frame keeps its input
+ * row (the reference's concatenation interpolates it across the neighbouring tracks in memory; its callers filter such tracks out
+ * first), and the whole row is one interpolation for any T (the reference restarts at every 64-frame chunk, an artefact of its
+ * batching).  vel_dirs [G,3(T-1)] (may be NULL; T >= 2 then, else D4GS_EINVAL): vel_dirs[g, 3t + c] = v_c / (|v| + 1e-5) with
+ * v = xyz_interp[g,t+1] - xyz_interp[g,t] taken from the double values before they are rounded.  G T 3 <= 2^31 - 1.
+ *
+ * k nearest neighbours (loss_utils.py:93-99, sklearn's brute force; exact): points [N,3] fp32, 1 <= k <= D4GS_KNN_MAX_K, N >= k + 1
+ * (sklearn raises below that) and N <= 2^24.  dists [N,k] fp32 ascending, idx [N,k] int32 (may be NULL): the k nearest OTHER points.
+ * Self is excluded by index, so an exact duplicate of the query is a neighbour at distance 0 - the distances of the reference's "drop
+ * column 0".  The squared distance is the sum of the three squared coordinate differences (never |a|^2 + |b|^2 - 2 a.b), its root
+ * is taken once at the end; among equal distances the lower index comes first.  Candidates are staged in LDS D4GS_KNN_TILE at a time;
+ * above N = D4GS_KNN_SPLIT_MIN the candidate range is split over d4gs_knn_splits(N) blocks per query block and a second pass merges
+ * their lists.  workspace: d4gs_knn_workspace_bytes(N, k) bytes, 16-byte aligned (0: illegal N or k; never 0 for a legal pair).
+ * Non-finite coordinates: unspecified neighbours, no fault.
+ *
+ * k-means (Lloyd iterations; cuML's KMeans in the reference, :577-582): x [G,D] fp32, centres [K,D] fp32 and labels [G] int32 are
+ * read AND written, 1 <= K <= D4GS_KMEANS_MAX_K, K D <= 12288 (the centres live in LDS), G D <= 2^31 - 1.  One iteration: every row
+ * takes the label of its nearest centre by the fp32 sum of squared differences (ties: the lowest index, as argmin), then every centre
+ * becomes the mean of its rows - sums in double in the fixed order of csrc/reduce.h (thread t of block b adds rows 256 b + t +
+ * 256 d4gs_kmeans_blocks(G) i in increasing i, block sum, ordered total over the blocks); a centre without rows keeps its value.
+ * `iters` >= 1 iterations run back to back on the stream.  changed [1] int32: how many labels the LAST iteration changed (the first
+ * one compares with the labels passed in).  scratch: d4gs_kmeans_scratch_bytes(G, D, K) bytes, 8-byte aligned (0: illegal sizes).
+ * The initial centres are the caller's: the package seeds them by k-means++, so its labels are a Lloyd fixed point of that seed and
+ * NOT cuML's labels (cuML's random initialisation cannot be matched and is no contract).
+ *
+ * Procrustes moments (the sums under solve_procrustes for every (basis, frame) pair of init_motion_params_with_procrustes, :188-240,
+ * in one launch): xyz [G,T,3], weights [G,T], conf [G,T] fp32; order [G] int32 = the track indices sorted by cluster, seg [K+1] int32
+ * = where each cluster starts in order (entries outside 0..G - 1 / 0..G are skipped / clamped, never followed).  For cluster n and
+ * frame t, over the tracks p of the cluster, with u = ((w[p,cano_t] w[p,t]) (conf[p,cano_t] + conf[p,t])) / 2, src = xyz[p,cano_t],
+ * dst = xyz[p,t]:   out[n,t,0] = sum u, [1..3] = sum u src, [4..6] = sum u dst, [7 + 3 i + j] = sum u dst_i src_j
+ * out [K,T,16] doubles, 8-byte aligned; every product and sum in double, one block per pair in the block-sum order of reduce.h (thread
+ * t adds members t, t + 256, ... in increasing order).  0 <= cano_t < T, K <= 65535, G T 3 <= 2^31 - 1.  The reference's logged
+ * err / err_before are not computed. */
+#define D4GS_INIT_API __attribute__((visibility("default")))
+#define D4GS_KNN_MAX_K 8
+#define D4GS_KNN_TILE 1024
+#define D4GS_KNN_SPLIT_MIN 4096
+#define D4GS_KMEANS_MAX_K 64
+D4GS_INIT_API int d4gs_track_features(const float *xyz, const uint8_t *visible, int32_t G, int32_t T, float *xyz_interp, float *vel_dirs,
+                                      void *stream);
+D4GS_INIT_API int32_t d4gs_knn_splits(int64_t N);                    /* 0: illegal N */
+D4GS_INIT_API int64_t d4gs_knn_workspace_bytes(int64_t N, int32_t k); /* 0: illegal N or k */
+D4GS_INIT_API int d4gs_knn(const float *points, int32_t N, int32_t k, float *dists, int32_t *idx, void *workspace, void *stream);
+D4GS_INIT_API int64_t d4gs_kmeans_blocks(int64_t G);                                     /* 0: illegal G */
+D4GS_INIT_API int64_t d4gs_kmeans_scratch_bytes(int64_t G, int32_t D, int32_t K); /* 0: illegal sizes */
+D4GS_INIT_API int d4gs_kmeans_step(const float *x, int32_t G, int32_t D, int32_t K, int32_t iters, float *centres, int32_t *labels,
+                                   int32_t *changed, void *scratch, void *stream);
+D4GS_INIT_API int d4gs_procrustes_moments(const float *xyz, const float *weights, const float *conf, const int32_t *order,
+                                          const int32_t *seg, int32_t G, int32_t T, int32_t K, int32_t cano_t, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
