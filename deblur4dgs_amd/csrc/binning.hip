@@ -19,7 +19,7 @@ struct EmitArgs {
   const int32_t *tile_rects;
   const int32_t *tiles_touched;
   const int32_t *isect_offsets;
-  int32_t *isect_offsets_out;  // fused scan (d4gs_fused_scan_chunks): this kernel computes and writes the offsets
+  int32_t *isect_offsets_out;  // fused scan (FrontPlan.fused_chunks): this kernel computes and writes the offsets
   const int32_t *chunk_base;   // [S * nchunks] exclusive scan of k_count_tiles' chunk sums
   int nchunks;                 // 0: offsets come from k_scan_apply
   int32_t *tile_cursor;  // tile_counts: [0,T) splats per tile, [T,2T) slot cursors (zero on entry)
@@ -34,8 +34,8 @@ struct EmitArgs {
   const uint64_t *tile_masks;  // D4GS_EXACT_TILES: per instance, the tiles of its rectangle that are binned (0: all of them); or NULL
 };
 
-// Slot assignment without per-intersection global atomics.  Block b takes 4096 instances of sub-sample b % S
-// (1024 lanes x 4, the chunks of k_count_tiles):
+// Slot assignment without per-intersection global atomics.  Block b takes one chunk of sub-sample b % S
+// (D4GS_CHUNK_THREADS lanes x EMIT_PER_THREAD instances, the chunks of k_count_tiles: FrontPlan, host.h):
 //   1. histogram of the chunk's tile touches in LDS;
 //   2. ONE returning global atomic per non-empty tile reserves the chunk's run inside that tile's (unsorted) list;
 //      the bin becomes the absolute first slot of the run;
@@ -43,13 +43,12 @@ struct EmitArgs {
 // Which slot a key lands in is irrelevant (k_tile_sort orders the list by depth, then emission index), so nothing
 // has to be carried from the counting pass, splats of any footprint take the same path, and the 8-byte key stores
 // of a block fall into short contiguous runs.  Tile grids too big for the LDS histogram use global cursors.
-constexpr int EMIT_THREADS = 1024;
 // LZ (D4GS_LAZY_SORT): 1 - only the keys of the depth buckets up to each tile's pivot are emitted, to the front of the tile's list (the
 // near part, lazy.near[t] keys); 2 - launched by d4gs_lazy_far_sort between the two composite passes: the other keys, behind the near
 // part, but only of the tiles the first pass flagged (the far part of a list whose tile saturated inside its near part is never
 // written, let alone sorted).  A pair's emission index does not depend on which launch writes it.
-template <int EMIT_PER_THREAD, int LZ>  // EMIT_PER_THREAD = d4gs_chunk_per_thread(dims), like k_count_tiles
-__global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
+template <int EMIT_PER_THREAD, int LZ>  // EMIT_PER_THREAD = FrontPlan.pt, like k_count_tiles
+__global__ void __launch_bounds__(D4GS_CHUNK_THREADS) k_emit(const EmitArgs a) {
   extern __shared__ int bins[];  // [tiles] (+ LZ: [tiles] pivots)
   if (lists_overflowed(a.n_dev, a.cap, a.max_hint)) return;
   constexpr bool LAZY = LZ != 0;
@@ -59,7 +58,7 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
   const bool lds = a.use_lds;
   __shared__ int fbox[4];  // LZ == 2: bounding box of the sub-sample's flagged tiles
   if (lds) {
-    for (int z = tid; z < tiles; z += EMIT_THREADS) bins[z] = 0;
+    for (int z = tid; z < tiles; z += D4GS_CHUNK_THREADS) bins[z] = 0;
     if (LZ == 2 && tid == 0) fbox[0] = fbox[1] = 1 << 30, fbox[2] = fbox[3] = -1;
     __syncthreads();
   }
@@ -67,7 +66,7 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
   // LZ: the sub-sample's pivots, staged once per block (one read per key otherwise); 2: "never" for the tiles that were not flagged
   int *piv = bins + tiles;
   if (LAZY) {
-    for (int z = tid; z < tiles; z += EMIT_THREADS) {
+    for (int z = tid; z < tiles; z += D4GS_CHUNK_THREADS) {
       int p = a.lazy.pivot[tbase + z];
       if (LZ == 2) {
         if (a.lazy.flag[tbase + z] == 1) {  // (2: an earlier d4gs_raster_fwd on these lists emitted + sorted that far part)
@@ -90,52 +89,40 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
   // instance by instance the kernel walked 2 x EMIT_PER_THREAD dependent round trips to memory (count -> branch ->
   // rectangle -> histogram, four times over) at 19 % VALU utilisation.  (The empty asm statements keep the compiler from sinking
   // the loads back behind the branches.)
-#ifndef D4GS_EMIT_BATCHED_LOADS
-#define D4GS_EMIT_BATCHED_LOADS 1
-#endif
 #pragma unroll
   for (int q = 0; q < EMIT_PER_THREAD; q++) {
-    const int g = (chunk * EMIT_PER_THREAD + q) * EMIT_THREADS + tid;
+    const int g = (chunk * EMIT_PER_THREAD + q) * D4GS_CHUNK_THREADS + tid;
     cnt[q] = 0, msk[q] = 0, rx[q] = 0, ry[q] = 0, dep[q] = 0.f;
     if (g < a.d.N) cnt[q] = a.tiles_touched[(int64_t)s * a.d.N + g];
   }
-  if constexpr (D4GS_EMIT_BATCHED_LOADS) {
 #pragma unroll
-    for (int q = 0; q < EMIT_PER_THREAD; q++) {
-      const int g = (chunk * EMIT_PER_THREAD + q) * EMIT_THREADS + tid;
-      if (g < a.d.N) {
-        const int64_t i = (int64_t)s * a.d.N + g;
-        const int2 rc = *reinterpret_cast<const int2 *>(a.tile_rects + i * 2);
-        rx[q] = rc.x, ry[q] = rc.y;
-        dep[q] = a.depths[i];
-        if (a.tile_masks) msk[q] = a.tile_masks[i];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < EMIT_PER_THREAD; q++) {
-      uint32_t ml = (uint32_t)msk[q], mh = (uint32_t)(msk[q] >> 32);
-      asm volatile("" : "+v"(cnt[q]), "+v"(rx[q]), "+v"(ry[q]), "+v"(dep[q]), "+v"(ml), "+v"(mh));
-      msk[q] = ((uint64_t)mh << 32) | ml;
+  for (int q = 0; q < EMIT_PER_THREAD; q++) {
+    const int g = (chunk * EMIT_PER_THREAD + q) * D4GS_CHUNK_THREADS + tid;
+    if (g < a.d.N) {
+      const int64_t i = (int64_t)s * a.d.N + g;
+      const int2 rc = *reinterpret_cast<const int2 *>(a.tile_rects + i * 2);
+      rx[q] = rc.x, ry[q] = rc.y;
+      dep[q] = a.depths[i];
+      if (a.tile_masks) msk[q] = a.tile_masks[i];
     }
   }
 #pragma unroll
   for (int q = 0; q < EMIT_PER_THREAD; q++) {
-    const int g = (chunk * EMIT_PER_THREAD + q) * EMIT_THREADS + tid;
+    uint32_t ml = (uint32_t)msk[q], mh = (uint32_t)(msk[q] >> 32);
+    asm volatile("" : "+v"(cnt[q]), "+v"(rx[q]), "+v"(ry[q]), "+v"(dep[q]), "+v"(ml), "+v"(mh));
+    msk[q] = ((uint64_t)mh << 32) | ml;
+  }
+#pragma unroll
+  for (int q = 0; q < EMIT_PER_THREAD; q++) {
+    const int g = (chunk * EMIT_PER_THREAD + q) * D4GS_CHUNK_THREADS + tid;
     if (g < a.d.N) {
-      const int64_t i = (int64_t)s * a.d.N + g;
       if (cnt[q] > 0) {
-        if constexpr (!D4GS_EMIT_BATCHED_LOADS) {
-          const int2 rc = *reinterpret_cast<const int2 *>(a.tile_rects + i * 2);
-          rx[q] = rc.x, ry[q] = rc.y;
-          dep[q] = a.depths[i];
-        }
         const int x0 = rx[q] & 0xffff, x1 = rx[q] >> 16, y0 = ry[q] & 0xffff, y1 = ry[q] >> 16;
         if (LZ == 2 && (x0 > fbox[2] || x1 <= fbox[0] || y0 > fbox[3] || y1 <= fbox[1])) {
           cnt[q] = 0;  // touches no flagged tile
           continue;
         }
         bkq[q] = LAZY ? d4gs_depth_bucket(dep[q], zlo, zhi, a.lazy.nb) : 0;
-        if constexpr (!D4GS_EMIT_BATCHED_LOADS) msk[q] = a.tile_masks ? a.tile_masks[i] : 0;
         if (cnt[q] > 0 && !a.tile_masks) msk[q] = 0;
         if (lds && msk[q]) {  // D4GS_EXACT_TILES: bit (ty - y0) * 8 + (tx - x0)
           for (uint64_t m = msk[q]; m; m &= m - 1) {
@@ -154,7 +141,7 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
   }
   if (lds) {
     __syncthreads();
-    for (int z = tid; z < tiles; z += EMIT_THREADS) {
+    for (int z = tid; z < tiles; z += D4GS_CHUNK_THREADS) {
       const int c = bins[z];
       if (c == 0) continue;
       const int t = tbase + z;
@@ -168,7 +155,7 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
   // instance order (q-major, then lane) - exactly what k_scan_apply would have written
   uint32_t ebase[EMIT_PER_THREAD];
   if (LZ != 2 && a.nchunks) {
-    __shared__ int wsum[EMIT_THREADS / 64];
+    __shared__ int wsum[D4GS_CHUNK_THREADS / 64];
     int carry = a.chunk_base[s * a.nchunks + chunk];
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
@@ -183,7 +170,7 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
       __syncthreads();
       int base = 0, tot = 0;
 #pragma unroll
-      for (int w = 0; w < EMIT_THREADS / 64; w++) {
+      for (int w = 0; w < D4GS_CHUNK_THREADS / 64; w++) {
         const int x = wsum[w];
         base += w < wave ? x : 0;
         tot += x;
@@ -191,14 +178,14 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(const EmitArgs a) {
       ebase[q] = (uint32_t)(carry + base + inc - cnt[q]);
       carry += tot;
       __syncthreads();
-      const int g = (chunk * EMIT_PER_THREAD + q) * EMIT_THREADS + tid;
+      const int g = (chunk * EMIT_PER_THREAD + q) * D4GS_CHUNK_THREADS + tid;
       if (g < a.d.N) a.isect_offsets_out[(int64_t)s * a.d.N + g] = (int32_t)ebase[q];
     }
   }
 #pragma unroll
   for (int q = 0; q < EMIT_PER_THREAD; q++) {
     if (cnt[q] == 0) continue;
-    const int g = (chunk * EMIT_PER_THREAD + q) * EMIT_THREADS + tid;
+    const int g = (chunk * EMIT_PER_THREAD + q) * D4GS_CHUNK_THREADS + tid;
     const int64_t i = (int64_t)s * a.d.N + g;
     const int x0 = rx[q] & 0xffff, x1 = rx[q] >> 16, y0 = ry[q] & 0xffff, y1 = ry[q] >> 16;
     const uint64_t hi = (uint64_t)__float_as_uint(dep[q]) << 32;
@@ -508,11 +495,10 @@ __global__ void __launch_bounds__(1024) k_tile_sort(const SortArgs a) {
 // global memory.  (Round 1 had only the 16 KB and 128 KB classes: a scene whose lists run to ~4 k keys sorted them one workgroup
 // of 4 waves per CU - 1.54 ms on cfg2 with 4x larger splats.)  pass: 0 whole lists, 1 / 2 the near / flagged far parts
 // (D4GS_LAZY_SORT).
-int launch_sorts(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect *isect, int pass, hipStream_t stream) {
-  const int tw = (dims->width + D4GS_TILE - 1) / D4GS_TILE, th = (dims->height + D4GS_TILE - 1) / D4GS_TILE;
-  const int n_tiles = dims->S * tw * th;
+int launch_sorts(const D4gsDims *dims, const FrontPlan &fp, const D4gsProjOut *proj, const D4gsIsect *isect, int pass, hipStream_t stream) {
+  const int n_tiles = fp.n_tiles;
   LazyWs lw{};
-  if (pass) lw = d4gs_lazy_carve(proj->lazy_ws, dims->S, tw * th);
+  if (pass) lw = d4gs_lazy_carve(proj->lazy_ws, dims->S, fp.tiles);
   // per call: the attribute belongs to the (function, device) pair and a process may drive several GPUs
   (void)hipFuncSetAttribute((const void *)k_tile_sort, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
   const int64_t longest = isect->max_tile_count > 0 ? isect->max_tile_count : isect->n_isect;
@@ -522,7 +508,7 @@ int launch_sorts(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect 
   const bool merge_short = pass == 0 && longest > CHUNK && isect->n_isect >= (int64_t)768 * n_tiles;  // (capacity ~ 1.25 x the count)
   // ... and the other way round (round 6): where the lists are mostly SHORT, the few of 513 ... 2 048 keys are sorted by the workgroup of
   // k_tile_sort_w that owns them (all four waves, 16 KB of LDS) instead of a launch of the first LDS class for their sake.
-  static const bool no_long = getenv("D4GS_SORT_NO_MERGE_LONG") != nullptr;  // A/B hook
+  static const bool no_long = getenv("D4GS_SORT_NO_MERGE_LONG") != nullptr;  // the tests' hook for the first LDS class
   // Only whole-list passes whose lists average at most ~512 keys (capacity / tiles < 640): where many lists are long - the near / far
   // passes of a lazy sort, cfg5: 609 -> 739 us - four of them queue up inside one workgroup.  Measured (profiles/r06_ab_sort_merge_long.txt):
   // the reference's training shape 56.4 -> 46.8 us, cfg3 97.8 -> 87.7.
@@ -543,61 +529,34 @@ int launch_sorts(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect 
   return d4gs_check_launch("k_tile_sort");
 }
 
-}  // namespace
-
-namespace {
-
-int fill_emit_args(EmitArgs &e, const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect *isect) {
+// k_emit's arguments but for the lazy workspace (the callers below carve it)
+EmitArgs emit_args(const D4gsDims *dims, const FrontPlan &fp, const D4gsProjOut *proj, const D4gsIsect *isect) {
+  EmitArgs e;
   e.d = *dims;
   e.depths = proj->depths;
   e.tile_rects = proj->tile_rects;
   e.tiles_touched = proj->tiles_touched;
   e.isect_offsets = proj->isect_offsets;
-  e.isect_offsets_out = proj->isect_offsets, e.chunk_base = proj->scan_ws, e.nchunks = d4gs_fused_scan_chunks(dims);
+  e.isect_offsets_out = proj->isect_offsets, e.chunk_base = proj->scan_ws, e.nchunks = fp.fused_chunks;
   e.tile_cursor = proj->tile_counts;
   e.tile_masks = (dims->flags & D4GS_EXACT_TILES) ? proj->tile_masks : nullptr;
   e.tile_offsets = proj->tile_offsets;
   e.keys = isect->keys;
   e.gid_of_emit = isect->gid_of_emit;
-  e.tw = (dims->width + D4GS_TILE - 1) / D4GS_TILE;
-  e.th = (dims->height + D4GS_TILE - 1) / D4GS_TILE;
+  e.tw = fp.tw, e.th = fp.th;
   e.n_dev = proj->n_isect, e.cap = isect->n_isect, e.max_hint = isect->max_tile_count;
-  const int per_block = EMIT_THREADS * d4gs_chunk_per_thread(dims);
-  if (e.nchunks && e.nchunks != (dims->N + per_block - 1) / per_block) {  // k_count_tiles' chunks must be this kernel's
-    d4gs_set_error("internal: fused scan chunking mismatch (%d vs %d)", e.nchunks, (dims->N + per_block - 1) / per_block);
-    return D4GS_EINVAL;
-  }
-  e.use_lds = sizeof(int) * (size_t)e.tw * e.th <= 64 * 1024;
+  e.use_lds = fp.hist_in_lds;
   e.lazy = LazyWs{};
-  return D4GS_OK;
+  return e;
 }
 
-template <int PT, int LZ>
-void emit_one(const EmitArgs &e, unsigned eblocks, size_t ebytes, hipStream_t stream) {
-  if (ebytes > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_emit<PT, LZ>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-  D4GS_LAUNCH("k_emit", (k_emit<PT, LZ>), dim3(eblocks), dim3(EMIT_THREADS), ebytes, stream, e);
-}
-template <int PT>
-void emit_pt(const EmitArgs &e, int lz, unsigned eblocks, size_t ebytes, hipStream_t stream) {
-  switch (lz) {
-    case 0: return emit_one<PT, 0>(e, eblocks, ebytes, stream);
-    case 1: return emit_one<PT, 1>(e, eblocks, ebytes, stream);
-    default: return emit_one<PT, 2>(e, eblocks, ebytes, stream);
-  }
-}
 // lz: 0 plain, 1 / 2 the near parts / the flagged tiles' far parts of a D4GS_LAZY_SORT frame (k_emit)
-int launch_emit(const EmitArgs &e, const D4gsDims *dims, int lz, hipStream_t stream) {
-  const int pt = d4gs_chunk_per_thread(dims), per_block = EMIT_THREADS * pt;
-  const unsigned eblocks = (unsigned)(((dims->N + per_block - 1) / per_block) * dims->S);
-  const size_t ebytes = e.use_lds ? sizeof(int) * (size_t)e.tw * e.th * (lz ? 2 : 1) : 0;
-  switch (pt) {
-    case 1: emit_pt<1>(e, lz, eblocks, ebytes, stream); break;
-    case 2: emit_pt<2>(e, lz, eblocks, ebytes, stream); break;
-    case 3: emit_pt<3>(e, lz, eblocks, ebytes, stream); break;
-    case 5: emit_pt<5>(e, lz, eblocks, ebytes, stream); break;
-    case 6: emit_pt<6>(e, lz, eblocks, ebytes, stream); break;
-    default: emit_pt<4>(e, lz, eblocks, ebytes, stream); break;
-  }
+int launch_emit(const EmitArgs &e, const FrontPlan &fp, int lz, hipStream_t stream) {
+  const size_t ebytes = fp.hist_in_lds ? sizeof(int) * (size_t)fp.tiles * (lz ? 2 : 1) : 0;
+  d4gs_with_pt(fp.pt, [&](auto pt) {
+    constexpr int PT = decltype(pt)::value;
+    d4gs_launch_chunks("k_emit", lz == 0 ? k_emit<PT, 0> : lz == 1 ? k_emit<PT, 1> : k_emit<PT, 2>, fp, ebytes, stream, e);
+  });
   return d4gs_check_launch("k_emit");
 }
 
@@ -609,16 +568,16 @@ int d4gs_bin_sort_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4gs
     d4gs_set_error("n_isect=%lld exceeds int32 indexing", (long long)isect->n_isect);
     return D4GS_ECAPACITY;
   }
-  EmitArgs e;
-  int rc = fill_emit_args(e, dims, proj, isect);
-  if (rc) return rc;
-  const bool lazy = d4gs_lazy_on(dims, proj);
+  const FrontPlan fp = d4gs_front_plan(dims);
+  EmitArgs e = emit_args(dims, fp, proj, isect);
+  int rc;
+  const bool lazy = d4gs_lazy_on(dims, proj, fp);
   if (lazy) {  // every tile's near / far pivot first (the caller's near_target is known here, not in d4gs_project_fwd)
-    e.lazy = d4gs_lazy_carve(proj->lazy_ws, dims->S, e.tw * e.th);
-    if ((rc = d4gs_lazy_pivot_launch(dims, proj, isect->near_target, stream))) return rc;
+    e.lazy = d4gs_lazy_carve(proj->lazy_ws, dims->S, fp.tiles);
+    if ((rc = d4gs_lazy_pivot_launch(dims, proj, fp, isect->near_target, stream))) return rc;
   }
-  if ((rc = launch_emit(e, dims, lazy ? 1 : 0, stream))) return rc;
-  return launch_sorts(dims, proj, isect, lazy ? 1 : 0, stream);
+  if ((rc = launch_emit(e, fp, lazy ? 1 : 0, stream))) return rc;
+  return launch_sorts(dims, fp, proj, isect, lazy ? 1 : 0, stream);
 }
 
 // D4GS_LAZY_SORT, second half (called by d4gs_raster_fwd between its two composite passes): the far parts of the lists whose tile
@@ -627,10 +586,9 @@ int d4gs_bin_sort_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4gs
 // (raster_bwd.hip), which never touches a dead row (copying their emission indices for the dense zero-fill cost 176 us on cfg2 with
 // 4x splats - more than the sort it saved).
 int d4gs_lazy_far_sort(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect *isect, hipStream_t stream) {
-  EmitArgs e;
-  int rc = fill_emit_args(e, dims, proj, isect);
-  if (rc) return rc;
-  e.lazy = d4gs_lazy_carve(proj->lazy_ws, dims->S, e.tw * e.th);
-  if ((rc = launch_emit(e, dims, 2, stream))) return rc;
-  return launch_sorts(dims, proj, isect, 2, stream);
+  const FrontPlan fp = d4gs_front_plan(dims);
+  EmitArgs e = emit_args(dims, fp, proj, isect);
+  e.lazy = d4gs_lazy_carve(proj->lazy_ws, dims->S, fp.tiles);
+  if (int rc = launch_emit(e, fp, 2, stream)) return rc;
+  return launch_sorts(dims, fp, proj, isect, 2, stream);
 }

@@ -156,18 +156,19 @@ int d4gs_query_sizes(const D4gsDims *d, D4gsSizes *z) {
     return D4GS_EINVAL;
   }
   const int64_t N = d->N, S = d->S, SN = S * N, W = d->width, H = d->height;
-  const int64_t tw = (W + D4GS_TILE - 1) / D4GS_TILE, th = (H + D4GS_TILE - 1) / D4GS_TILE;
-  const int64_t nch = d->D + (d->depth_mode != D4GS_DEPTH_NONE ? 1 : 0), DP = (d->D + 3) & ~3;
+  const FrontPlan fp = d4gs_front_plan(d);
+  const int64_t n_tiles = fp.n_tiles;
+  const int64_t nch = d4gs_nch(d), DP = (d->D + 3) & ~3;
   z->means2d = SN * 2, z->depths = SN, z->conics = SN * 3, z->radii = SN, z->opac_act = N, z->ctab = N * DP;
   z->geom = SN * D4GS_GEOM_STRIDE, z->tile_rects = SN * 2, z->tiles_touched = SN, z->isect_offsets = SN;
-  z->tile_counts = 2 * S * tw * th, z->tile_offsets = S * tw * th + 1, z->n_isect = 4;
+  z->tile_counts = 2 * n_tiles, z->tile_offsets = n_tiles + 1, z->n_isect = 4;
   z->scan_ws = (int64_t)d4gs_scan_ws_elems(SN);
   z->render_colors = S * H * W * nch, z->render_alphas = S * H * W, z->last_ids = S * H * W, z->final_T = S * H * W;
   z->isect_grad_row = 6 + nch + ((d->flags & D4GS_ABSGRAD) ? 2 : 0);  // absgrad: |dL/dx|, |dL/dy| behind the channels
   z->bwd_partials = (int64_t)d4gs_bwd_partials_elems(d);
   z->seg_state = d4gs_seg_state_elems(d);
-  z->lazy_ws = d4gs_lazy_ws_elems((int)S, (int)(tw * th));
-  z->tiles_x = (int32_t)tw, z->tiles_y = (int32_t)th, z->channels = (int32_t)nch;
+  z->lazy_ws = d4gs_lazy_ws_elems((int)S, fp.tiles);
+  z->tiles_x = fp.tw, z->tiles_y = fp.th, z->channels = (int32_t)nch;
   z->blend_bases = d->G > 0 ? S * (int64_t)d->K * 16 : 0;
   z->tile_masks = SN;
   z->compensations = (d->flags & D4GS_ANTIALIASED) ? SN : 0;

@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "host.h"  // include/d4gs.h + the host functions that cross translation units
+#include <type_traits>
+
+#include "host.h" // include/d4gs.h + the host functions that cross translation units
 
 #define D4GS_WAVE 64
 #define D4GS_MAX_K 32         // motion bases held in LDS per block
@@ -72,6 +74,24 @@ __device__ __forceinline__ void gram_schmidt(const float *r6, GS6 &o) {
   o.z[0] = o.x[1] * o.y[2] - o.x[2] * o.y[1];
   o.z[1] = o.x[2] * o.y[0] - o.x[0] * o.y[2];
   o.z[2] = o.x[0] * o.y[1] - o.x[1] * o.y[0];
+}
+
+// ---- the time slot of a sub-sample (params.py:152-177) ---------------------------------------------------------------
+// Clamped floor / ceil frames and the lerp weight w = t - (clamped floor): k_project_fwd's slab, k_poses_fwd's, k_bases_table and
+// k_finish's adjoint must work with the same numbers (the table a caller without `blend_bases` gets is the one the forward rendered
+// with: tests/test_gpu_exposure.py).  The blend itself, (1 - w) * vf + w * vc, stays written out in each kernel: preblend_bases and
+// k_bases_table round its two products and the sum separately (contract(off) - torch's lerp), k_poses_fwd has always fused them, and a
+// shared function changed k_bases_table's instruction order.  (cpu_twin.hip is host-only code without this header and keeps its own
+// three-line time_slot.)
+struct TimeSlot {
+  int f, c;  // floor and ceil frame
+  float w;
+};
+__host__ __device__ __forceinline__ TimeSlot d4gs_time_slot(float t, int T) {
+  const float ff = fminf(fmaxf(floorf(t), 0.f), (float)(T - 1));
+  const float cf = fminf(fmaxf(ceilf(t), 0.f), (float)(T - 1));
+  const float w = t - ff;
+  return TimeSlot{(int)ff, (int)cf, w};
 }
 
 // ---- pose compose on quaternions (flow3d/scene_model.py:94-102; roma 1.5.0 conventions, XYZW storage there) --------
@@ -633,3 +653,25 @@ __device__ __forceinline__ bool lists_overflowed(const int64_t *n_dev, int64_t c
     ProfScope _ps(name, stream);                                              \
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);        \
   } while (0)
+
+// FrontPlan.pt (1 ... 6; anything else means 4) as a compile-time constant: f(std::integral_constant<int, PT>) - the one dispatch of
+// k_count_tiles<PT, LAZY> and k_emit<PT, LZ>
+template <typename F>
+void d4gs_with_pt(int pt, F &&f) {
+  switch (pt) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+// One block of D4GS_CHUNK_THREADS lanes per chunk of the plan, `bytes` of dynamic LDS.  More than 64 KB has to be allowed per kernel
+// (152 KB + the kernels' static LDS <= 160 KB) - per call: the attribute belongs to the (function, device) pair and a process may
+// drive several GPUs.
+template <typename... P, typename... A>
+void d4gs_launch_chunks(const char *name, void (*kernel)(P...), const FrontPlan &fp, size_t bytes, hipStream_t stream, A... args) {
+  if (bytes > 64 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+  D4GS_LAUNCH(name, kernel, dim3(fp.blocks), dim3(D4GS_CHUNK_THREADS), bytes, stream, args...);
+}

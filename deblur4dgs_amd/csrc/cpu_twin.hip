@@ -266,8 +266,8 @@ int check_args(const D4gsDims *d, const D4gsProjIn *in, const D4gsFrameIO *io, c
 void forward_impl(const D4gsDims &d, const D4gsProjIn &in, const D4gsFrameIO &io, Frame &f) {
   const int N = d.N, S = d.S, W = d.width, H = d.height, D = d.D;
   f.d = d;
-  f.tw = (W + D4GS_TILE - 1) / D4GS_TILE, f.th = (H + D4GS_TILE - 1) / D4GS_TILE;
-  f.NCH = D + (d.depth_mode != D4GS_DEPTH_NONE ? 1 : 0);
+  f.tw = d4gs_tiles_across(W), f.th = d4gs_tiles_across(H);
+  f.NCH = d4gs_nch(&d);
   f.cam.fx = in.Kmat[0], f.cam.fy = in.Kmat[4], f.cam.cx = in.Kmat[2], f.cam.cy = in.Kmat[5];
   f.cam.limx = 1.3f * (0.5f * (float)W / f.cam.fx), f.cam.limy = 1.3f * (0.5f * (float)H / f.cam.fy);
   const bool raw = d.flags & D4GS_RAW_PARAMS;

@@ -148,8 +148,7 @@ int d4gs_forward(const D4gsDims *dims, const D4gsProjIn *in, const D4gsFrameIO *
   if ((rc = d4gs_bin_sort_impl(dims, &b.proj, &b.isect, stream))) return rc;
   if ((rc = d4gs_raster_fwd_impl(dims, &b.proj, &b.isect, &b.raster, stream))) return rc;
   if (io->blended) {
-    const int nch = dims->D + (dims->depth_mode != D4GS_DEPTH_NONE ? 1 : 0);
-    rc = d4gs_blend_fwd_impl(dims->S, (int64_t)dims->width * dims->height, nch, io->policy, io->renders, io->alphas, io->blended,
+    rc = d4gs_blend_fwd_impl(dims->S, (int64_t)dims->width * dims->height, d4gs_nch(dims), io->policy, io->renders, io->alphas, io->blended,
                              io->acc, b.blend_win, stream,  // (the winner map: read by the folded adjoint or by k_blend_bwd)
                              io->n_isect, io->counts_pinned);
   } else if (io->counts_pinned) {
@@ -177,20 +176,17 @@ int d4gs_backward(const D4gsDims *dims, const D4gsProjIn *in, const D4gsFrameIO 
   const float *v_renders = g->v_renders, *v_alphas = g->v_alphas;
   // The blend's adjoint rides in the composite backward's prologue (common.h BlendAdj) unless the caller also holds gradients on the
   // sub-sample images themselves: no k_blend_bwd launch, no [S,H,W,channels] gradient stack written and read back.
-  // D4GS_FUSE_BLEND_BWD=0: the separate kernel (A/B; same bits).
-  static const bool fuse_env = []() { const char *e = getenv("D4GS_FUSE_BLEND_BWD"); return !(e && e[0] == '0'); }();
-  const int nch_all = dims->D + (dims->depth_mode != D4GS_DEPTH_NONE ? 1 : 0);
+  const int nch = d4gs_nch(dims);
   // (narrow renders only: the 17-channel composite backward sits at its register budget - with the blend prologue it ran 1 018 -> 1 086 us
   // on the reference's training shape, more than the 42 us k_blend_bwd costs there; profiles/r04t_ab_blend_bwd.txt)
-  const bool fuse_blend = fuse_env && io->blended && !g->v_renders && !g->v_alphas && dims->D <= 5;
+  const bool fuse_blend = io->blended && !g->v_renders && !g->v_alphas && dims->D <= 5;
   BlendAdj ba{};
   if (fuse_blend) {
     ba.v_blended = g->v_blended, ba.v_acc = g->v_acc, ba.win = b.blend_win;
-    for (int c = 0; c < nch_all; c++)
+    for (int c = 0; c < nch; c++)
       if (io->policy && io->policy[c] != 0) ba.non_mean |= (uint64_t)1 << c;
     v_renders = nullptr, v_alphas = nullptr;
   } else if (io->blended) {
-    const int nch = dims->D + (dims->depth_mode != D4GS_DEPTH_NONE ? 1 : 0);
     // (gradients the caller holds on the sub-sample images themselves are summed in by the same kernel)
     if ((rc = d4gs_blend_bwd_add_impl(dims->S, (int64_t)dims->width * dims->height, nch, io->policy, io->renders, io->blended,
                                       g->v_blended, g->v_acc, b.v_renders, b.v_alphas, g->v_renders, g->v_alphas, stream,

@@ -33,16 +33,34 @@ int d4gs_poses_bwd_impl(const D4gsDims *dims, const D4gsProjIn *in, const D4gsPo
 size_t d4gs_poses_bwd_partials_bound(const D4gsDims *d);  // host arithmetic only: no device is asked
 // [S][K][16] time-blended bases (project_bwd.hip: k_bases_table), for callers of d4gs_project_bwd without D4gsProjOut.blend_bases
 int d4gs_bases_table_launch(const D4gsDims *dims, const D4gsProjIn *in, float *btab, hipStream_t stream);
-// Instances per lane of the 1024-lane blocks of k_count_tiles / k_emit (their chunks must agree): 4 - or 1 when 4 would leave
-// fewer blocks than CUs (one or two sub-samples of a few 100 k Gaussians: S = 1, N = 300 k gave 74 blocks for 256 CUs).
-int d4gs_chunk_per_thread(const D4gsDims *d);
-// > 0: the fused scan is in effect for this configuration and this is its chunk count per sub-sample (project_fwd.hip)
-int d4gs_fused_scan_chunks(const D4gsDims *d);
+// tiles across `pixels` of width or height; colour channels + the depth channel of a render
+inline int d4gs_tiles_across(int pixels) { return (pixels + D4GS_TILE - 1) / D4GS_TILE; }
+inline int d4gs_nch(const D4gsDims *d) { return d->D + (d->depth_mode != D4GS_DEPTH_NONE ? 1 : 0); }
+
+// ---- the list front end's launch rules, stated once (project_fwd.hip) -----------------------------------------------------
+// Projection, tile counting, the scans, k_emit, the tile sorts and the composites all launch over the same tile grid, and
+// k_count_tiles / k_emit over the same chunks of instances: every entry point computes this plan once and reads it.
+constexpr int D4GS_CHUNK_THREADS = 1024;  // lanes of a k_count_tiles / k_emit block: one constant, so their chunks cannot drift apart
+static_assert(D4GS_CHUNK_THREADS % 64 == 0 && D4GS_CHUNK_THREADS <= 1024, "whole waves, one workgroup");
+struct FrontPlan {
+  int tw, th, tiles;  // the tile grid of one sub-sample
+  int n_tiles;        // x S
+  bool hist_in_lds;   // one sub-sample's tile histogram (an int per tile) fits in 64 KB of LDS: k_emit bins there, and ...
+  bool count_apart;   // ... k_count_tiles counts there (unless N = 0 or D4GS_COUNT_IN_PROJECT, the tests' hook for the fallback,
+                      // k_project_fwd's global atomics, that bigger grids take)
+  // Chunks: a block takes per_block = D4GS_CHUNK_THREADS * pt consecutive instances of one sub-sample.  pt, the instances per lane,
+  // is 1 when 4 would leave fewer blocks than CUs (S = 1, N = 300 k gave 74 blocks for 256 CUs), else the fewest of 2 ... 6 that
+  // makes the launch one round of the chip's 512 block slots, else 4 (always 4 for D4GS_LAZY_SORT): d4gs_front_plan.
+  int pt, per_block, nchunks /* per sub-sample */, blocks /* nchunks * S */;
+  int fused_chunks;  // nchunks: the fused scan is in effect (k_count_tiles leaves chunk sums, k_emit writes isect_offsets); 0: the
+                     // two-pass scan (D4GS_NO_FUSED_SCAN, the tests' hook; !count_apart; a scan_ws too small for the chunk sums)
+};
+FrontPlan d4gs_front_plan(const D4gsDims *d);
 
 // ---- binning, D4GS_LAZY_SORT (binning.hip, project_fwd.hip) ---------------------------------------------------------------
 int d4gs_bin_sort_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect *isect, hipStream_t stream);
-bool d4gs_lazy_on(const D4gsDims *d, const D4gsProjOut *out);
-int d4gs_lazy_pivot_launch(const D4gsDims *d, const D4gsProjOut *out, int64_t near_target, hipStream_t stream);
+bool d4gs_lazy_on(const D4gsDims *d, const D4gsProjOut *out, const FrontPlan &fp);
+int d4gs_lazy_pivot_launch(const D4gsDims *d, const D4gsProjOut *out, const FrontPlan &fp, int64_t near_target, hipStream_t stream);
 int d4gs_lazy_far_sort(const D4gsDims *dims, const D4gsProjOut *proj, const D4gsIsect *isect, hipStream_t stream);
 
 // ---- composites (raster_fwd.hip, raster_bwd.hip) --------------------------------------------------------------------------

@@ -60,14 +60,7 @@ struct BwdArgs {
 template <int MODE>
 int slots_of(int S) { return (MODE != MODE_RENDER || S >= 3) ? 4 : S == 2 ? 2 : 1; }
 
-#ifndef PB_MFMA_WAVES
-#define PB_MFMA_WAVES 3
-#endif
-#ifndef PB_NO_SB
 #define SB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define SB()
-#endif
 // accumulate into the lane's private LDS row: plain read-modify-write (ds_add_f32, 22 per pass, measured 2.6x slower for the
 // whole kernel: 306 vs 117 us on cfg2 - LDS float atomics run at a fraction of the plain DS rate on gfx950)
 #define ACC(slot_, val_) ac[slot_] += (val_)
@@ -92,16 +85,14 @@ __device__ __forceinline__ void rotmat_adj_to_quat(const float *q, const float *
 // address, constant address space: s_load_dwordx8 + dword per basis) and the values are SGPR operands of the multiply-adds: no LDS
 // traffic, no transient VGPRs (128 VGPRs + a 24-byte scratch frame -> 122, none).  Row stride 16 floats.  Measured (A/B build, same
 // run): cfg2 119.5 -> 112.5 us, cfg3 118.5 -> 112.6, refdefault (K = 20) 128 -> 118, cfg5 (K = 12) 967 -> 736 (profiles/r05_ab_bases_table.txt).
-// contract(off): the same two products and one sum as k_project_fwd's preblend_bases (and the reference's lerp), bit for bit - the table a
-// caller without `blend_bases` gets here must be the one the forward rendered with (tests/test_gpu_exposure.py).
+// d4gs_blend_basis (common.h): the same two products and one sum as k_project_fwd's preblend_bases (and the reference's lerp), bit for bit -
+// the table a caller without `blend_bases` gets here must be the one the forward rendered with (tests/test_gpu_exposure.py).
 __global__ void __launch_bounds__(256) k_bases_table(const D4gsDims d, const float *times, const float *rots, const float *transls, float *btab) {
 #pragma clang fp contract(off)
   const int s = blockIdx.x, K = d.K, T = d.T;
-  const float t = times[s];
-  const float ff = fminf(fmaxf(floorf(t), 0.f), (float)(T - 1));
-  const float cf_ = fminf(fmaxf(ceilf(t), 0.f), (float)(T - 1));
-  const float w = t - ff;
-  const int f = (int)ff, c = (int)cf_;
+  const TimeSlot ts = d4gs_time_slot(times[s], T);
+  const float w = ts.w;
+  const int f = ts.f, c = ts.c;
   for (int idx = threadIdx.x; idx < K * 16; idx += 256) {
     const int k = idx >> 4, j = idx & 15;
     float v = 0.f;
@@ -113,20 +104,17 @@ __global__ void __launch_bounds__(256) k_bases_table(const D4gsDims d, const flo
 // A kernel argument read afresh from the kernarg segment where it is used (s_load at the use site).  k_project_bwd sits at the SGPR limit:
 // its ~370-byte argument block was loaded at entry and ~130 of those values were parked in VGPR lanes (v_writelane) and restored with
 // v_readlane, 16-register tuples at a time - ~170 restores in the per-group epilogue alone.  The epilogue's pointers are read with this.
-#ifndef PB_KARG_RELOAD
-#define PB_KARG_RELOAD 1
-#endif
 template <typename T>
 __device__ __forceinline__ T pb_karg_at(size_t off) {
   typedef const volatile __attribute__((address_space(4))) T *kp;
   const __attribute__((address_space(4))) char *base = (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
   return *(kp)(base + off);
 }
-#define PB_KARG(f_) (PB_KARG_RELOAD ? pb_karg_at<std::remove_cv_t<std::remove_reference_t<decltype(a.f_)>>>((size_t)((const char *)&(a.f_) - (const char *)&a)) : a.f_)
+#define PB_KARG(f_) pb_karg_at<std::remove_cv_t<std::remove_reference_t<decltype(a.f_)>>>((size_t)((const char *)&(a.f_) - (const char *)&a))
 typedef const __attribute__((address_space(4))) float *cfloat_p;
 #define PB_BROW(k_) ((cfloat_p)(uintptr_t)a.btab + ((size_t)s * K + (k_)) * 16)
 template <int MODE, bool MFMA /* K > 8: basis-gradient column sums on the matrix pipe */, int SL /* slots per sub-group */>
-__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(MFMA ? PB_MFMA_WAVES : 4))) k_project_bwd(const BwdArgs a) {
+__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(MFMA ? 3 : 4))) k_project_bwd(const BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const D4gsDims &d = a.d;
   const int N = d.N, G = d.G, S = d.S;
@@ -755,13 +743,10 @@ __global__ void __launch_bounds__(1024) k_finish(const BwdArgs a, const float *r
       const int k = gtid / (T * 9), r = gtid - k * T * 9, fr = r / 9, j = r - fr * 9;
       float acc = 0.f;
       for (int s = 0; s < S; s++) {
-        const float t = a.in.times[s];
-        const float ff = fminf(fmaxf(floorf(t), 0.f), (float)(T - 1));
-        const float cfl = fminf(fmaxf(ceilf(t), 0.f), (float)(T - 1));
-        const float w = t - ff;
+        const TimeSlot ts = d4gs_time_slot(a.in.times[s], T);
         const float v = red[s * stride + k * 9 + j];
-        if ((int)ff == fr) acc += (1.f - w) * v;
-        if ((int)cfl == fr) acc += w * v;
+        if (ts.f == fr) acc += (1.f - ts.w) * v;
+        if (ts.c == fr) acc += ts.w * v;
       }
       if (j < 3) a.g.v_transls[(k * T + fr) * 3 + j] = acc;
       else a.g.v_rots[(k * T + fr) * 6 + j - 3] = acc;
@@ -769,10 +754,8 @@ __global__ void __launch_bounds__(1024) k_finish(const BwdArgs a, const float *r
     // v_times[s] = dL/dw = sum_kj (base_c - base_f) * v_Bs
     if (gtid < S) {
       const int s = gtid;
-      const float t = a.in.times[s];
-      const float ff = fminf(fmaxf(floorf(t), 0.f), (float)(T - 1));
-      const float cfl = fminf(fmaxf(ceilf(t), 0.f), (float)(T - 1));
-      const int f = (int)ff, c = (int)cfl;
+      const TimeSlot ts = d4gs_time_slot(a.in.times[s], T);
+      const int f = ts.f, c = ts.c;
       float acc = 0.f;
       for (int k = 0; k < K; k++)
         for (int j = 0; j < 9; j++) {
@@ -946,9 +929,8 @@ static int launch_project_bwd(BwdArgs &a, const D4gsDims *dims, const D4gsLeafGr
   }
   // Mid-size shared vectors (round 5; cfg2: 540 floats, 1 296 leaf elements): ONE block of 1 024 lanes does the second pass once - RCH x
   // n_shared coalesced loads, the same additions in the same order, so the totals are the same bits - and then walks the leaf elements
-  // itself: one launch instead of two (k_reduce_partials' second pass + a six-block k_finish).  D4GS_FINISH_ONE=0: the two launches (A/B).
-  static const bool one_env = []() { const char *e = getenv("D4GS_FINISH_ONE"); return !(e && e[0] == '0'); }();
-  if (one_env && a.n_shared <= 1024 && fin <= 8192) {
+  // itself: one launch instead of two (k_reduce_partials' second pass + a six-block k_finish).
+  if (a.n_shared <= 1024 && fin <= 8192) {
     D4GS_LAUNCH("k_finish", k_finish, dim3(1), dim3(1024), fin_lds, stream, a, (const float *)red2, RCH);
     return d4gs_check_launch("k_finish");
   }

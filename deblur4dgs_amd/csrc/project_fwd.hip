@@ -32,11 +32,9 @@ __device__ __forceinline__ void preblend_bases(const FwdArgs &a, float *Bs) {
   const int K = a.d.K, T = a.d.T;
   for (int idx = threadIdx.x; idx < a.d.S * K * 9; idx += blockDim.x) {
     int s = idx / (K * 9), r = idx - s * K * 9, k = r / 9, j = r - k * 9;
-    float t = a.in.times[s];
-    float ff = fminf(fmaxf(floorf(t), 0.f), (float)(T - 1));
-    float cf = fminf(fmaxf(ceilf(t), 0.f), (float)(T - 1));
-    float w = t - ff;
-    int f = (int)ff, c = (int)cf;
+    const TimeSlot ts = d4gs_time_slot(a.in.times[s], T);
+    const float w = ts.w;
+    const int f = ts.f, c = ts.c;
     float vf, vc;
     if (j < 3) {
       vf = a.in.transls[(k * T + f) * 3 + j];
@@ -52,10 +50,7 @@ __device__ __forceinline__ void preblend_bases(const FwdArgs &a, float *Bs) {
 template <bool XT /* D4GS_EXACT_TILES: the wave-cooperative per-tile ellipse test (its own instantiation: 88 instead of 64 VGPRs) */,
           bool TAB /* FwdArgs.use_table: blended bases from the global table (scalar loads) instead of the block's LDS slab */,
           bool AA = false /* D4GS_ANTIALIASED: opacity * compensation in the geom record and the culls, compensation -> out.compensations */>
-__global__ void __launch_bounds__(D4GS_PROJ_BLOCK)
-#ifdef XT_WAVES  // (A/B) the exact-tiles instantiations at XT_WAVES waves per SIMD (6: 80 VGPRs + a 16-byte scratch frame; default: 83-85, 5 waves)
-__attribute__((amdgpu_waves_per_eu(XT ? XT_WAVES : 1, XT ? XT_WAVES : 10)))
-#endif
+__global__ void __launch_bounds__(D4GS_PROJ_BLOCK)  // (XT: 83-85 VGPRs, 5 waves per SIMD; forced to 6 waves: 80 + a 16-byte scratch frame, not kept)
 k_project_fwd(const FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const D4gsDims &d = a.d;
@@ -391,11 +386,9 @@ __global__ void __launch_bounds__(POSE_GPB * POSE_SLOTS) k_poses_fwd(const Poses
   for (int s = slot; s < S; s += POSE_SLOTS) {
     if (dyn_block) {
       const int T = d.T;
-      const float t = a.in.times[s];
-      const float ff = fminf(fmaxf(floorf(t), 0.f), (float)(T - 1));
-      const float cfl = fminf(fmaxf(ceilf(t), 0.f), (float)(T - 1));
-      const float w = t - ff;
-      const int f = (int)ff, c = (int)cfl;
+      const TimeSlot ts = d4gs_time_slot(a.in.times[s], T);
+      const float w = ts.w;
+      const int f = ts.f, c = ts.c;
       for (int idx = lane; idx < nk; idx += 64) {
         const int k = idx / 9, j = idx - k * 9;
         float vf, vc;
@@ -467,7 +460,6 @@ __global__ void __launch_bounds__(POSE_GPB * POSE_SLOTS) k_poses_fwd(const Poses
 // every non-empty bin to the global counter with one atomic: ~13x fewer global atomics.  (k_emit later repeats the
 // same histogram to hand out the slots, see binning.hip.)
 // ---------------------------------------------------------------------------------------------------
-constexpr int COUNT_THREADS = 1024;
 
 // D4GS_LAZY_SORT: the depth range of every sub-sample's binned instances, the scale of d4gs_depth_bucket - from a SAMPLE (every
 // 16th instance): the bucket map clamps outside the range, so any range gives a monotone, consistent partition; an exact one
@@ -508,26 +500,26 @@ __global__ void __launch_bounds__(256) k_lazy_pivot(LazyWs w, int n_tiles, int t
 }
 
 template <int COUNT_PER_THREAD, bool LAZY>
-__global__ void __launch_bounds__(COUNT_THREADS) k_count_tiles(const int *__restrict__ tile_rects,
+__global__ void __launch_bounds__(D4GS_CHUNK_THREADS) k_count_tiles(const int *__restrict__ tile_rects,
                                                               const int *__restrict__ tiles_touched, int N, int S, int tw,
                                                               int th, int *__restrict__ tile_counts, int *__restrict__ chunk_sums,
                                                               const float *__restrict__ depths, LazyWs lazy,
                                                               const uint64_t *__restrict__ tile_masks /* D4GS_EXACT_TILES or NULL */) {
   extern __shared__ int hist[];  // [tiles] (+ LAZY: [tiles][nb] per depth bucket)
-  __shared__ int wsum[COUNT_THREADS / 64];
+  __shared__ int wsum[D4GS_CHUNK_THREADS / 64];
   const int tiles = tw * th, tid = threadIdx.x;
   const int s = blockIdx.x % S, chunk = blockIdx.x / S;  // neighbouring blocks work on different sub-samples' counters
-  for (int z = tid; z < (LAZY ? tiles * (1 + lazy.nb) : tiles); z += COUNT_THREADS) hist[z] = 0;
+  for (int z = tid; z < (LAZY ? tiles * (1 + lazy.nb) : tiles); z += D4GS_CHUNK_THREADS) hist[z] = 0;
   __syncthreads();
   int *hist2 = hist + tiles;
   const uint32_t zlo = LAZY ? ~lazy.zr[2 * s] : 0u, zhi = LAZY ? lazy.zr[2 * s + 1] : 0u;
-  int touched = 0;  // this lane's share of the chunk's intersection count (fused scan: see d4gs_fused_scan)
+  int touched = 0;  // this lane's share of the chunk's intersection count (fused scan: FrontPlan.fused_chunks)
   if constexpr (LAZY) {
     // (the lazy instantiation - cfg5: a 150 KB histogram, ONE resident workgroup per CU - keeps the instance-by-instance walk: with all
     // loads up front its sixteen waves load together and then hammer the LDS together, 199 -> 226 us)
   #pragma unroll
     for (int q = 0; q < COUNT_PER_THREAD; q++) {
-      const int g = (chunk * COUNT_PER_THREAD + q) * COUNT_THREADS + tid;
+      const int g = (chunk * COUNT_PER_THREAD + q) * D4GS_CHUNK_THREADS + tid;
       if (g >= N) continue;
       const size_t i = (size_t)s * N + g;
       const int tt = tiles_touched[i];
@@ -559,7 +551,7 @@ __global__ void __launch_bounds__(COUNT_THREADS) k_count_tiles(const int *__rest
     uint64_t msks[COUNT_PER_THREAD];
   #pragma unroll
     for (int q = 0; q < COUNT_PER_THREAD; q++) {
-      const int g = (chunk * COUNT_PER_THREAD + q) * COUNT_THREADS + tid;
+      const int g = (chunk * COUNT_PER_THREAD + q) * D4GS_CHUNK_THREADS + tid;
       tts[q] = 0, rxs[q] = 0, rys[q] = 0, deps[q] = 0.f, msks[q] = 0;
       if (g < N) {
         const size_t i = (size_t)s * N + g;
@@ -605,19 +597,19 @@ __global__ void __launch_bounds__(COUNT_THREADS) k_count_tiles(const int *__rest
     if ((tid & 63) == 0) wsum[tid >> 6] = touched;
   }
   __syncthreads();
-  for (int z = tid; z < tiles; z += COUNT_THREADS) {
+  for (int z = tid; z < tiles; z += D4GS_CHUNK_THREADS) {
     const int c = hist[z];
     if (c > 0) atomicAdd(tile_counts + (size_t)s * tiles + z, c);
   }
   if (LAZY)
-    for (int z = tid; z < tiles * lazy.nb; z += COUNT_THREADS) {
+    for (int z = tid; z < tiles * lazy.nb; z += D4GS_CHUNK_THREADS) {
       const int c = hist2[z];
       if (c > 0) atomicAdd(lazy.hist + (size_t)s * tiles * lazy.nb + z, c);
     }
   if (chunk_sums && tid == 0) {
     int t = 0;
 #pragma unroll
-    for (int w = 0; w < COUNT_THREADS / 64; w++) t += wsum[w];
+    for (int w = 0; w < D4GS_CHUNK_THREADS / 64; w++) t += wsum[w];
     chunk_sums[(size_t)s * gridDim.x / S + chunk] = t;  // (sub-sample, chunk) order = the flat instance order
   }
 }
@@ -740,60 +732,59 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_apply(const int *in, cons
 }  // namespace
 
 extern "C" size_t d4gs_scan_ws_elems(int64_t n_instances) {  // (block sums of the two-pass scan / chunk sums of the fused one)
-  return (size_t)((n_instances + COUNT_THREADS - 1) / COUNT_THREADS) + 64;
+  return (size_t)((n_instances + D4GS_CHUNK_THREADS - 1) / D4GS_CHUNK_THREADS) + 64;
 }
 
-// D4GS_LAZY_SORT in effect?  (needs the LDS-aggregated counting pass and the scratch buffer; D4GS_LAZY=0 forces it off)
-bool d4gs_lazy_on(const D4gsDims *d, const D4gsProjOut *out) {
-  if (!(d->flags & D4GS_LAZY_SORT) || !out->lazy_ws || d->N <= 0) return false;
-  const char *env = getenv("D4GS_LAZY");
-  if (env && env[0] == '0') return false;
-  const size_t tiles = (size_t)((d->width + D4GS_TILE - 1) / D4GS_TILE) * ((d->height + D4GS_TILE - 1) / D4GS_TILE);
-  return sizeof(int) * tiles * (1 + d4gs_lazy_buckets((int)tiles)) <= 150 * 1024 && sizeof(int) * tiles <= 64 * 1024 &&
-         getenv("D4GS_COUNT_IN_PROJECT") == nullptr;
-}
-int d4gs_lazy_pivot_launch(const D4gsDims *d, const D4gsProjOut *out, int64_t near_target, hipStream_t stream) {
-  const int tiles = ((d->width + D4GS_TILE - 1) / D4GS_TILE) * ((d->height + D4GS_TILE - 1) / D4GS_TILE), nt = d->S * tiles;
-  const int target = near_target > 0 ? (int)(near_target > (1 << 20) ? (1 << 20) : near_target) : 1024;
-  D4GS_LAUNCH("k_lazy_pivot", k_lazy_pivot, dim3((nt + 255) / 256), dim3(256), 0, stream, d4gs_lazy_carve(out->lazy_ws, d->S, tiles), nt, target);
-  return d4gs_check_launch("k_lazy_pivot");
-}
-
-// (256 = the CU count of the one device this library is built for - gfx950 / MI355X; the choice must not depend on a device query:
-// d4gs_query_sizes answers on GPU-less hosts too, and k_count_tiles / k_emit only need to agree with each other)
-int d4gs_chunk_per_thread(const D4gsDims *d) {
-  const int64_t blocks4 = (((int64_t)d->N + 4 * COUNT_THREADS - 1) / (4 * COUNT_THREADS)) * d->S;
+// The launch plan of the list front end (host.h).  Pure host arithmetic - d4gs_query_sizes answers on GPU-less hosts too, and
+// k_count_tiles / k_emit only need to agree with each other: 256 = the CU count of the one device this library is built for
+// (gfx950 / MI355X), and its 1024-lane blocks fit two per CU = 512 at a time.
+FrontPlan d4gs_front_plan(const D4gsDims *d) {
+  static const bool force_in_kernel = getenv("D4GS_COUNT_IN_PROJECT") != nullptr;  // the tests' hooks for the fallback paths
+  static const bool no_fused_scan = getenv("D4GS_NO_FUSED_SCAN") != nullptr;
+  FrontPlan p;
+  p.tw = d4gs_tiles_across(d->width), p.th = d4gs_tiles_across(d->height);
+  p.tiles = p.tw * p.th, p.n_tiles = d->S * p.tiles;
+  p.hist_in_lds = sizeof(int) * (size_t)p.tiles <= 64 * 1024;
+  p.count_apart = p.hist_in_lds && d->N > 0 && !force_in_kernel;
+  auto blocks_at = [&](int pt) { return (((int64_t)d->N + (int64_t)pt * D4GS_CHUNK_THREADS - 1) / ((int64_t)pt * D4GS_CHUNK_THREADS)) * d->S; };
   // (round 5, measured and dropped: 8 / 16 instances per lane on 720p grids - 4x fewer per-bin device-scope atomics - made k_emit
   // SLOWER, cfg5 720 -> 1 139 us, cfg3 193 -> 245: its time is not those atomics; profiles/r05_ab_chunk16.txt)
-  if (blocks4 < 256) return 1;
-  // Round 6: the 1024-lane blocks of k_count_tiles / k_emit fit two per CU = 512 at a time.  cfg2's 592 blocks (74 chunks x 8 sub-samples)
-  // are one full round and one of 80 blocks that costs as much again; five or six instances per lane make the same launch ONE round
-  // (472 blocks).  Only when it saves a round - beyond two rounds the longer dependent chain per lane costs more than the tail.
-  static const int pt_env = getenv("D4GS_CHUNK_PT") ? atoi(getenv("D4GS_CHUNK_PT")) : 0;  // A/B hook: 2 ... 6
-  if (pt_env >= 2 && pt_env <= 6) return pt_env;
-  const int64_t slots = 512;
-  auto blocks_at = [&](int pt) { return (((int64_t)d->N + (int64_t)pt * COUNT_THREADS - 1) / ((int64_t)pt * COUNT_THREADS)) * d->S; };
-  if (d->flags & D4GS_LAZY_SORT) return 4;  // (the lazy instantiations walk more per pair: 5 measured slower)
-  // the FEWEST instances per lane that still make the launch one round: shorter dependent chains per lane, more blocks in flight
-  // (the reference's training shape: 4 -> 3 per lane, 385 -> 506 blocks)
-  for (int pt = 2; pt <= 6; pt++)
-    if (blocks_at(pt) <= slots) return pt;
-  return 4;
+  p.pt = 4;
+  if (blocks_at(4) < 256) {
+    p.pt = 1;
+  } else if (!(d->flags & D4GS_LAZY_SORT)) {  // (the lazy instantiations walk more per pair: 5 measured slower)
+    // Round 6: cfg2's 592 blocks (74 chunks x 8 sub-samples) are one full round of the 512 slots and one of 80 blocks that costs as much
+    // again; five or six instances per lane make the same launch ONE round (472 blocks).  Only when it saves a round - beyond two rounds
+    // the longer dependent chain per lane costs more than the tail - and the FEWEST per lane that do: shorter chains, more blocks in
+    // flight (the reference's training shape: 4 -> 3 per lane, 385 -> 506 blocks).
+    for (int pt = 2; pt <= 6; pt++)
+      if (blocks_at(pt) <= 512) {
+        p.pt = pt;
+        break;
+      }
+  }
+  p.per_block = D4GS_CHUNK_THREADS * p.pt;
+  p.nchunks = (d->N + p.per_block - 1) / p.per_block;
+  p.blocks = p.nchunks * d->S;
+  // Fused scan of the per-instance intersection counts (small tile grids, i.e. every BASELINE config): k_count_tiles also leaves
+  // the sum of each (sub-sample, chunk), one single-block scan turns the sums into chunk bases, and k_emit - whose blocks are the
+  // same chunks - scans inside its chunk and writes isect_offsets itself: no k_scan_sums / k_scan_apply launches.  Same flat
+  // order, same offsets.  (Not with tiny N and many sub-samples: the chunk sums must fit in scan_ws.)
+  const bool fits = (size_t)p.blocks + 1 <= d4gs_scan_ws_elems((int64_t)d->S * d->N);
+  p.fused_chunks = p.count_apart && !no_fused_scan && fits ? p.nchunks : 0;
+  return p;
 }
 
-// Fused scan of the per-instance intersection counts (small tile grids, i.e. every BASELINE config): k_count_tiles also
-// leaves the sum of each (sub-sample, 4096-instance chunk), one single-block scan turns the sums into chunk bases, and
-// k_emit - whose blocks are the same chunks - scans inside its chunk and writes isect_offsets itself: no k_scan_sums /
-// k_scan_apply launches.  Same flat order, same offsets.  Both d4gs_project_fwd and d4gs_bin_sort ask this predicate.
-int d4gs_fused_scan_chunks(const D4gsDims *d) {
-  static const bool force_in_kernel = getenv("D4GS_COUNT_IN_PROJECT") != nullptr;
-  static const bool off = getenv("D4GS_NO_FUSED_SCAN") != nullptr;  // A/B hook
-  const int tw = (d->width + D4GS_TILE - 1) / D4GS_TILE, th = (d->height + D4GS_TILE - 1) / D4GS_TILE;
-  if (off || force_in_kernel || d->N <= 0 || sizeof(int) * (size_t)tw * th > 64 * 1024) return 0;
-  const int per_block = COUNT_THREADS * d4gs_chunk_per_thread(d);
-  const int64_t nchunks = (d->N + per_block - 1) / per_block;
-  if ((size_t)(nchunks * d->S) + 1 > d4gs_scan_ws_elems((int64_t)d->S * d->N)) return 0;  // tiny N, many sub-samples
-  return (int)nchunks;
+// D4GS_LAZY_SORT in effect?  (needs the LDS-aggregated counting pass and the scratch buffer)
+bool d4gs_lazy_on(const D4gsDims *d, const D4gsProjOut *out, const FrontPlan &fp) {
+  if (!(d->flags & D4GS_LAZY_SORT) || !out->lazy_ws) return false;
+  return fp.count_apart && sizeof(int) * (size_t)fp.tiles * (1 + d4gs_lazy_buckets(fp.tiles)) <= 150 * 1024;
+}
+int d4gs_lazy_pivot_launch(const D4gsDims *d, const D4gsProjOut *out, const FrontPlan &fp, int64_t near_target, hipStream_t stream) {
+  const int target = near_target > 0 ? (int)(near_target > (1 << 20) ? (1 << 20) : near_target) : 1024;
+  D4GS_LAUNCH("k_lazy_pivot", k_lazy_pivot, dim3((fp.n_tiles + 255) / 256), dim3(256), 0, stream, d4gs_lazy_carve(out->lazy_ws, d->S, fp.tiles),
+              fp.n_tiles, target);
+  return d4gs_check_launch("k_lazy_pivot");
 }
 
 static size_t fwd_lds_bytes(const D4gsDims *dims) {
@@ -814,14 +805,14 @@ int d4gs_poses_fwd_impl(const D4gsDims *dims, const D4gsProjIn *in, const D4gsPo
 }
 
 int d4gs_project_fwd_impl(const D4gsDims *dims, const D4gsProjIn *in, const D4gsProjOut *out, hipStream_t stream) {
+  const FrontPlan fp = d4gs_front_plan(dims);
   FwdArgs a;
   a.d = *dims;
   a.in = *in;
   a.out = *out;
-  a.tw = (dims->width + D4GS_TILE - 1) / D4GS_TILE;
-  a.th = (dims->height + D4GS_TILE - 1) / D4GS_TILE;
+  a.tw = fp.tw, a.th = fp.th;
+  a.count_apart = fp.count_apart;
   const int64_t n_inst = (int64_t)dims->S * dims->N;
-  const int64_t n_tiles = (int64_t)dims->S * a.tw * a.th;
   const size_t lds = fwd_lds_bytes(dims);
   if (lds > 64 * 1024) {
     d4gs_set_error("S*K too large for the LDS-resident bases (S=%d K=%d)", dims->S, dims->K);
@@ -831,13 +822,8 @@ int d4gs_project_fwd_impl(const D4gsDims *dims, const D4gsProjIn *in, const D4gs
     d4gs_set_error("D4GS_EXACT_TILES needs D4gsProjOut.tile_masks and D4GS_EXACT_CULL (the masks refine the tight rectangle)");
     return D4GS_EINVAL;
   }
-  const int blocks = (dims->N + D4GS_PROJ_BLOCK - 1) / D4GS_PROJ_BLOCK;
-  const size_t hist_bytes = sizeof(int) * (size_t)a.tw * a.th;
-  static const bool force_in_kernel = getenv("D4GS_COUNT_IN_PROJECT") != nullptr;  // test hook for the fallback
-  a.count_apart = hist_bytes <= 64 * 1024 && dims->N > 0 && !force_in_kernel;  // bigger tile grids: in-kernel atomics
-  const int fused_chunks = a.count_apart ? d4gs_fused_scan_chunks(dims) : 0;
-  if (!a.count_apart) {  // (count_apart: k_project_fwd zeroes the histogram itself, k_count_tiles fills it afterwards)
-    hipError_t e = hipMemsetAsync(out->tile_counts, 0, sizeof(int32_t) * 2 * n_tiles, stream);
+  if (!fp.count_apart) {  // (count_apart: k_project_fwd zeroes the histogram itself, k_count_tiles fills it afterwards)
+    hipError_t e = hipMemsetAsync(out->tile_counts, 0, sizeof(int32_t) * 2 * fp.n_tiles, stream);
     if (e != hipSuccess) {
       d4gs_set_error("hipMemsetAsync(tile_counts): %s", hipGetErrorString(e));
       return D4GS_ELAUNCH;
@@ -846,26 +832,24 @@ int d4gs_project_fwd_impl(const D4gsDims *dims, const D4gsProjIn *in, const D4gs
   // Many motion bases (K >= 10: cfg5's 12, the reference's 20): the S x K x 9 blended values are built ONCE by a small launch in front
   // and every lane's 9 K multiply-adds per sub-sample take them as scalar operands instead of LDS broadcast reads - refdefault 73.4 ->
   // 61.2 us, cfg5 382 -> 357; at K = 6 the saving (1.5 us) is less than the launch (profiles/r05_ab_bases_table.txt).
-  // D4GS_FWD_TABLE=0 / 1 forces it off / on (A/B).
-  static const int tab_env = []() { const char *e = getenv("D4GS_FWD_TABLE"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-  a.use_table = dims->G > 0 && out->blend_bases && (tab_env < 0 ? dims->K >= 10 : tab_env == 1);
+  a.use_table = dims->G > 0 && out->blend_bases && dims->K >= 10;
   if (a.use_table) {
     int rc0 = d4gs_bases_table_launch(dims, in, out->blend_bases, stream);
     if (rc0) return rc0;
   }
   {
-    const bool xt = dims->flags & D4GS_EXACT_TILES;
-    const void *fn = xt ? (a.use_table ? (const void *)k_project_fwd<true, true> : (const void *)k_project_fwd<true, false>)
-                        : (a.use_table ? (const void *)k_project_fwd<false, true> : (const void *)k_project_fwd<false, false>);
-    if (dims->flags & D4GS_ANTIALIASED)
-      fn = xt ? (a.use_table ? (const void *)k_project_fwd<true, true, true> : (const void *)k_project_fwd<true, false, true>)
-              : (a.use_table ? (const void *)k_project_fwd<false, true, true> : (const void *)k_project_fwd<false, false, true>);
+    static const void *const kernels[2][2][2] = {  // [XT][TAB][AA]
+        {{(const void *)k_project_fwd<false, false, false>, (const void *)k_project_fwd<false, false, true>},
+         {(const void *)k_project_fwd<false, true, false>, (const void *)k_project_fwd<false, true, true>}},
+        {{(const void *)k_project_fwd<true, false, false>, (const void *)k_project_fwd<true, false, true>},
+         {(const void *)k_project_fwd<true, true, false>, (const void *)k_project_fwd<true, true, true>}}};
+    const void *fn = kernels[(dims->flags & D4GS_EXACT_TILES) != 0][a.use_table][(dims->flags & D4GS_ANTIALIASED) != 0];
     // sub-sample groups (the kernel's header comment): as many as keep the launch within ONE round of the chip's 2 048 four-wave slots
-    static const int sg_env = getenv("D4GS_PROJ_SG") ? atoi(getenv("D4GS_PROJ_SG")) : 0;  // A/B hook
     // (measured, profiles/r06_ab_proj_groups.txt: the training shape - 547 blocks - 57.7 -> 44.1 us with 3 groups; cfg2 - 1 172 blocks - 65.3 -> 62.3
     // with 2, 71 with 4; cfg5 - 3 907 blocks, two rounds already - slower with 2)
-    int sg = sg_env > 0 ? sg_env : 2048 / (blocks > 0 ? blocks : 1);
-    if (sg_env <= 0 && sg < 2 && blocks < 1536) sg = 2;
+    const int blocks = (dims->N + D4GS_PROJ_BLOCK - 1) / D4GS_PROJ_BLOCK;
+    int sg = 2048 / (blocks > 0 ? blocks : 1);
+    if (sg < 2 && blocks < 1536) sg = 2;
     sg = sg < 1 ? 1 : (sg > dims->S ? dims->S : sg);
     ProfScope _ps("k_project_fwd", stream);
     void *kargs[] = {(void *)&a};
@@ -873,52 +857,37 @@ int d4gs_project_fwd_impl(const D4gsDims *dims, const D4gsProjIn *in, const D4gs
   }
   int rc = d4gs_check_launch("k_project_fwd");
   if (rc) return rc;
-  if (a.count_apart) {
-    const int pt = d4gs_chunk_per_thread(dims), per_block = COUNT_THREADS * pt;
-    const int cblocks = ((dims->N + per_block - 1) / per_block) * dims->S;
-    const bool lazy = d4gs_lazy_on(dims, out);
+  if (fp.count_apart) {
+    const bool lazy = d4gs_lazy_on(dims, out, fp);
     LazyWs lw{};
-    size_t cbytes = hist_bytes;
+    size_t cbytes = sizeof(int) * (size_t)fp.tiles;
     if (lazy) {  // depth range of every sub-sample first: it scales the (tile, depth bucket) histogram
-      lw = d4gs_lazy_carve(out->lazy_ws, dims->S, a.tw * a.th);
-      cbytes += hist_bytes * lw.nb;
+      lw = d4gs_lazy_carve(out->lazy_ws, dims->S, fp.tiles);
+      cbytes *= 1 + lw.nb;
       const int rblocks = 8;
       D4GS_LAUNCH("k_depth_range", k_depth_range, dim3(rblocks, dims->S), dim3(256), 0, stream, (const float *)out->depths,
                   (const int *)out->tiles_touched, dims->N, lw.zr);
     }
-#define D4GS_COUNT(PT_, LZ_)                                                                                                  \
-  do {                                                                                                                        \
-    if (cbytes > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_count_tiles<PT_, LZ_>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); /* (+ the kernel's static LDS <= 160 KB) */ \
-    D4GS_LAUNCH("k_count_tiles", (k_count_tiles<PT_, LZ_>), dim3(cblocks), dim3(COUNT_THREADS), cbytes, stream,              \
-                (const int *)out->tile_rects, (const int *)out->tiles_touched, dims->N, dims->S, a.tw, a.th, out->tile_counts, \
-                fused_chunks ? out->scan_ws : (int *)nullptr, (const float *)out->depths, lw,                                 \
-                (const uint64_t *)((dims->flags & D4GS_EXACT_TILES) ? out->tile_masks : nullptr));                            \
-  } while (0)
-    if (pt == 1 && lazy) D4GS_COUNT(1, true);
-    else if (pt == 1) D4GS_COUNT(1, false);
-    else if (pt == 2 && lazy) D4GS_COUNT(2, true);
-    else if (pt == 2) D4GS_COUNT(2, false);
-    else if (pt == 3 && lazy) D4GS_COUNT(3, true);
-    else if (pt == 3) D4GS_COUNT(3, false);
-    else if (pt == 5 && lazy) D4GS_COUNT(5, true);
-    else if (pt == 5) D4GS_COUNT(5, false);
-    else if (pt == 6 && lazy) D4GS_COUNT(6, true);
-    else if (pt == 6) D4GS_COUNT(6, false);
-    else if (lazy) D4GS_COUNT(4, true);
-    else D4GS_COUNT(4, false);
-#undef D4GS_COUNT
+    d4gs_with_pt(fp.pt, [&](auto pt) {
+      auto count = [&](auto kernel) {
+        d4gs_launch_chunks("k_count_tiles", kernel, fp, cbytes, stream, out->tile_rects, out->tiles_touched, dims->N, dims->S, fp.tw, fp.th,
+                           out->tile_counts, fp.fused_chunks ? out->scan_ws : nullptr, out->depths, lw,
+                           (dims->flags & D4GS_EXACT_TILES) ? out->tile_masks : nullptr);
+      };
+      lazy ? count(k_count_tiles<decltype(pt)::value, true>) : count(k_count_tiles<decltype(pt)::value, false>);
+    });
     // (the near / far pivot of every tile is chosen in d4gs_bin_sort, where the caller's D4gsIsect.near_target is known)
     rc = d4gs_check_launch("k_count_tiles");
     if (rc) return rc;
   }
-  const int sblocks = fused_chunks ? fused_chunks * dims->S : (int)((n_inst + SCAN_TILE - 1) / SCAN_TILE);
-  if (!fused_chunks)
+  const int sblocks = fp.fused_chunks ? fp.blocks : (int)((n_inst + SCAN_TILE - 1) / SCAN_TILE);
+  if (!fp.fused_chunks)
     D4GS_LAUNCH("k_scan_sums", k_scan_sums, dim3(sblocks), dim3(SCAN_THREADS), 0, stream, out->tiles_touched, n_inst,
                        out->scan_ws);
   const ScanJob jsums{out->scan_ws, nullptr, out->scan_ws, (int64_t)sblocks, 0, out->n_isect, nullptr};
-  const ScanJob jtiles{out->tile_counts, out->tile_counts + n_tiles, out->tile_offsets, (int64_t)n_tiles, 1, nullptr, out->n_isect + 1};
+  const ScanJob jtiles{out->tile_counts, out->tile_counts + fp.n_tiles, out->tile_offsets, (int64_t)fp.n_tiles, 1, nullptr, out->n_isect + 1};
   D4GS_LAUNCH("k_scan_single", k_scan_single, dim3(2), dim3(1024), 0, stream, jsums, jtiles);
-  if (!fused_chunks)  // (fused: k_emit writes isect_offsets)
+  if (!fp.fused_chunks)  // (fused: k_emit writes isect_offsets)
     D4GS_LAUNCH("k_scan_apply", k_scan_apply, dim3(sblocks), dim3(SCAN_THREADS), 0, stream, out->tiles_touched, out->scan_ws,
                        n_inst, out->isect_offsets);
   return d4gs_check_launch("scan");

@@ -534,10 +534,7 @@ template <> struct GatherArgsT<true> : GatherArgs { GatherAA aa; };
 // rows of LDS per wave: wide rows (D >= 8: 56 - 92 bytes) take half the rows, i.e. about the same bytes - the training shape's gather
 // 91 -> 77 us with twice the blocks per CU; narrow rows lose with smaller stages (cfg2 50 -> 53 -> 61 us at 128 / 96;
 // profiles/r04t_ab_gather_rows.txt)
-#ifndef D4GS_GATHER_ROWS_SPARSE
-#define D4GS_GATHER_ROWS_SPARSE 192
-#endif
-constexpr int gather_rows(int D, bool sparse) { return D >= 8 ? 96 : sparse ? D4GS_GATHER_ROWS_SPARSE : 192; }
+constexpr int gather_rows(int D) { return D >= 8 ? 96 : 192; }  // (dense and sparse rows alike: 96 for the sparse narrow rows measured no gain)
 constexpr int GATHER_SC = 1024;                         // rows per super-chunk of the cooperative sparse path (16 flags per lane)
 // ABS: rows of 6 + NCH + 2 floats (raster_bwd_q_body); the last two columns are summed, in the same order, into v_means2d_abs
 // AA: the rows' opacity column (the gradient of the effective opacity opac_act * comp) is split into comp * it for v_opac_act and the
@@ -548,7 +545,7 @@ __global__ void __launch_bounds__(SLOTS * 64) k_gather(const GatherArgsT<AA> a) 
   constexpr int NCH = D + (DEPTH ? 1 : 0);
   constexpr int DP = (D + 3) & ~3;
   constexpr int R = 6 + NCH + (ABS ? 2 : 0);
-  constexpr int GATHER_ROWS = gather_rows(D, SPARSE);
+  constexpr int GATHER_ROWS = gather_rows(D);
   __shared__ __attribute__((aligned(16))) float stage[SLOTS * GATHER_ROWS * R];
   __shared__ uint32_t slive[SPARSE ? SLOTS * 64 : 1];  // flags of a chunk as 4-byte words (<= GATHER_ROWS + 3 bytes)
   // cooperative sparse path (super-chunks of SC rows): the flags, the exclusive live-row count in front of every 16-row group
@@ -905,8 +902,8 @@ int d4gs_raster_bwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   a.fuse_blend = blend != nullptr;
   a.blend = blend ? *blend : BlendAdj{};
   a.N = dims->N, a.S = dims->S, a.width = dims->width, a.height = dims->height;
-  a.tw = (dims->width + D4GS_TILE - 1) / D4GS_TILE;
-  a.th = (dims->height + D4GS_TILE - 1) / D4GS_TILE;
+  const FrontPlan fp = d4gs_front_plan(dims);
+  a.tw = fp.tw, a.th = fp.th;
   a.ed = dims->depth_mode == D4GS_DEPTH_ED;
   a.geom = proj->geom, a.ctab = proj->ctab, a.background = r->background;
   a.tile_offsets = proj->tile_offsets, a.sorted_gid = isect->sorted_gid, a.sorted_emit = isect->sorted_emit;
@@ -938,7 +935,7 @@ int d4gs_raster_bwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   GatherAA gaa;
   gaa.comp = proj->compensations, gaa.opac_act = proj->opac_act, gaa.geom = proj->geom, gaa.eps2d = dims->eps2d;
   const bool dep = dims->depth_mode != D4GS_DEPTH_NONE;
-  const bool lazy = d4gs_lazy_on(dims, proj);
+  const bool lazy = d4gs_lazy_on(dims, proj, fp);
 #define D4GS_LBA(DD, DEP, ABS_) (aa ? launch_bwd<DD, DEP, ABS_, true>(a, ga, gaa, isect->n_isect, g->row_mode, lazy, stream) \
                                     : launch_bwd<DD, DEP, ABS_, false>(a, ga, gaa, isect->n_isect, g->row_mode, lazy, stream))
 #define D4GS_LB(DD, DEP) (absg ? D4GS_LBA(DD, DEP, true) : D4GS_LBA(DD, DEP, false))

@@ -507,11 +507,9 @@ int launch_fwd(const RasterFwdArgs &a, hipStream_t stream) {
 
 // ---- depth segments: when, and how much state (common.h) ----
 int64_t d4gs_seg_state_elems(const D4gsDims *d) {
-  const int64_t tw = (d->width + D4GS_TILE - 1) / D4GS_TILE, th = (d->height + D4GS_TILE - 1) / D4GS_TILE;
-  const int64_t n_tiles = (int64_t)d->S * tw * th;
+  const int64_t n_tiles = d4gs_front_plan(d).n_tiles;
   if (n_tiles > (d->D <= 4 ? D4GS_SEG_TILES_MAX_NARROW : D4GS_SEG_TILES_MAX)) return 0;
-  const int64_t nch = d->D + (d->depth_mode != D4GS_DEPTH_NONE ? 1 : 0);
-  return n_tiles * D4GS_SEG_MAX * (1 + nch) * 256;
+  return n_tiles * D4GS_SEG_MAX * (1 + d4gs_nch(d)) * 256;
 }
 bool d4gs_seg_on(const D4gsDims *d, const D4gsIsect *isect, const D4gsRaster *r) {
   const char *env = getenv("D4GS_SEG");  // (read per call: tests toggle it) "0": never, "1": whenever the buffer is there (tests); default: see below
@@ -530,8 +528,8 @@ int d4gs_raster_fwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
                          hipStream_t stream) {
   RasterFwdArgs a;
   a.N = dims->N, a.S = dims->S, a.width = dims->width, a.height = dims->height;
-  a.tw = (dims->width + D4GS_TILE - 1) / D4GS_TILE;
-  a.th = (dims->height + D4GS_TILE - 1) / D4GS_TILE;
+  const FrontPlan fp = d4gs_front_plan(dims);
+  a.tw = fp.tw, a.th = fp.th;
   a.ed = dims->depth_mode == D4GS_DEPTH_ED;
   a.geom = proj->geom, a.ctab = proj->ctab, a.background = r->background;
   a.tile_offsets = proj->tile_offsets, a.sorted_gid = isect->sorted_gid;
@@ -541,9 +539,9 @@ int d4gs_raster_fwd_impl(const D4gsDims *dims, const D4gsProjOut *proj, const D4
   a.lazy_near = nullptr, a.lazy_flag = nullptr, a.lazy_pass = 0;
   const char *bf = getenv("D4GS_BLOCK_FILTER");  // (read per call, like D4GS_SEG: tests and the A/B toggle it) "0": off
   a.block_filter = !(bf && bf[0] == '0');
-  const bool lazy = d4gs_lazy_on(dims, proj) && isect->n_isect > 0;
+  const bool lazy = d4gs_lazy_on(dims, proj, fp) && isect->n_isect > 0;
   if (lazy) {
-    const LazyWs lw = d4gs_lazy_carve(proj->lazy_ws, dims->S, a.tw * a.th);
+    const LazyWs lw = d4gs_lazy_carve(proj->lazy_ws, dims->S, fp.tiles);
     a.lazy_near = lw.near, a.lazy_flag = lw.flag, a.lazy_pass = 1;
   }
 #ifdef D4GS_TRACE

@@ -1,7 +1,7 @@
 """Two builds of libd4gs.so give the same bits in every loss and metric that sums in a fixed order (csrc/reduce.h) and in the
 rasterizer's forward and backward - and the losses take the same time.
 
-    python scripts/ab_bitwise.py PARENT.so [NEW.so] [--times] [--rounds 2] [--out FILE]
+    python scripts/ab_bitwise.py PARENT.so [NEW.so] [--times | --front] [--rounds 2] [--out FILE]
 
 PARENT.so: the parent commit's library (export it with `git archive <parent>` into the git-ignored scripts/ablate/parent/, build it there
 with `python -m deblur4dgs_amd.build --force`); NEW.so defaults to this tree's deblur4dgs_amd/libd4gs.so.  D4GS_LIB_PATH is read when
@@ -14,6 +14,9 @@ path of pwcnet, spherical harmonics forward and backward with a view-origin grad
 shape of the loss's GPU test and one whose count of block partials exceeds 256 (aligned L1 caps its partials at 128 per pair: that
 size), and prints the sha256 of every output and gradient.  The rasterizer's cases (_raster_cases) follow, at 6 000 splats on 200 x 120
 and 30 000 on 320 x 200.  The script fails if a digest differs between the libraries.
+
+--front: the digests of the list front end's and the projection backward's cases instead (_front_cases: one per launch rule of
+csrc/host.h's FrontPlan and of project_bwd.hip), plain and with each of the three hooks the tests keep set in a child of its own.
 
 --times: the losses at their own benchmarks' sizes (scripts/bench_photometric.py, bench_metrics.py, bench_trimmed.py, bench_aligned.py's
 frame and pair count for the aligned L1 alone, bench_sh.py's first configuration, the regularizers at the size of
@@ -225,11 +228,100 @@ def _raster_cases():
             "frame S=4 one call": frame}
 
 
-def child(times, iters, windows):
+# the (N, lazy lists, instances per lane) rows of the list front end at S = 64 on 64 x 64: tests/test_gpu_front_plan.py derives them
+HOOKS = ("D4GS_COUNT_IN_PROJECT", "D4GS_NO_FUSED_SCAN", "D4GS_SORT_NO_MERGE_LONG")  # --front: one more child per library with each set
+
+
+def _front_cases():
+    """The list front end and the projection backward, one case per launch rule of csrc/host.h's FrontPlan and of project_bwd.hip: every
+    instances-per-lane arm of k_count_tiles / k_emit; k_project_fwd<XT, TAB, AA> in all eight combinations (exact tiles, K = 12 against
+    K = 6 for the bases table, antialiased) on a dynamic scene of S = 8; one sub-sample group (>= 1 536 blocks) against several; the
+    three tails of launch_project_bwd - n_shared <= 160 (S = 1, K = 6), the one-block k_finish (S = 8, K = 6, T = 10), the two launches
+    (S = 8, K = 20: n_shared 1 548; K = 6, T = 160: 8 640 leaf elements); the sub-group mappings S = 1, 2, 4 and the poses adjoint; the
+    one-call frame with the blend's adjoint folded (D = 3) and launched (D = 16); a backward without D4gsProjOut.blend_bases; a scene of
+    mostly short lists with some of 513 ... 2 048 keys (tests/ladder.py "mid": the merge_long regime)."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from deblur4dgs_amd import engine
+    from deblur4dgs_amd.exposure import render_exposure
+    from deblur4dgs_amd.synth import make_scene
+    from tests import ladder, test_gpu_front_plan as fp
+    from tests.test_gpu_list_edges import _render as ladder_render
+
+    dev = "cuda:0"
+    names = ("means", "quats", "scales", "opacities", "colors", "motion_coefs", "rots", "transls", "times", "RTs", "viewmat")
+    small_only = lambda run: (lambda size: run if size == "small" else (lambda: []))
+
+    def arm(N, lazy):
+        def run():
+            leaves, w2c, K = fp._scene(N)
+            r, offs, ids = fp._render(leaves, w2c, K, fp.S, lazy)
+            return [r["renders"], r["alphas"], r["means2d"], r["radii"], offs] + ([] if lazy else [ids[:int(offs[-1])]])
+        return small_only(run)
+
+    def dynamic(N, G, K_, S, T=24, D=3, W=96, H=64, fused=False, drop_table=False, **kw):
+        def run():
+            sc = make_scene(N, G, K_, S, W, H, seed=41, T=T, D=D, cam_jitter=0.01)
+            L = {k: sc[k].to(dev).clone().requires_grad_() for k in names}
+            g = torch.Generator().manual_seed(5)
+            wb, wa = torch.randn(H, W, D + 1, generator=g).to(dev), torch.randn(H, W, generator=g).to(dev)
+            r = render_exposure(*(L[k] for k in names[:5]), min(D, 3), *(L[k] for k in names[5:]), sc["K"].to(dev), W, H, return_depth=True,
+                                blend=True, fused=fused, lazy_sort=False, **kw)
+            assert bool(r["state"].frame_io) == fused
+            if drop_table:
+                r["state"].proj_out["blend_bases"] = None
+            ((r["blended"] * wb).sum() + (r["acc"] * wa).sum()).backward()
+            torch.cuda.synchronize()
+            return [r["blended"].detach(), r["acc"].detach(), r["renders"].detach(), r["means2d"].detach(), r["radii"]] + [L[k].grad for k in names]
+        return small_only(run)
+
+    def one_group():
+        leaves, w2c, K = fp._scene(400000)  # 1 563 blocks of 256: one sub-sample group
+        r, offs, ids = fp._render(leaves, w2c, K, 2, False)
+        return [r["renders"], r["means2d"], r["radii"], offs, ids[:int(offs[-1])]]
+
+    def poses():
+        sc = make_scene(3000, 2000, 6, 4, 64, 48, seed=43)
+        L = [sc[k].to(dev).clone().requires_grad_() for k in ("means", "quats", "motion_coefs", "rots", "transls")]
+        m, q, _ = engine.poses(*L, sc["times"].to(dev))
+        g = torch.Generator().manual_seed(6)
+        ((m * torch.randn(m.shape, generator=g).to(dev)).sum() + (q * torch.randn(q.shape, generator=g).to(dev)).sum()).backward()
+        torch.cuda.synchronize()
+        return [m.detach(), q.detach()] + [x.grad for x in L]
+
+    def mid_lists():
+        sc = ladder.build("mid")
+        engine._SIZE_GUESS.clear()
+        rc, ra, info, _ = ladder_render(sc, "RGB")
+        torch.cuda.synchronize()
+        return [rc, ra, info["flatten_ids"], info["isect_offsets"]]
+
+    cases = {f"front N={N}{' lazy' if lazy else ''} (per lane: {pt})": arm(N, lazy) for N, lazy, pt in fp.ROWS}
+    for xt in (False, True):
+        for K_ in (6, 12):
+            for aa in (False, True):
+                cases[f"project XT={int(xt)} TAB={int(K_ >= 10)} AA={int(aa)} S=8"] = dynamic(2500, 1500, K_, 8, exact_tiles=xt, antialiased=aa)
+    cases["project one sub-sample group"] = small_only(one_group)
+    cases["project_bwd tail n_shared<=160 (S=1 K=6)"] = dynamic(2500, 1500, 6, 1)
+    cases["project_bwd tail one-block k_finish (S=8 K=6 T=10)"] = dynamic(2500, 1500, 6, 8, T=10)
+    cases["project_bwd tail two launches (S=8 K=20)"] = dynamic(2500, 1500, 20, 8)
+    cases["project_bwd tail two launches (K=6 T=160)"] = dynamic(2500, 1500, 6, 8, T=160)
+    cases["project_bwd sub-groups S=2"] = dynamic(2500, 1500, 6, 2)
+    cases["project_bwd sub-groups S=4"] = dynamic(2500, 1500, 6, 4)
+    cases["poses fwd + adjoint"] = small_only(poses)
+    cases["frame one call, blend adjoint folded (D=3)"] = dynamic(2500, 1500, 6, 4, fused=True)
+    cases["frame one call, k_blend_bwd (D=16)"] = dynamic(2500, 1500, 6, 4, D=16, fused=True)
+    cases["backward without blend_bases"] = dynamic(2500, 1500, 6, 4, drop_table=True)
+    cases["lists mid (merge_long)"] = small_only(mid_lists)
+    return cases
+
+
+def child(times, iters, windows, front=False):
     import torch
 
     assert torch.cuda.is_available(), "ab_bitwise.py runs on the GPU"
-    cases = _cases() if times else {**_cases(), **_raster_cases()}  # (the composites are timed by bench.py, not here)
+    cases = _front_cases() if front else _cases() if times else {**_cases(), **_raster_cases()}  # (the composites are timed by bench.py, not here)
     for name, make in cases.items():
         if not times:
             for size in ("small", "large"):
@@ -261,8 +353,8 @@ def child(times, iters, windows):
         print("TIME " + json.dumps({"case": name, "median_us": statistics.median(us), "min_us": min(us), "max_us": max(us)}), flush=True)
 
 
-def run_child(lib, extra):
-    env = dict(os.environ, D4GS_LIB_PATH=os.path.abspath(lib))
+def run_child(lib, extra, env_extra=None):
+    env = dict(os.environ, D4GS_LIB_PATH=os.path.abspath(lib), **(env_extra or {}))
     cmd = ["timeout", "-k", "10", str(CHILD_SECONDS), sys.executable, os.path.abspath(__file__), "--child", *extra]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
     if r.returncode != 0:
@@ -277,22 +369,27 @@ def main():
     ap.add_argument("new", nargs="?", default=os.path.join(ROOT, "deblur4dgs_amd", "libd4gs.so"))
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--times", action="store_true")
+    ap.add_argument("--front", action="store_true")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.child:
-        return child(a.times, a.iters, a.windows)
+        return child(a.times, a.iters, a.windows, a.front)
     if not a.parent:
         ap.error("the parent commit's library is required")
     sha = lambda p: hashlib.sha256(open(p, "rb").read()).hexdigest()
     lines = [f"parent {sha(a.parent)}  {os.path.relpath(a.parent, ROOT)}", f"new    {sha(a.new)}  {os.path.relpath(a.new, ROOT)}"]
     ok = True
     if not a.times:
-        dig = {}
-        for tag, lib in (("parent", a.parent), ("new", a.new)):
-            dig[tag] = {k: v for k, v in (ln[7:].rsplit(" | ", 1) for ln in run_child(lib, []) if ln.startswith("DIGEST "))}
+        dig = {"parent": {}, "new": {}}
+        # --front: the front end's cases, once plain and once per kept hook (read once per process: a child of its own each)
+        runs = [("", {})] + [(f"[{h}=1] ", {h: "1"}) for h in HOOKS] if a.front else [("", {})]
+        for prefix, hook in runs:
+            for tag, lib in (("parent", a.parent), ("new", a.new)):
+                out = run_child(lib, ["--front"] if a.front else [], hook)
+                dig[tag].update({prefix + k: v for k, v in (ln[7:].rsplit(" | ", 1) for ln in out if ln.startswith("DIGEST "))})
         assert dig["parent"] and dig["parent"].keys() == dig["new"].keys(), "the two children did not run the same cases"
         for k, h in dig["parent"].items():
             same = dig["new"][k] == h
