@@ -76,3 +76,72 @@ def check_columns(case: str, tensor: str, got, ref, tol: float = 1e-4):
     bad = [(c, f"{e:.2e}") for c, e in enumerate(worst) if not e <= tol]
     assert not bad, f"{case} / {tensor}: columns off by > {tol:g} x max|ref[..., c]|: {bad}"
     return max(worst)
+
+
+# ---- the row norm -------------------------------------------------------------------------------------------
+# Per-Gaussian gradients are heavy-tailed: a few large, bright splats set max|ref| and most rows sit decades below it, so the tensor
+# norm of `check` holds the median row to percents of its own size.  `check_rows` states the error of every row against that row's
+# own scale, as a DISTRIBUTION (an ill-conditioned row, whose pixel contributions cancel, misses 1e-4 of itself in any fp32 evaluation).
+ROW_LEVELS = (1e-4, 1e-3, 1e-2)      # 1e-4: north_star / GTOL
+ROW_CAPS = (0.10, 0.01, 0.005)       # share of the live rows allowed beyond each level (conditions, not measurements)
+ROW_SMALL_GROUP = 200                # fewer live rows than this: one row more beyond each level
+ROW_YARD_RATIO = 4.0                 # device median / 90 % quantile <= this x the fp32 oracle's (summation order, exp2 / rcp, one rounding per stage)
+ROW_YARD_FLOOR = 2.5e-6              # ... which is never taken below this
+
+
+def _rows64(x):
+    x = x.detach().double().cpu().numpy() if torch.is_tensor(x) else np.asarray(x, np.float64)
+    return x.reshape(x.shape[0], -1)
+
+
+def row_errors(got, ref):
+    """-> (r [n_live], live [N] bool).  Rows = leading axis (one Gaussian each), the other axes flattened; a row is live when its
+    reference row has a non-zero element; r_i = max_j |got_ij - ref_ij| / max_j |ref_ij| over the live rows."""
+    g, r = _rows64(got), _rows64(ref)
+    assert g.shape == r.shape, (g.shape, r.shape)
+    if r.shape[0] == 0:
+        return np.zeros(0), np.zeros(0, bool)
+    top = np.abs(r).max(1)
+    live = top > 0
+    return np.abs(g - r).max(1)[live] / top[live], live
+
+
+def _row_stats(r):
+    if r.size == 0:
+        return dict(median=0.0, q90=0.0, shares=[0.0] * len(ROW_LEVELS))
+    return dict(median=float(np.quantile(r, 0.5)), q90=float(np.quantile(r, 0.9)), shares=[float((r > lv).mean()) for lv in ROW_LEVELS])
+
+
+def check_rows(case: str, tensor: str, got, ref, yard=None, dead=None, ratio=ROW_YARD_RATIO, cap_scale: float = 1.0):
+    """Record and assert the per-ROW statement of `got` against the fp64 `ref`:
+      caps      the share of live rows with r_i beyond ROW_LEVELS is at most ROW_CAPS (x cap_scale), one row more where fewer than
+                ROW_SMALL_GROUP rows are live;
+      yardstick `yard` = the same quantity from the oracle evaluated in fp32 on the same inputs: the median and the 90 % quantile of r_i
+                are at most `ratio` x the yardstick's (floored at ROW_YARD_FLOOR); ratio=None logs the yardstick without judging by it;
+      dead      bool [N]: rows culled on both sides, exactly zero in `got`.
+    -> the logged entry (tests/util.record's keys plus the shares, both quantile pairs and norm="per row")."""
+    record(case, tensor, got, ref)
+    entry = PARITY_LOG[-1]
+    r, live = row_errors(got, ref)
+    n = int(r.size)
+    st = _row_stats(r)
+    entry.update(norm="per row", live_rows=n, median=st["median"], q90=st["q90"],
+                 share_1e4=st["shares"][0], share_1e3=st["shares"][1], share_1e2=st["shares"][2], asserted_caps=[c * cap_scale for c in ROW_CAPS])
+    if yard is not None:
+        ys = _row_stats(np.abs(_rows64(yard) - _rows64(ref)).max(1)[live] / np.abs(_rows64(ref)).max(1)[live] if n else np.zeros(0))
+        entry.update(yard_median=ys["median"], yard_q90=ys["q90"], yard_share_1e4=ys["shares"][0], yard_share_1e3=ys["shares"][1],
+                     yard_share_1e2=ys["shares"][2], asserted_ratio=ratio)
+    if os.environ.get("D4GS_PARITY_MEASURE"):
+        return entry
+    extra = 1 if n < ROW_SMALL_GROUP else 0
+    for lv, cap, share in zip(ROW_LEVELS, ROW_CAPS, st["shares"]):
+        assert round(share * n) <= cap * cap_scale * n + extra, \
+            f"{case} / {tensor}: {share:.2%} of the {n} live rows off by > {lv:g} x their own max|ref| (cap {cap * cap_scale:.2%}; median {st['median']:.2e}, q90 {st['q90']:.2e})"
+    if yard is not None and ratio is not None:
+        for q in ("median", "q90"):
+            lim = ratio * max(ys[q], ROW_YARD_FLOOR)
+            assert st[q] <= lim, f"{case} / {tensor}: per-row {q} {st[q]:.2e} > {ratio:g} x the fp32 oracle's {ys[q]:.2e} (floor {ROW_YARD_FLOOR:g})"
+    if dead is not None:
+        d = np.asarray(dead.cpu() if torch.is_tensor(dead) else dead, bool)
+        assert not np.abs(_rows64(got))[d].any(), f"{case} / {tensor}: {int(np.abs(_rows64(got))[d].any(1).sum())} culled rows are not exactly zero"
+    return entry
