@@ -7,6 +7,7 @@
 // round; a 4 M-element tensor is 2048 workgroups, one residency round of the chip - the same code, no per-tensor launch.
 // The bias corrections want beta^t: an fp64 square-and-multiply on the integer step (<= 24 rounds, once per thread, while the
 // loads are in flight), so the CPU twin gets the same bits without trusting two libm pow() to agree.
+#include "adam_math.h"  // AdamCoef, adam_coef, adam_update: the per-element update, shared with pose_refine.hip
 #include "common.h"
 
 namespace {
@@ -16,44 +17,6 @@ constexpr int ADAM_VEC_ITERS = D4GS_ADAM_CHUNK / (4 * ADAM_BLOCK);
 constexpr int ADAM_DWORD_ITERS = D4GS_ADAM_CHUNK / ADAM_BLOCK;
 constexpr int ADAM_PATCH = 64;  // gradient pointers per k_adam_set_grads launch (512 B of kernel arguments)
 static_assert(D4GS_ADAM_CHUNK % (4 * ADAM_BLOCK) == 0, "a chunk is a whole number of float4 rounds of the block");
-
-struct AdamCoef {
-  float w1, b2, w2;     // 1 - beta1, beta2, 1 - beta2
-  float neg_step_size;  // -lr / (1 - beta1^t)
-  float bc2_sqrt;       // sqrt(1 - beta2^t)
-  float eps;
-};
-
-__host__ __device__ inline double adam_ipow(double b, int t) {
-  double r = 1.0;
-  for (; t > 0; t >>= 1, b *= b)
-    if (t & 1) r *= b;
-  return r;
-}
-
-// t: the step count AFTER this update (>= 1), exact in fp32 like torch's `step` tensor
-__host__ __device__ inline AdamCoef adam_coef(double lr, double beta1, double beta2, double eps, float t) {
-  const int ti = (int)t;
-  AdamCoef c;
-  c.w1 = (float)(1.0 - beta1), c.b2 = (float)beta2, c.w2 = (float)(1.0 - beta2);
-  c.neg_step_size = (float)(-(lr / (1.0 - adam_ipow(beta1, ti))));
-  c.bc2_sqrt = (float)sqrt(1.0 - adam_ipow(beta2, ti));
-  c.eps = (float)eps;
-  return c;
-}
-
-// THE per-element update (device kernel and CPU twin), in the order of torch's single-tensor Adam: lerp_ (one FMA),
-// mul_ + addcmul_ (value * g rounded, then one FMA), sqrt / bias_correction2_sqrt + eps, addcdiv_ ((value * m) / denom, then the
-// add).  Written this way both moments come out bit-identical to torch's fp32 CPU path; sqrt and the divisions are the correctly
-// rounded ones.  The FMAs are explicit and contraction is off, so the twin (host compiler) and the kernel (device compiler)
-// cannot each pick their own.
-__host__ __device__ __forceinline__ void adam_update(float &p, float &m, float &v, float g, const AdamCoef &c) {
-#pragma clang fp contract(off)
-  m = __builtin_fmaf(c.w1, g - m, m);
-  v = __builtin_fmaf(c.w2 * g, g, v * c.b2);
-  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
-  p = p + (c.neg_step_size * m) / denom;
-}
 
 __device__ __forceinline__ void adam_update4(float4 &p, float4 &m, float4 &v, const float4 g, const AdamCoef &c) {
   adam_update(p.x, m.x, v.x, g.x, c);

@@ -105,6 +105,7 @@ static int check_dims(const D4gsDims *d) {
   }
   return D4GS_OK;
 }
+int d4gs_check_dims(const D4gsDims *d) { return check_dims(d); }
 
 extern "C" {
 

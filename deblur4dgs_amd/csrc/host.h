@@ -17,6 +17,7 @@
 // ---- error plumbing and argument checks (capi.hip) ------------------------------------------------------------------------
 void d4gs_set_error(const char *fmt, ...);  // the thread's d4gs_last_error() message
 int d4gs_check_launch(const char *what);    // hipGetLastError() -> D4GS_OK / D4GS_ELAUNCH (+ message)
+int d4gs_check_dims(const D4gsDims *d);     // the dims every render entry point accepts -> D4GS_OK / D4GS_EINVAL (+ message)
 // D4GS_ABSGRAD and its buffers come together; so do D4GS_ANTIALIASED and D4gsProjOut.compensations
 int d4gs_check_absgrad(const char *who, const D4gsDims *d, const float *v_means2d_abs, int32_t stats_absgrad);
 int d4gs_check_antialiased(const char *who, const D4gsDims *d, const float *compensations);

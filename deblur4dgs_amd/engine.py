@@ -3,6 +3,7 @@ HIP kernels on torch's current stream.
 
   ProjectFn   leaf params (+ bases, times, camera deltas, viewmat)  ->  means2d, conics, depths  [S,N,...],
               activated opacities / colour table.   fwd: d4gs_project_fwd     bwd: d4gs_project_bwd
+              (RenderCfg.pose_only: d4gs_pose_bwd - the camera's gradients and nothing else)
   RasterFn    those per-instance tensors                            ->  render_colors [S,H,W,D'], alphas
               fwd: d4gs_bin_sort + d4gs_raster_fwd                   bwd: d4gs_raster_bwd
   FrameFn     the leaves -> blended frame, accumulation, renders, alphas: the whole staged chain (and the blend) as ONE
@@ -79,6 +80,9 @@ class RenderCfg:
     #                                  alpha >= 1/255 ellipse reaches.  Same image and gradients bit for bit, shorter lists; the test costs the
     #                                  projection ~1 instruction per candidate pair and lane, so None (D4GS_EXACT_TILES=auto) turns it on from
     #                                  EXACT_TILES_FROM intersections per instance, measured by the previous render of the shape
+    pose_only: bool = False  # the scene is frozen and only the camera is differentiated (test-time pose refinement, pose_refine.py):
+    #                          ProjectFn's backward calls d4gs_pose_bwd and returns gradients for `RTs` and `viewmat` alone - every other
+    #                          leaf gets None, and no leaf-gradient buffer is allocated.  The staged chain only (frame_supported)
 
     @property
     def DP(self) -> int:
@@ -593,15 +597,25 @@ class ProjectFn(torch.autograd.Function):
         dev = o["means2d"].device
         z = lambda g, ref: torch.zeros_like(ref) if g is None else g.to(torch.float32).contiguous()
         v_means2d, v_conics, v_depths = z(v_means2d, o["means2d"]), z(v_conics, o["conics"]), z(v_depths, o["depths"])
-        v_opac_act, v_ctab = z(v_opac_act, o["opac_act"]), z(v_ctab, o["ctab"])
         lib = L.lib()
         dims = cfg.dims()
         pi = dict(zip(_PROJ_IN, ctx.saved_tensors))  # raises if a leaf was modified in place since the forward
+        vp = lambda t: C.c_void_p(L.ptr(t))  # bare Python ints would be truncated to 32-bit C ints
+        if cfg.pose_only:  # the camera's adjoint alone: v_opac_act and v_ctab do not reach it, and nothing of size N is written
+            f32 = dict(dtype=torch.float32, device=dev)
+            g = dict.fromkeys(_LEAVES)
+            g["viewmat"] = torch.empty(4, 4, **f32)
+            g["RTs"] = torch.empty(cfg.S, 3, 4, **f32) if pi["RTs"] is not None and ctx.needs[_LEAVES.index("RTs")] else None
+            partials = torch.empty(lib.d4gs_pose_bwd_partials_elems(C.byref(dims)), **f32)
+            L.check(lib.d4gs_pose_bwd(C.byref(dims), C.byref(L.fill(L.ProjIn(), **pi)), C.byref(L.fill(L.ProjOut(), **st.proj_out)),
+                                      vp(v_means2d), vp(v_conics), vp(v_depths), vp(g["viewmat"]), vp(g["RTs"]), vp(partials),
+                                      _stream()), "d4gs_pose_bwd")
+            return (None, *_only_needed([g[k] for k in _LEAVES], ctx.needs), None)
+        v_opac_act, v_ctab = z(v_opac_act, o["opac_act"]), z(v_ctab, o["ctab"])
         g = _leaf_grads(cfg, dims, pi, dev, with_partials=True)
         pin = L.fill(L.ProjIn(), **pi)
         pout = L.fill(L.ProjOut(), **st.proj_out)
         lg = L.fill(L.LeafGrads(), **g)
-        vp = lambda t: C.c_void_p(L.ptr(t))  # bare Python ints would be truncated to 32-bit C ints
         L.check(lib.d4gs_project_bwd(C.byref(dims), C.byref(pin), C.byref(pout), vp(v_means2d), vp(v_conics),
                                      vp(v_depths), vp(v_opac_act), vp(v_ctab), C.byref(lg), _stream()),
                 "d4gs_project_bwd")
@@ -923,8 +937,9 @@ FRAME_BLEND_MAX_S = 129  # D4GS_FRAME_BLEND_MAX_S of include/d4gs.h
 def frame_supported(cfg: RenderCfg, blended: bool = True) -> bool:
     """One kernel width, no channel chunking: what the one-call path covers.  With a blended frame, at most FRAME_BLEND_MAX_S
     sub-samples: its winner map holds the max / min channels' winning sub-sample (0 .. S - 2) in one signed byte - beyond that
-    d4gs_forward refuses and the staged chain, whose k_blend_bwd searches the renders, takes the frame."""
-    return cfg.N > 0 and cfg.D in SUPPORTED_D and not (blended and cfg.S > FRAME_BLEND_MAX_S)
+    d4gs_forward refuses and the staged chain, whose k_blend_bwd searches the renders, takes the frame.  Not with cfg.pose_only: the
+    camera-only backward is a stage of the staged chain."""
+    return cfg.N > 0 and cfg.D in SUPPORTED_D and not (blended and cfg.S > FRAME_BLEND_MAX_S) and not cfg.pose_only
 
 
 class PosesFn(torch.autograd.Function):

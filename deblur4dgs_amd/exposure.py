@@ -90,6 +90,7 @@ def render_exposure(
     exact_tiles: bool | None = None,
     absgrad: bool = False,
     antialiased: bool = False,
+    pose_only: bool = False,
 ):
     """-> dict(renders [S,H,W,D'], alphas [S,H,W,1], blended [H,W,D'] | None, acc [H,W] | None,
                means2d [S,N,2], radii [S,N], state).
@@ -99,7 +100,8 @@ def render_exposure(
     absgrad=True (RenderCfg.absgrad): the backward also leaves gsplat's absgrad [S,N,2] in state.v_means2d_abs (and as `.absgrad`
     of `means2d` on the staged chain, of the xys_sink tensors on the one-call path).
     antialiased=True (RenderCfg.antialiased): gsplat's rasterize_mode="antialiased" - every sub-sample composites with opacity *
-    compensation (D4GS_ANTIALIASED); the staged chain keeps the compensations in state.proj_out["compensations"] [S,N]."""
+    compensation (D4GS_ANTIALIASED); the staged chain keeps the compensations in state.proj_out["compensations"] [S,N].
+    pose_only=True (RenderCfg.pose_only): the backward differentiates `RTs` and `w2c` alone (d4gs_pose_bwd); the staged chain."""
     N = means.shape[0]
     G = 0 if motion_coefs is None else motion_coefs.shape[0]
     S = 1 if times is None else times.shape[0]
@@ -111,7 +113,7 @@ def render_exposure(
                     depth_mode=L.DEPTH_ED if return_depth else L.DEPTH_NONE, flags=flags, n_sigmoid=n_sigmoid,
                     exact_cull=exact_cull, grad_arena=grad_arena, control_stats=control_stats,
                     deferred_size_check=deferred_size_check, lazy_sort=lazy_sort, near_target=near_target, exact_tiles=exact_tiles,
-                    absgrad=absgrad, antialiased=antialiased)
+                    absgrad=absgrad, antialiased=antialiased, pose_only=pose_only)
     if fused and frame_supported(cfg, blended=blend):
         # ONE autograd node over d4gs_forward / d4gs_backward: same kernels and bits as the staged chain below, a fraction
         # of its host work.  `means2d` is then a plain tensor; its gradient goes to st.xys_sink / st.v_means2d.

@@ -162,6 +162,8 @@ class SceneModel(nn.Module):
         #                    as the staged chain, a fraction of the host work); False: always the staged chain
         self.deferred_size_check = False  # True: renders never wait for the device-side intersection count (engine
         #                                   RenderCfg.deferred_size_check; call engine.check_deferred() once per step)
+        self.pose_only = False  # True: the scene is frozen and a backward differentiates only the camera - `w2cs` and, through the camera
+        #                         deltas, the MoveModel (engine RenderCfg.pose_only; pose_refine.refine_pose sets it for its own renders)
 
     def attach_control_stats(self, running_stats: dict, batch_size: int, update_max_radii: bool = False, absgrad: bool = False):
         """SURVEY 8f-1, fused: until `detach_control_stats()`, the backward of every full render (all Gaussians, no
@@ -359,7 +361,7 @@ class SceneModel(nn.Module):
             times_s if G > 0 else None, RTs_s, w2cs[0], Ks[0], W, H, background=bg_color[0], return_depth=return_depth,
             policy=None, blend=True,
             control_stats=self._sink_for(N) if (which == "all" and filter_mask is None) else None,
-            deferred_size_check=self.deferred_size_check, fused=self.fused,
+            deferred_size_check=self.deferred_size_check, fused=self.fused, pose_only=self.pose_only,
             absgrad=self._stats_sink is not None and self._stats_sink[3] and torch.is_grad_enabled())
         blended = res["blended"][None]  # [1,H,W,D']
         renders = res["renders"]

@@ -836,6 +836,53 @@ D4GS_INIT_API int d4gs_kmeans_step(const float *x, int32_t G, int32_t D, int32_t
 D4GS_INIT_API int d4gs_procrustes_moments(const float *xyz, const float *weights, const float *conf, const int32_t *order,
                                           const int32_t *seg, int32_t G, int32_t T, int32_t K, int32_t cano_t, double *out, void *stream);
 
+/* Test-time pose refinement (appended; D4GS_VERSION unchanged): what Validator.validate_imgs_with_optimization (flow3d/validator.py:
+ * 400-456) runs per validation frame - 500 iterations of render, L1, backward into a free 3x3 transR and a 3x1 transT composed into
+ * w2c, CosineAnnealingLR.step(), Adam.step() - needs beyond the render.  The block is declared under a macro of its own, like the
+ * scene initialisation: D4GS_EVAL_API is the evaluation-time block (the binding's EVAL_PROTOTYPES); exported, parsed by the same
+ * strict rules and bound by the same call.  csrc/pose_refine.hip; DESIGN.md section 25.
+ *
+ * d4gs_pose_bwd: the camera-only adjoint of d4gs_project_fwd.  From the three cotangents v_means2d [S,N,2], v_conics [S,N,3] and
+ * v_depths [S,N] (v_opac_act and v_ctab do not reach the camera; with D4GS_ANTIALIASED the compensation's adjoint arrives folded
+ * into v_conics) it writes what d4gs_project_bwd leaves in D4gsLeafGrads.v_viewmat / .v_RTs - the same mathematics, summed in
+ * another order - and NO per-Gaussian gradient: nothing of size N is allocated, computed or written.  v_viewmat [4,4]: rows 0-2 the
+ * gradient, row 3 exact zeros.  v_RTs [S,3,4] or NULL (not wanted; with in->RTs == NULL it must be NULL).  Reads in->means, quats,
+ * scales, viewmat, Kmat, RTs and, for G > 0, motion_coefs, rots, transls, times (the deformation is recomputed from the leaves and
+ * proj->blend_bases; without that table it is built behind the partial sums, one small launch more); proj->radii and proj->conics
+ * (an instance with radii == 0 contributes nothing: near / far plane, radius_clip and the screen test are the forward's decisions).
+ * Honours D4GS_RAW_PARAMS and the 1.3 tan(fov / 2) clamp of the Jacobian; opacities, colours and their tables are not read.
+ * One lane per (sub-sample, Gaussian), gridDim.y = S; the 24 values of a lane (12 of the view matrix, 12 of its sub-sample's camera
+ * delta) are summed per block and then over the blocks in the fixed order of csrc/reduce.h - no atomics, nothing to zero: bitwise
+ * reproducible from run to run and graph replay to graph replay.  partials: d4gs_pose_bwd_partials_elems(dims) floats of scratch
+ * (host arithmetic only; 0 for dims the entry point refuses).  D4GS_EINVAL, before any HIP call, for bad dims (G > N among them),
+ * a NULL required pointer, a NULL partials, or v_RTs without in->RTs.
+ *
+ * d4gs_pose_step: one one-wave launch that ends an iteration and prepares the next.  w2c [4,4] the base matrix [R0 t0; .], v_W [4,4]
+ * the gradient of the composed matrix, p [12] the parameters (transR row-major, then transT), m, v [12] Adam's moments, step [1]
+ * int32 the number of updates made - all in device memory, so a captured launch stays valid while the learning rate moves.
+ *   g[0:9] = v_W[:3,:3] R0^T,  g[9:12] = v_W[:3,3]
+ *   k = step + 1;  lr = eta_min + (lr0 - eta_min) (1 + cos(pi k / t_max)) / 2 in double: the reference calls scheduler.step() BEFORE
+ *   optimizer.step(), so update i (from 0) runs at lr(i + 1) and update t_max - 1 at eta_min
+ *   torch.optim.Adam on (p, m, v) with gradient g, learning rate lr and t = k: d4gs_adam_step's per-element update
+ *   step <- k;  lr_out[0] <- (float)lr (may be NULL);  W [4,4] <- [transR R0 | transT + t0; 0 0 0 1]
+ * W may be the buffer v_W was taken with respect to, not w2c.  The reference leaves ZEROS in the bottom row of its composed matrix
+ * (torch.zeros_like(w2c), validator.py:442); nothing reads that row - the projection, the MoveModel's pose encoding and both
+ * adjoints use rows 0-2 - so (0, 0, 0, 1) is written, and every other matrix of the package stays a rigid transform.
+ * D4GS_EINVAL, before any HIP call, for a NULL (lr_out excepted) or misaligned pointer or t_max < 1.
+ * d4gs_pose_step_cpu: the same inline function on HOST pointers, one thread, no stream.  Never a fallback. */
+#define D4GS_EVAL_API __attribute__((visibility("default")))
+D4GS_EVAL_API size_t d4gs_pose_bwd_partials_elems(const D4gsDims *dims);
+D4GS_EVAL_API int d4gs_pose_bwd(const D4gsDims *dims, const D4gsProjIn *in, const D4gsProjOut *proj, const float *v_means2d,
+                                const float *v_conics, const float *v_depths, float *v_viewmat, float *v_RTs, float *partials,
+                                void *stream);
+D4GS_EVAL_API int d4gs_pose_step(const float *w2c, const float *v_W, float *p, float *m, float *v, int32_t *step, double lr0,
+                                 double eta_min, int32_t t_max, double beta1, double beta2, double eps, float *lr_out, float *W,
+                                 void *stream);
+D4GS_EVAL_API int d4gs_pose_step_cpu(const float *w2c /* [host] */, const float *v_W /* [host] */, float *p /* [host] */,
+                                     float *m /* [host] */, float *v /* [host] */, int32_t *step /* [host] */, double lr0,
+                                     double eta_min, int32_t t_max, double beta1, double beta2, double eps,
+                                     float *lr_out /* [host] */, float *W /* [host] */);
+
 #ifdef __cplusplus
 }
 #endif
