@@ -1,10 +1,15 @@
 """A scene from nothing but tracks: synthetic 3-D tracks and static points -> deblur4dgs_amd.scene_init -> SceneModel -> one render.
 
-    python examples/init_scene.py [--tracks 4000] [--frames 12] [--bases 6] [--points 8000]
+    python examples/init_scene.py [--tracks 4000] [--frames 12] [--bases 6] [--points 8000] [--from-2d]
 
 What a user with a reference-format dataset does before training: `init_motion_params_with_procrustes` clusters the tracks' velocity
 directions (HIP k-means), fits an SE(3) per (basis, frame) pair (HIP moments + one batched SVD on the host), `init_fg_from_tracks_3d`
-and `init_bg` size the Gaussians by their 3 nearest neighbours (HIP kNN).  Prints the shapes of what comes out."""
+and `init_bg` size the Gaussians by their 3 nearest neighbours (HIP kNN).  Prints the shapes of what comes out.
+
+With --from-2d the observations are not handed over but derived, as from a dataset's raw arrays: the known moving scene is drawn into
+per-frame depth maps, foreground masks and TAPIR-style 2-D tracks (x, y, occlusion logit, expected-distance logit) in front of a
+textured wall, and deblur4dgs_amd.observations turns those back into observations: `filter_depths` (HIP masked median blur),
+`tracks_3d` (HIP lifting) and `bkgd_points` (HIP points, normals and ordered compaction)."""
 import argparse
 import os
 import sys
@@ -12,6 +17,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from deblur4dgs_amd import observations as O  # noqa: E402
 from deblur4dgs_amd import scene_init as S  # noqa: E402
 from deblur4dgs_amd.scene_model import SceneModel  # noqa: E402
 
@@ -21,6 +27,7 @@ ap.add_argument("--frames", type=int, default=12)
 ap.add_argument("--bases", type=int, default=6)
 ap.add_argument("--points", type=int, default=8000)
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--from-2d", action="store_true", help="derive the observations from synthetic depths, masks and 2-D tracks")
 a = ap.parse_args()
 if not torch.cuda.is_available():
     raise SystemExit("init_scene.py needs an MI355X (ROCm) device")
@@ -39,6 +46,38 @@ tracks = S.TrackObservations(xyz, visibles, ~visibles, torch.rand(G, T, generato
 floor = torch.rand(a.points, 3, generator=gen) * torch.tensor([6.0, 6.0, 0.05]) - torch.tensor([3.0, 3.0, 1.5])
 points = S.StaticObservations(floor, torch.tensor([[0.0, 0.0, 1.0]]).expand(a.points, 3).contiguous(),
                               torch.rand(a.points, 3, generator=gen) * 0.9 + 0.05).to(dev)
+W, H = 96, 64
+Ks = torch.tensor([[80.0, 0.0, W / 2], [0.0, 80.0, H / 2], [0.0, 0.0, 1.0]]).repeat(T, 1, 1)
+w2cs = torch.eye(4).repeat(T, 1, 1)
+w2cs[:, 2, 3] = 5.0
+
+if a.from_2d:
+    # the scene as a dataset would hold it: every track is a 5 x 5 pixel patch at its own depth in front of a wall at camera z = 8
+    cam = xyz @ w2cs[0, :3, :3].T + w2cs[0, :3, 3]                                # [G,T,3] (the camera does not move)
+    uv = cam[..., :2] / cam[..., 2:] * Ks[0, 0, 0] + Ks[0, :2, 2]                   # [G,T,2] pixel coordinates
+    depths, masks = torch.full((T, H, W), 8.0), torch.zeros(T, H, W)
+    centre = uv.round().long()
+    for g in torch.argsort(cam[:, cano_t, 2], descending=True).tolist():           # far to near: the nearest patch stays on top
+        for t in range(T):
+            cx, cy = centre[g, t].tolist()
+            if 2 <= cx < W - 2 and 2 <= cy < H - 2:
+                depths[t, cy - 2:cy + 3, cx - 2:cx + 3] = cam[g, t, 2]
+                masks[t, cy - 2:cy + 3, cx - 2:cx + 3] = 1.0
+    depths += 0.3 * (torch.rand(T, H, W, generator=gen) < 0.02) * masks              # speckle that the median blur removes
+    imgs = torch.rand(T, H, W, 3, generator=gen) * 0.9 + 0.05
+    logit = torch.where(visibles, -4.0, 4.0)                                         # occlusion logit: visible <=> negative
+    tracks_2d = torch.cat([uv, logit[..., None], torch.full((G, T, 1), -4.0)], -1)  # [G,T,4]
+    queries = [0, cano_t, T - 1]                                                    # each third of the tracks was queried in one frame
+    raw = [tracks_2d[i::3].to(dev) for i in range(3)]
+    valid = torch.ones(T, H, W)
+    d = O.filter_depths(depths.to(dev), masks.to(dev), valid.to(dev))
+    fg_masks = ((masks.to(dev) * (d > 0)) > 0.5).float()
+    tracks = O.tracks_3d(raw, queries, imgs.to(dev), d, fg_masks, Ks.to(dev), w2cs.to(dev))
+    points = O.bkgd_points(imgs.to(dev), d, masks.to(dev), valid.to(dev), Ks.to(dev), w2cs.to(dev), a.points,
+                           generator=torch.Generator().manual_seed(a.seed))
+    print(f"from 2-D: {int((d.cpu() != depths).sum())} depths changed by the blur; tracks {tracks.xyz.shape[0]} of {G} kept, "
+          f"{float(tracks.visibles.float().mean()):.2f} visible; background points {points.xyz.shape[0]}")
+    G = tracks.xyz.shape[0]
 
 bases, coefs, tracks = S.init_motion_params_with_procrustes(tracks, K, "6d", cano_t, generator=torch.Generator().manual_seed(a.seed))
 fg = S.init_fg_from_tracks_3d(cano_t, tracks, coefs, generator=torch.Generator().manual_seed(a.seed))
@@ -48,10 +87,6 @@ print(f"tracks kept {tracks.xyz.shape[0]} of {G}; bases rots {tuple(bases.params
 for name, gp in (("fg", fg), ("bg", bg)):
     print(name, {k: tuple(v.shape) for k, v in gp.params.items()}, "scene_scale", float(gp.scene_scale))
 
-W, H = 96, 64
-Ks = torch.tensor([[80.0, 0.0, W / 2], [0.0, 80.0, H / 2], [0.0, 0.0, 1.0]]).repeat(T, 1, 1)
-w2cs = torch.eye(4).repeat(T, 1, 1)
-w2cs[:, 2, 3] = 5.0
 model = SceneModel(Ks, w2cs, fg, bases, bg).to(dev)
 with torch.no_grad():
     out = model.render(cano_t, model.w2cs[cano_t:cano_t + 1], model.Ks[cano_t:cano_t + 1], (W, H), return_depth=True)

@@ -883,6 +883,61 @@ D4GS_EVAL_API int d4gs_pose_step_cpu(const float *w2c /* [host] */, const float 
                                      double eta_min, int32_t t_max, double beta1, double beta2, double eps,
                                      float *lr_out /* [host] */, float *W /* [host] */);
 
+/* Observations (appended; D4GS_VERSION unchanged): what the reference's flow3d/data/utils.py and the get_tracks_3d / get_bkgd_points
+ * bodies of its datasets do to a dataset's raw arrays - aligned depth maps, foreground masks, TAPIR 2-D tracks, Ks, w2cs - before
+ * the scene initialisation takes over.  The block is declared under a macro of its own, like the two before it: D4GS_DATA_API is
+ * the data-preparation block (the binding's DATA_PROTOTYPES); exported, parsed by the same strict rules and bound by the same call.
+ * csrc/observations.hip; DESIGN.md section 26.  Every pointer is DEVICE memory, tensors are contiguous fp32 unless stated, every
+ * launch is on `stream`, nothing is read on the host, and every result is bitwise reproducible from run to run.  D4GS_EINVAL, by
+ * host arithmetic alone and before any HIP call, for a NULL required pointer, a misaligned pointer, a size < 1, a product of sizes
+ * beyond 2^31 - 1 as each entry names it, or an illegal kernel_size / query.
+ *
+ * d4gs_masked_median_blur: masked_median_blur (utils.py:207-250), exactly.  image, mask, out [n_img,H,W] (n_img = B C), kernel_size
+ * k odd in 3..15, n_img H W <= 2^31 - 1.  The window is k x k and zero-padded: a position outside the image has value 0 and mask 0.
+ * An entry is VALID iff its mask value equals 1.0f; every other entry, out-of-image positions included, is invalid.
+ * lo = min(min(image), 0), hi = max(max(image), 0).  Enumerate the invalid entries in (image, h, w, window index ky k + kx) order:
+ * the even-numbered ones count as lo, the odd-numbered ones as hi - so a pixel's own invalid entries alternate, starting with lo
+ * iff an even number of invalid entries precedes the pixel.  out = the LOWER median of the pixel's k k entries, rank (k k - 1) / 2:
+ * with n_lo entries sent to lo, it is lo if rank < n_lo, else the (rank - n_lo)-th smallest valid value if there is one, else hi.
+ * The output is one of the inputs' bit patterns (or lo / hi).  Inputs must be finite; -0.0 orders below +0.0.
+ * per_image != 0: lo, hi and the enumeration restart at every image, so n_img images give what n_img calls with one image give
+ * (the dataset blurs frame by frame).  blend (may be NULL) [n_img,H,W]: out = median * blend + image * (1 - blend), each product and
+ * the sum rounded to fp32 on its own (the dataset's depth * mask + old * (1 - mask), stereo_low_dataset.py:239-241).  out must not be
+ * image.  workspace: d4gs_masked_median_ws_bytes(n_img, H, W) bytes, 16-byte aligned (0: a size < 1 or past the limit; never 0
+ * for legal sizes).  Tiles of 16 x 16 pixels, staged with their (k - 1) / 2 halo in LDS.
+ *
+ * d4gs_lift_tracks: get_tracks_3d_for_query_frame (utils.py:69-152) before its filter.  tracks_2d [N,T,4] = x, y, occlusion logit,
+ * expected-distance logit; depths, masks [T,H,W]; query_img [H,W,3]; inv_Ks [T,3,3]; c2ws [T,4,4]; 0 <= query < T.  Per sample:
+ * vis = 1 - sigmoid(occ), conf = 1 - sigmoid(dist), visible = vis conf > 0.5, invisible = (1 - vis) conf > 0.5, confidence = conf
+ * where either holds, else 0; depth = bilinear sample of depths[t] at (x, y) with the coordinates clamped to the image;
+ * xyz = c2ws[t] (inv_Ks[t] (x, y, 1) depth) with the unclamped x, y.  in_mask = every one of the four bilinear corners of (x, y)
+ * that has a non-zero weight lies inside the image and has mask == 1.0f; the corner floor(x) always weighs, floor(x) + 1 weighs iff
+ * x is no integer, the same in y.  (The reference's grid_sample(...) == 1 also rejects ~1.5 % of samples whose corners are all 1,
+ * where the rounded weights do not sum to 1: rounding, not intent.)  visibles, invisibles [N,T] uint8 and confidences [N,T] are
+ * multiplied by in_mask [N,T] uint8.  colors [N,3]: query_img sampled like the depth at the track's position in frame `query`.
+ * visible_count [N] int32 = the row sums of visibles; hist [T + 1] int32 = how many tracks have each count (zeroed by the call;
+ * integer atomics).  N T 4, T H W and H W 3 <= 2^31 - 1.  Non-finite coordinates: not in the mask, depth from a clamped position.
+ *
+ * d4gs_bkgd_points: the per-pixel part of get_bkgd_points (stereo_low_dataset.py:512-547) and normal_from_depth_image (utils.py:
+ * 337-360) for T frames.  depths, masks, valid_masks [T,H,W]; inv_Ks [T,3,3]; c2ws [T,4,4].  points [T,H,W,3] = c2ws[t] (inv_Ks[t]
+ * (x, y, 1) depth).  normals [T,H,W,3] = n / max(|n|, 1e-12), n = cross(right - left, top - bottom) of the four neighbours' world
+ * points (top = y - 1); exact zeros on the one-pixel border.  keep [T,H,W] uint8 = ((1 - mask) valid_mask (depth > 0)) != 0.
+ * index [T,H,W] int32 and counts [T] int32 (both or neither): index[t, 0 .. counts[t]) = the offsets y W + x of frame t's kept pixels
+ * in ascending order - the order boolean indexing gives, so a caller's selections mean what they mean in the reference; the rest of
+ * index[t] is not written.  One block per frame walks it with a ballot scan (the single-block plan of d4gs_control_plan, T frames
+ * side by side); counts is the one thing a caller reads on the host.  T H W 3 <= 2^31 - 1. */
+#define D4GS_DATA_API __attribute__((visibility("default")))
+D4GS_DATA_API int64_t d4gs_masked_median_ws_bytes(int64_t n_img, int64_t H, int64_t W); /* 0: illegal sizes */
+D4GS_DATA_API int d4gs_masked_median_blur(const float *image, const float *mask, const float *blend, int32_t n_img, int32_t H, int32_t W,
+                                          int32_t kernel_size, int32_t per_image, float *out, void *workspace, void *stream);
+D4GS_DATA_API int d4gs_lift_tracks(const float *tracks_2d, const float *depths, const float *masks, const float *query_img,
+                                   const float *inv_Ks, const float *c2ws, int32_t N, int32_t T, int32_t H, int32_t W, int32_t query,
+                                   float *xyz, uint8_t *visibles, uint8_t *invisibles, float *confidences, uint8_t *in_mask,
+                                   float *colors, int32_t *visible_count, int32_t *hist, void *stream);
+D4GS_DATA_API int d4gs_bkgd_points(const float *depths, const float *masks, const float *valid_masks, const float *inv_Ks,
+                                   const float *c2ws, int32_t T, int32_t H, int32_t W, float *points, float *normals, uint8_t *keep,
+                                   int32_t *index, int32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
