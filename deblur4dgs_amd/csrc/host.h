@@ -123,6 +123,13 @@ int d4gs_move_model_bwd_impl(const float *jac, const float *dtimes, const float 
                              int32_t index, int32_t n_time_params, float *v_delta, float *const *v_w, float *const *v_b,
                              float *v_time_params, float *v_enc, hipStream_t stream);
 
+// ---- quantile selection over a caller's own values (trimmed.hip; track_fit.hip calls it) ----------------------------------
+// values: the first n words of `scratch` (d4gs_trimmed_scratch_words(n, 1) words, 8-byte aligned), written on `stream` before this
+// call.  masked_l1_loss(normalize=True): out[0] = sum_{v < thr} v w / (sum_{v < thr} w + 1e-8), out[1] = thr, out[2] = 1 / denominator;
+// quantile >= 1 keeps every element.  No second radix select anywhere: this is trim_reduce.
+bool d4gs_bad_quantile(float q);  // NaN, <= 0, inf
+int d4gs_trim_masked_impl(void *scratch, const float *weights, int64_t n, float quantile, float *out, hipStream_t stream);
+
 // ---- photometric loss (photometric.hip), spherical harmonics (sh.hip) -----------------------------------------------------
 int d4gs_photometric_fwd_impl(const float *pred, const float *gt, const float *mask, int32_t B, int32_t H, int32_t W, float w_l1,
                               float w_ssim, float *maps, float *partials, float *loss, hipStream_t stream);

@@ -462,6 +462,17 @@ int track_check(const char *who, const void *const *ptrs, int n_ptrs, int64_t n_
 
 }  // namespace
 
+// host.h: the masked, normalized form over values that a caller's own kernel has left in the first n words of `scratch`
+// (track_fit.hip's per-frame 2-D errors) - the control words are set here, the rest is trim_reduce
+bool d4gs_bad_quantile(float q) { return bad_quantile(q); }
+int d4gs_trim_masked_impl(void *scratch, const float *weights, int64_t n, float quantile, float *out, hipStream_t stream) {
+  uint32_t *ctrl = (uint32_t *)scratch + trim_ctrl_offset(n, 1);
+  double *partials = (double *)((uint32_t *)scratch + trim_partials_offset(n, 1));
+  D4GS_LAUNCH("k_trim_init", k_trim_init, dim3(1), dim3(TB), 0, stream, ctrl, 1, (uint32_t)n);
+  if (int rc = d4gs_check_launch("k_trim_init")) return rc;
+  return trim_reduce((float *)scratch, weights, n, 1, quantile >= 1.f ? 0 : 1, 0, quantile, ctrl, partials, out, stream);
+}
+
 extern "C" {
 
 int64_t d4gs_trimmed_scratch_words(int64_t n_max, int32_t terms) {

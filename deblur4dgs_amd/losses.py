@@ -20,6 +20,10 @@ and projects them, the selection runs for the 2-D term only, one kernel scatters
 bases, the smoothness of every foreground track, the acceleration along the viewing ray and the variance of the raw scales, in one
 call forward and one backward on the pose kernels (`csrc/motion_regs.hip`).
 
+`track_fit_losses` is the loss of the warm-up that runs before training (flow3d/init_utils.py:273-402, `run_initial_optim`): six terms
+from one deformation per (Gaussian, frame), forward and backward on the pose kernels (`csrc/track_fit.hip`, DESIGN.md section 27);
+`scene_init.run_initial_optim` is the loop around it.
+
 `dilate_mask`, `sharp_keep_loss` and `coverage_loss` are the passes of those two functions that the reference writes as plain torch
 ops: `nn.MaxPool2d(9, 1, 4)` on the foreground mask (trainer.py:120,388,575,901), the area-reduced masked L1 between the sharp
 sub-sample and the blurry target (:736-760) and `F.mse_loss` on the accumulated alpha (:621-631) (`csrc/image_terms.hip`, DESIGN.md
@@ -388,6 +392,77 @@ def scene_motion_regularizers(model, ts, w2cs, **kw):
         loss += w_smooth_bases * sb + w_smooth_tracks * st + w_z_accel * za + w_scale_var * sv"""
     fg, mb = model.fg.params, model.motion_bases.params
     return motion_regularizers(fg["means"], fg["motion_coefs"], mb["rots"], mb["transls"], fg["scales"], ts, w2cs, **kw)
+
+
+class _TrackFitFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, motion_coefs, rots, transls, targets, quantile):
+        G, K, T = means.shape[0], rots.shape[0], rots.shape[1]
+        leaves = tuple(f32c(x) for x in (means, motion_coefs, rots, transls))
+        lib = L.lib()
+        nbytes = lib.d4gs_track_fit_workspace_bytes(G, K, T)
+        if nbytes == 0:
+            raise RuntimeError(f"track_fit_losses: unsupported size G={G} K={K} T={T} (K <= 32, 3 <= T <= 65535, 9 G T <= 2^31 - 1)")
+        ws = torch.empty(nbytes, device=means.device, dtype=torch.uint8)
+        out = torch.empty(8, device=means.device, dtype=torch.float32)
+        L.check(lib.d4gs_track_fit_fwd(*[vp(x) for x in leaves], G, K, T, quantile, None, vp(targets.buf), targets.nbytes, vp(ws), nbytes,
+                                       vp(out), None, None, 0, stream_of(means)), "d4gs_track_fit_fwd")
+        ctx.save_for_backward(*leaves, ws)  # version-checked: a leaf changed in place before the backward raises
+        ctx.targets = targets
+        ctx.args = (G, K, T, quantile, nbytes, tuple(x.dtype for x in (means, motion_coefs, rots, transls)))
+        return out[1:7].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v_terms):
+        means, coefs, rots, transls, ws = ctx.saved_tensors
+        G, K, T, quantile, nbytes, dtypes = ctx.args
+        v = v_terms.detach().float().contiguous()
+        g = dict(v_means=torch.empty_like(means), v_motion_coefs=torch.empty_like(coefs), v_rots=torch.empty_like(rots),
+                 v_transls=torch.empty_like(transls))
+        L.check(L.lib().d4gs_track_fit_bwd(vp(means), vp(coefs), vp(rots), vp(transls), G, K, T, quantile, vp(ctx.targets.buf),
+                                           ctx.targets.nbytes, vp(ws), nbytes, vp(v), C.byref(L.fill(L.LeafGrads(), **g)), stream_of(means)),
+                "d4gs_track_fit_bwd")
+        outs = (g["v_means"], g["v_motion_coefs"], g["v_rots"], g["v_transls"])
+        return tuple(o.to(dt) if need else None for o, dt, need in zip(outs, dtypes, ctx.needs_input_grad[:4])) + (None, None)
+
+
+def track_fit_losses(means, motion_coefs, rots, transls, targets, quantile: float = 0.95):
+    """-> [6]: track_3d, track_2d, coef_sparse, smooth_bases, smooth_tracks, z_accel of the reference's warm-up loop body
+    (flow3d/init_utils.py:320-388), unweighted; the loop weighs them 1, 0.5, 0.01, w(i), 0.5 w(i), 0.1.
+
+    means [G,3], raw motion_coefs [G,K], rots [K,T,6], transls [K,T,3]; `targets` = `scene_init.track_fit_targets(tracks_3d, Ks, w2cs)`,
+    the prepared observations of the same G tracks and T frames.  With p[g,tau] the deformed mean at the integer frame tau:
+      track_3d      = masked_l1_loss(p, xyz, visibles * confidences)
+      track_2d      = masked_l1_loss(proj(p), proj(xyz), invisibles * confidences, quantile=quantile) / Ks[0,0,0]
+      coef_sparse   = 1 - (softmax(motion_coefs) ** 2).sum(-1).mean()
+      smooth_bases  = compute_se3_smoothness_loss(rots, transls)
+      smooth_tracks = compute_accel_loss(p)                  (the mean over G (T - 2) norms: not `motion_regularizers`' 0.5 factor)
+      z_accel       = compute_z_acc_loss(p at clamp(b, 1, T-2) + {-1, 0, 1}, w2cs), b = 0 .. T-1
+    Every p is computed once (a composition of `motion_regularizers` with ts = arange(T) deforms each Gaussian at 3 T times).  Gradients
+    flow to the four leaves; the observations are data.  The gradient of |x| at 0 and of a norm at exactly zero is zero; none flows
+    through the quantile.  Nothing is read on the host, so the call can sit inside a captured HIP graph; forward and backward are
+    bitwise reproducible.  T < 3 is refused (the reference's mean over nothing is NaN)."""
+    q = _check_quantile(quantile, upper_open=True)
+    for name, x, lead, tail in (("means", means, 1, (3,)), ("motion_coefs", motion_coefs, 2, ()), ("rots", rots, 2, (6,)),
+                                ("transls", transls, 2, (3,))):
+        if not torch.is_tensor(x) or x.dim() != lead + len(tail) or tuple(x.shape[lead:]) != tail:
+            raise ValueError(f"{name} {tuple(x.shape) if torch.is_tensor(x) else type(x)}: expected "
+                             "means [G,3], motion_coefs [G,K], rots [K,T,6], transls [K,T,3]")
+    G, K, T = means.shape[0], rots.shape[0], rots.shape[1]
+    if G == 0 or K == 0:
+        raise ValueError(f"no foreground Gaussians or no motion bases (G = {G}, K = {K})")
+    if motion_coefs.shape != (G, K) or transls.shape[:2] != (K, T):
+        raise ValueError(f"mismatched sizes: means {tuple(means.shape)}, motion_coefs {tuple(motion_coefs.shape)}, rots {tuple(rots.shape)}, "
+                         f"transls {tuple(transls.shape)} (G Gaussians, K bases, T frames)")
+    if T < 3:
+        raise ValueError(f"T = {T} frames: the fit needs an interior frame (T >= 3)")
+    if (getattr(targets, "G", None), getattr(targets, "T", None)) != (G, T):
+        raise ValueError(f"targets of G = {getattr(targets, 'G', None)}, T = {getattr(targets, 'T', None)} for leaves of G = {G}, T = {T} "
+                         "(scene_init.track_fit_targets of the same tracks and frames)")
+    for x in (means, motion_coefs, rots, transls):
+        need_gpu(x, _WHO)
+    return _TrackFitFn.apply(means, motion_coefs, rots, transls, targets, q)
 
 
 def _mask_bhw(masks, name="masks"):

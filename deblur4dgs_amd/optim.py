@@ -171,6 +171,14 @@ class AdamGroup:
         if not capturing:
             self._upload(items)
 
+    def device_table(self):
+        """The table in device memory after `sync()`: a uint8 tensor holding one `D4gsAdamRec` per handle that has state, in the
+        handles' order (None while no handle has any).  For a kernel that writes a field of it on the stream - a schedule that moves
+        `lr` between graph replays (`scene_init.track_fit_schedule`).  The next upload replaces what such a kernel wrote by the
+        handles' own values; uploads happen when a gradient tensor or a host-side hyper-parameter changed."""
+        self.sync()
+        return getattr(self, "_table", None)
+
     def _rebuild(self, items, structure):
         self._structure, self._index = structure, {id(it[0]): i for i, it in enumerate(items)}
         self.generation += 1

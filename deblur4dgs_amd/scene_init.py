@@ -22,10 +22,16 @@ What differs from the reference, on purpose:
     for two log lines;
   * `MotionBases` of this package holds 6-D rotations only: `rot_type="quat"` is served by `solve_motion_bases`, which returns the
     tensors, and refused by `init_motion_params_with_procrustes`.
-Not here: `run_initial_optim` (every term of it is in `losses.py`), the HDBSCAN mode, the viser visualisations, the dataset readers.
+`run_initial_optim`, the warm-up that fits the bases, the coefficients and the means to the tracks before training, is provided:
+`track_fit_targets` prepares the observations once, `losses.track_fit_losses` is its loss (csrc/track_fit.hip), and the loop keeps
+its schedule, its Adam state and its iteration count on the device, so one iteration is captured in a HIP graph and replayed
+(DESIGN.md section 27).
+Not here: the depth-range term of that warm-up (no caller of the reference sets it), the HDBSCAN mode, the viser visualisations, the
+dataset readers.
 """
 from __future__ import annotations
 
+import ctypes
 import dataclasses
 import math
 
@@ -37,7 +43,8 @@ from ._lib import check, need_gpu, stream_of, vp
 
 __all__ = ["TrackObservations", "StaticObservations", "track_features", "interp_tracks", "knn", "kmeans", "kmeans_step",
            "procrustes_moments", "get_weights_for_procrustes", "sample_initial_bases_centers", "solve_motion_bases",
-           "init_motion_params_with_procrustes", "init_fg_from_tracks_3d", "init_bg", "KNN_TILE", "KNN_SPLIT_MIN", "KNN_MAX_K",
+           "init_motion_params_with_procrustes", "init_fg_from_tracks_3d", "init_bg", "TrackFitTargets", "track_fit_targets",
+           "track_fit_schedule", "run_initial_optim", "FIT_LR0", "KNN_TILE", "KNN_SPLIT_MIN", "KNN_MAX_K",
            "KMEANS_MAX_K"]
 
 KNN_TILE, KNN_SPLIT_MIN, KNN_MAX_K, KMEANS_MAX_K = L.KNN_TILE, L.KNN_SPLIT_MIN, L.KNN_MAX_K, L.KMEANS_MAX_K
@@ -408,3 +415,148 @@ def init_bg(points: StaticObservations):
     quats = torch.cat([torch.cos(theta / 2), unit * torch.sin(theta / 2)], -1)
     return GaussianParams(xyz, quats, torch.log(_knn_scales(xyz).repeat(1, 3)), torch.logit(points.colors.float()),
                           torch.logit(torch.full((N,), 0.7, device=xyz.device)), scene_center=center, scene_scale=scene_scale)
+
+
+# ---- the warm-up (init_utils.py:273-402) ----------------------------------------------------------------------------------------
+FIT_LR0 = (1e-2, 3e-2, 1e-2, 1e-3)  # rots, transls, motion_coefs, means: the reference's four param groups, in its order
+
+
+class TrackFitTargets:
+    """What `d4gs_track_fit_prepare` leaves of the observations: `buf` (device bytes: the time-major planes of xyz, its projection and
+    the two weight planes, the sum of the 3-D weights, the camera tables with their centres, 1 / fx), for G tracks and T frames."""
+
+    def __init__(self, buf, G, T):
+        self.buf, self.nbytes, self.G, self.T = buf, buf.numel(), G, T
+
+
+def track_fit_targets(tracks_3d: TrackObservations, Ks, w2cs) -> TrackFitTargets:
+    """tracks_3d (xyz [G,T,3], visibles, invisibles, confidences [G,T]), Ks [T,3,3], w2cs [T,4,4] -> the prepared observations
+    `losses.track_fit_losses` reads.  Once per run: two launches, nothing read on the host."""
+    xyz = tracks_3d.xyz
+    need_gpu(xyz, WHO)
+    if xyz.dim() != 3 or xyz.shape[-1] != 3 or not tracks_3d.check_sizes():
+        raise ValueError(f"tracks_3d: xyz must be [G,T,3] with visibles, invisibles, confidences [G,T]; got xyz {tuple(xyz.shape)}")
+    G, T, _ = xyz.shape
+    if tuple(Ks.shape) != (T, 3, 3) or tuple(w2cs.shape) != (T, 4, 4):
+        raise ValueError(f"Ks {tuple(Ks.shape)} and w2cs {tuple(w2cs.shape)} must be [{T},3,3] and [{T},4,4]: one camera per frame")
+    if T < 3:
+        raise ValueError(f"T = {T} frames: the fit needs an interior frame (T >= 3)")
+    dev = xyz.device
+    nbytes = L.lib().d4gs_track_fit_targets_bytes(G, T)
+    if nbytes == 0:
+        raise RuntimeError(f"track_fit_targets: unsupported size G={G} T={T} (G >= 1, 3 <= T <= 65535, 9 G T <= 2^31 - 1)")
+    x, c = _f32(xyz), _f32(tracks_3d.confidences).to(dev)
+    vis = (tracks_3d.visibles != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    inv = (tracks_3d.invisibles != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    K3, W = _f32(Ks).to(dev), _f32(w2cs).to(dev)
+    buf = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    check(L.lib().d4gs_track_fit_prepare(vp(x), vp(vis), vp(inv), vp(c), vp(K3), vp(W), G, T, vp(buf), nbytes, stream_of(x)),
+          "d4gs_track_fit_prepare")
+    return TrackFitTargets(buf, G, T)
+
+
+def track_fit_schedule(group, it, num_iters: int, weights, lrs=None, lr0=FIT_LR0):
+    """d4gs_track_fit_schedule at the head of an iteration: reads the device counter `it` [1] int32, writes this iteration's six term
+    weights into `weights` [6], lr0_r 0.1^(it / num_iters) into the `lr` of the four records of `group`'s DEVICE table (handles in the
+    order rots, transls, motion_coefs, means) and into `lrs[it]` ([num_iters,4], optional), and stores it + 1.  The handles' own
+    `param_groups[...]["lr"]` are not touched: whatever makes `AdamGroup.sync()` upload its table again (a new gradient tensor, a
+    host-side lr change) replaces the scheduled rates by the handles' - keep the `.grad` tensors in place between iterations."""
+    if len(group.handles) != 4:
+        raise ValueError("track_fit_schedule: an AdamGroup of four handles (rots, transls, motion_coefs, means)")
+    table = group.device_table()  # (sync(): outside a capture it creates the state and uploads the table the kernel writes into)
+    if table is None or table.numel() != 4 * ctypes.sizeof(L.AdamRec):
+        raise RuntimeError("track_fit_schedule: every handle needs a gradient tensor (AdamGroup builds its table from them)")
+    check(L.lib().d4gs_track_fit_schedule(vp(it), int(num_iters), vp(table), *[float(x) for x in lr0], vp(weights), vp(lrs),
+                                          stream_of(weights)), "d4gs_track_fit_schedule")
+
+
+class _WarmupLoop:
+    """The state of `run_initial_optim` - parameters with their gradient buffers, the AdamGroup, the prepared observations, the
+    workspace, the device counter, the weights and the two histories - and `one()`, the launches of one iteration."""
+
+    def __init__(self, fg, bases, tracks_3d, Ks, w2cs, num_iters: int, quantile: float = 0.95):
+        from .optim import AdamGroup
+
+        self.params = [bases.params["rots"], bases.params["transls"], fg.params["motion_coefs"], fg.params["means"]]
+        rots, transls, coefs, means = self.params
+        for p in self.params:
+            need_gpu(p, WHO, " (no CPU fallback)")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("run_initial_optim updates contiguous float32 parameters in place")
+        self.G, self.K, self.T = G, K, T = means.shape[0], rots.shape[0], rots.shape[1]
+        self.targets = track_fit_targets(tracks_3d, Ks, w2cs)
+        if (self.targets.G, self.targets.T) != (G, T) or tuple(coefs.shape) != (G, K) or tuple(transls.shape) != (K, T, 3):
+            raise ValueError(f"tracks of G = {self.targets.G}, T = {self.targets.T} for means {tuple(means.shape)}, motion_coefs "
+                             f"{tuple(coefs.shape)}, rots {tuple(rots.shape)}, transls {tuple(transls.shape)}")
+        self.lib, dev = L.lib(), means.device
+        self.nbytes = self.lib.d4gs_track_fit_workspace_bytes(G, K, T)
+        if self.nbytes == 0:
+            raise RuntimeError(f"run_initial_optim: unsupported size G={G} K={K} T={T} (K <= 32, 9 G T <= 2^31 - 1)")
+        self.num_iters, self.quantile = int(num_iters), float(quantile)
+        self.ws = torch.empty(self.nbytes, device=dev, dtype=torch.uint8)
+        self.out = torch.zeros(8, device=dev, dtype=torch.float32)
+        self.weights = torch.zeros(6, device=dev, dtype=torch.float32)
+        self.it = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.losses = torch.zeros(self.num_iters, 7, device=dev, dtype=torch.float32)
+        self.lrs = torch.zeros(self.num_iters, 4, device=dev, dtype=torch.float32)
+        for p in self.params:
+            p.grad = torch.zeros_like(p)  # the backward writes here, the table points here: the same buffers at every iteration
+        self.group = AdamGroup()
+        self.handles = [self.group.adam(p, lr) for p, lr in zip(self.params, FIT_LR0)]
+        self.grads = L.fill(L.LeafGrads(), v_means=means.grad, v_motion_coefs=coefs.grad, v_rots=rots.grad, v_transls=transls.grad)
+        self.leaf_ptrs = [vp(means), vp(coefs), vp(rots), vp(transls)]
+
+    def one(self):
+        G, K, T, q, t, lib = self.G, self.K, self.T, self.quantile, self.targets, self.lib
+        stream = stream_of(self.ws)
+        track_fit_schedule(self.group, self.it, self.num_iters, self.weights, self.lrs)
+        check(lib.d4gs_track_fit_fwd(*self.leaf_ptrs, G, K, T, q, vp(self.weights), vp(t.buf), t.nbytes, vp(self.ws), self.nbytes,
+                                     vp(self.out), vp(self.it), vp(self.losses), self.num_iters, stream), "d4gs_track_fit_fwd")
+        # the cotangents of the six terms ARE the weights: d total / d term_k
+        check(lib.d4gs_track_fit_bwd(*self.leaf_ptrs, G, K, T, q, vp(t.buf), t.nbytes, vp(self.ws), self.nbytes, vp(self.weights),
+                                     L.C.byref(self.grads), stream), "d4gs_track_fit_bwd")
+        self.group.step()
+
+    def capture(self):
+        """one() in a HIP graph (after one eager one(), which creates the Adam state) -> the graph"""
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=torch.cuda.Stream()):
+            self.one()
+        return g
+
+
+def run_initial_optim(fg, bases, tracks_3d: TrackObservations, Ks, w2cs, num_iters: int = 1000, use_depth_range_loss: bool = False, *,
+                      graph: bool = True) -> dict:
+    """init_utils.py:273-402 with the reference's signature: `num_iters` Adam iterations (torch's defaults; lr 1e-2 rots, 3e-2 transls,
+    1e-2 motion_coefs, 1e-3 means, each decayed by 0.1^(i / num_iters)) on
+        track_3d + 0.5 track_2d + 0.01 coef_sparse + w(i) smooth_bases + 0.5 w(i) smooth_tracks + 0.1 z_accel
+    (`losses.track_fit_losses`; w(i) = 0.01 up to i = 400, then linear to 0.1 at num_iters), updating `fg.params["means" |
+    "motion_coefs"]` and `bases.params["rots" | "transls"]` IN PLACE.
+
+    One iteration = schedule step, forward, backward, `AdamGroup.step()`, with the schedule, Adam's state and the iteration count in
+    device memory.  The first iteration runs eagerly (it creates the Adam state); graph=True then captures one iteration in a HIP graph
+    and replays it num_iters - 1 times - the host does nothing per iteration but launch.  graph=False launches the same kernels
+    eagerly and gives the same bits.  There is no CPU fallback.
+
+    -> dict(losses [num_iters,7]: the weighted total and the six terms of every iteration, lrs [num_iters,4]), device tensors written
+    without a host wait.  The reference returns None (it prints the terms to a progress bar).  The parameters' `.grad` are left
+    holding the last iteration's gradients.  use_depth_range_loss=True raises NotImplementedError: no caller of the reference sets it."""
+    if use_depth_range_loss:
+        raise NotImplementedError("run_initial_optim: the depth-range term is not provided (no caller of the reference sets it)")
+    num_iters = int(num_iters)
+    if num_iters < 1:
+        raise ValueError(f"num_iters={num_iters}: at least one iteration")
+    loop = _WarmupLoop(fg, bases, tracks_3d, Ks, w2cs, num_iters)
+    with torch.no_grad():
+        loop.one()
+        if graph and num_iters > 1:
+            g = loop.capture()
+            for _ in range(num_iters - 1):
+                g.replay()
+        else:
+            for _ in range(num_iters - 1):
+                loop.one()
+    last = 0.1 ** ((num_iters - 1) / num_iters)
+    for h, lr0 in zip(loop.handles, FIT_LR0):
+        h.param_groups[0]["lr"] = lr0 * last  # the rate of the last update (lrs[-1]): what the device table holds
+    return dict(losses=loop.losses, lrs=loop.lrs)

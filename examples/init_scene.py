@@ -1,6 +1,6 @@
 """A scene from nothing but tracks: synthetic 3-D tracks and static points -> deblur4dgs_amd.scene_init -> SceneModel -> one render.
 
-    python examples/init_scene.py [--tracks 4000] [--frames 12] [--bases 6] [--points 8000] [--from-2d]
+    python examples/init_scene.py [--tracks 4000] [--frames 12] [--bases 6] [--points 8000] [--from-2d] [--warmup N]
 
 What a user with a reference-format dataset does before training: `init_motion_params_with_procrustes` clusters the tracks' velocity
 directions (HIP k-means), fits an SE(3) per (basis, frame) pair (HIP moments + one batched SVD on the host), `init_fg_from_tracks_3d`
@@ -9,7 +9,11 @@ and `init_bg` size the Gaussians by their 3 nearest neighbours (HIP kNN).  Print
 With --from-2d the observations are not handed over but derived, as from a dataset's raw arrays: the known moving scene is drawn into
 per-frame depth maps, foreground masks and TAPIR-style 2-D tracks (x, y, occlusion logit, expected-distance logit) in front of a
 textured wall, and deblur4dgs_amd.observations turns those back into observations: `filter_depths` (HIP masked median blur),
-`tracks_3d` (HIP lifting) and `bkgd_points` (HIP points, normals and ordered compaction)."""
+`tracks_3d` (HIP lifting) and `bkgd_points` (HIP points, normals and ordered compaction).
+
+With --warmup N the first scene is then fitted to its tracks for N iterations by `scene_init.run_initial_optim` (the reference runs
+1000): schedule, loss, backward and Adam of one iteration captured in a HIP graph and replayed.  Prints the first and the last row of
+the loss history (the weighted total, then track_3d, track_2d, coef_sparse, smooth_bases, smooth_tracks, z_accel)."""
 import argparse
 import os
 import sys
@@ -27,6 +31,7 @@ ap.add_argument("--frames", type=int, default=12)
 ap.add_argument("--bases", type=int, default=6)
 ap.add_argument("--points", type=int, default=8000)
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--warmup", type=int, default=0, help="iterations of run_initial_optim on the first scene (0: none)")
 ap.add_argument("--from-2d", action="store_true", help="derive the observations from synthetic depths, masks and 2-D tracks")
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -86,6 +91,12 @@ print(f"tracks kept {tracks.xyz.shape[0]} of {G}; bases rots {tuple(bases.params
       f"skipped pairs {sum(len(v) for v in bases.skipped_ts.values())}")
 for name, gp in (("fg", fg), ("bg", bg)):
     print(name, {k: tuple(v.shape) for k, v in gp.params.items()}, "scene_scale", float(gp.scene_scale))
+
+if a.warmup > 0:
+    fg, bases = fg.to(dev), bases.to(dev)
+    hist = S.run_initial_optim(fg, bases, tracks, Ks.to(dev), w2cs.to(dev), num_iters=a.warmup)
+    for label, row in (("first", hist["losses"][0]), ("last", hist["losses"][-1])):
+        print(f"warm-up {label:5s}", " ".join(f"{x:.5f}" for x in row.tolist()))
 
 model = SceneModel(Ks, w2cs, fg, bases, bg).to(dev)
 with torch.no_grad():

@@ -938,6 +938,77 @@ D4GS_DATA_API int d4gs_bkgd_points(const float *depths, const float *masks, cons
                                    const float *c2ws, int32_t T, int32_t H, int32_t W, float *points, float *normals, uint8_t *keep,
                                    int32_t *index, int32_t *counts, void *stream);
 
+/* Track fit (appended; D4GS_VERSION unchanged): the warm-up of flow3d/init_utils.py:273-402 (run_initial_optim) - an Adam fit of the
+ * motion bases, the raw motion coefficients and the canonical means to the 3-D tracks, before training starts.  The block is declared
+ * under a macro of its own, like the three before it: D4GS_FIT_API is the binding's FIT_PROTOTYPES; exported, parsed by the same
+ * strict rules and bound by the same call.  csrc/track_fit.hip; DESIGN.md section 27.  Every pointer is DEVICE memory unless marked,
+ * tensors are contiguous fp32 unless stated, every launch is on `stream`, nothing is read on the host, no atomics on floats, and every
+ * result is bitwise reproducible from run to run and graph replay to graph replay.
+ *
+ * Leaves: means [G,3], raw motion_coefs [G,K], rots [K,T,6], transls [K,T,3].  Data: xyz [G,T,3], visibles / invisibles [G,T] uint8
+ * (non-zero = set), confidences [G,T], Ks [T,3,3] (any 3x3), w2cs [T,4,4] = [A t; 0 0 0 1] (A any invertible 3x3).
+ *   p[g,tau] = the deformation of means_g at the integer frame tau (softmax coefficients, Gram-Schmidt)   tau = 0 .. T-1
+ *   w3 = visibles conf,  w2 = invisibles conf;  proj(x,tau): c = A x + t, v = Ks c, uv = v.xy / max(v.z, 1e-5)
+ *   out[1] track_3d      = sum w3 mean_3 |p - xyz| / (sum w3 + 1e-8)
+ *   out[2] track_2d      = masked_l1_loss(proj(p), proj(xyz), w2, quantile) / Ks[0,0,0]: e = mean_2 |.|, thr = torch.quantile of e over
+ *                          ALL G T elements (linear interpolation; quantile >= 1: every element kept), sum_{e < thr} w2 e / (sum_{e < thr}
+ *                          w2 + 1e-8); the selection is d4gs_masked_l1_fwd's
+ *   out[3] coef_sparse   = 1 - mean_g sum_k softmax(motion_coefs_g)_k^2
+ *   out[4] smooth_bases  = mean_{k, 1 <= tau <= T-2} |2 rots - rots[tau-1] - rots[tau+1]| + 2 (the same on transls)
+ *   out[5] smooth_tracks = mean_{g, 1 <= tau <= T-2} |2 p_tau - p_{tau-1} - p_{tau+1}|      (no factor 0.5: not d4gs_motion_regs')
+ *   out[6] z_accel       = mean_{g,b} ((m1 - m0).d)^2 + mean_{g,b} ((m2 - m1).d)^2, b = 0 .. T-1, m_j = p[g, clamp(b,1,T-2) + j - 1],
+ *                          d = normalize(m1 - centre_b, eps 1e-12), centre_b = -A_b^-1 t_b (cofactor inverse): the centre of frame b,
+ *                          so frames 1 and T-2 enter twice (T = 3: frame 1 three times)
+ *   out[0] = sum_k weights[k] out[1 + k] (weights [6] in device memory, what d4gs_track_fit_schedule left there; NULL: all 1);
+ *   out[7] = thr.  out [8].  losses (may be NULL) [num_iters,7]: out[0..6] also go to row *iter - 1 when that row exists - iter the
+ *   device counter as d4gs_track_fit_schedule has just left it (the iteration's index + 1) - so a loop keeps its history
+ *   without a launch of its own.
+ * The gradient of |x| at 0 and of a norm at exactly 0 is 0; the depth clamp passes the gradient where v.z >= 1e-5; none flows
+ * through thr.
+ *
+ * d4gs_track_fit_prepare, once per run: the time-major planes of xyz, proj(xyz), w3 and w2, sum w3 (double, the fixed order of
+ * csrc/reduce.h), the T camera tables with their centres and 1 / Ks[0,0,0] -> targets, d4gs_track_fit_targets_bytes(G, T) bytes,
+ * 16-byte aligned; K does not enter.  d4gs_track_fit_fwd: ONE deformation per (g, frame) by the pose kernels (time-major, S = T),
+ * then one loss launch - one lane per Gaussian, the frames split over gridDim.y in chunks of 4 with one-frame halos, the basis rows
+ * in extra blocks - the selection, one finish block.  workspace: d4gs_track_fit_workspace_bytes(G, K, T) bytes, 16-byte aligned; the
+ * forward leaves the positions, the errors e and thr there and d4gs_track_fit_bwd reads them.  The backward takes v_out [6], the
+ * cotangents of out[1..6], and OVERWRITES grads->v_means, v_motion_coefs, v_rots, v_transls (the other fields are not read): a
+ * gather over the frames (one writer per address), the pose adjoint, then the bases' and the coefficients' own terms.
+ * Both size functions are host arithmetic alone and return 0 for sizes the entry points refuse.  D4GS_EINVAL with a message, before
+ * any HIP call: a NULL required pointer, G < 1, K outside 1 .. D4GS_MAX_K (32), T < 3 (no interior frame: the reference's mean over
+ * nothing is NaN) or T > 65535, 9 G T, 9 K T or G K beyond 2^31 - 1, targets or workspace too small or not 16-byte aligned, a
+ * quantile that is NaN, <= 0 or infinite, a loss history without the counter or with num_iters < 1.
+ *
+ * d4gs_track_fit_schedule: one one-wave launch at the head of iteration i = *iter (int32, device).  table: FOUR D4gsAdamRec in
+ * device memory in the order rots, transls, motion_coefs, means (the reference's param groups).
+ *   lr_r = lr0_r 0.1^(i / num_iters) in double (ExponentialLR's closed form) -> table[r].lr and, for 0 <= i < num_iters, lrs[i,r]
+ *     (fp32 history [num_iters,4], may be NULL)
+ *   w = 0.01 for i <= 400 or num_iters <= 400, else (0.1 - 0.01) (i - 400) / (num_iters - 400) + 0.01 in double (never divides by
+ *     <= 0, also for a counter that has run past the end)
+ *   weights [6] = 1, 0.5, 0.01, w, 0.5 w, 0.1 rounded to fp32 (track_3d, track_2d, coef_sparse, smooth_bases, smooth_tracks, z_accel)
+ *   *iter = i + 1
+ * A captured launch therefore stays valid while four learning rates and the smoothness weight move; d4gs_adam_step reads the table
+ * as it is.  D4GS_EINVAL for a NULL iter / table / weights, a misaligned pointer, num_iters < 1 or an lr0 that is not finite and > 0.
+ * d4gs_track_fit_schedule_cpu: the same inline function on HOST pointers, one thread, no stream.  Never a fallback. */
+#define D4GS_FIT_API __attribute__((visibility("default")))
+D4GS_FIT_API size_t d4gs_track_fit_targets_bytes(int32_t G, int32_t T);              /* 0: illegal sizes */
+D4GS_FIT_API size_t d4gs_track_fit_workspace_bytes(int32_t G, int32_t K, int32_t T); /* 0: illegal sizes */
+D4GS_FIT_API int d4gs_track_fit_prepare(const float *xyz, const uint8_t *visibles, const uint8_t *invisibles, const float *confidences,
+                                        const float *Ks, const float *w2cs, int32_t G, int32_t T, void *targets, size_t targets_bytes,
+                                        void *stream);
+D4GS_FIT_API int d4gs_track_fit_fwd(const float *means, const float *motion_coefs, const float *rots, const float *transls, int32_t G,
+                                    int32_t K, int32_t T, float quantile, const float *weights, const void *targets, size_t targets_bytes,
+                                    void *workspace, size_t workspace_bytes, float *out, const int32_t *iter, float *losses,
+                                    int32_t num_iters, void *stream);
+D4GS_FIT_API int d4gs_track_fit_bwd(const float *means, const float *motion_coefs, const float *rots, const float *transls, int32_t G,
+                                    int32_t K, int32_t T, float quantile, const void *targets, size_t targets_bytes, void *workspace,
+                                    size_t workspace_bytes, const float *v_out, const D4gsLeafGrads *grads, void *stream);
+D4GS_FIT_API int d4gs_track_fit_schedule(int32_t *iter, int32_t num_iters, D4gsAdamRec *table /* [device] */, double lr0_rots,
+                                         double lr0_transls, double lr0_coefs, double lr0_means, float *weights, float *lrs, void *stream);
+D4GS_FIT_API int d4gs_track_fit_schedule_cpu(int32_t *iter /* [host] */, int32_t num_iters, D4gsAdamRec *table, double lr0_rots,
+                                             double lr0_transls, double lr0_coefs, double lr0_means, float *weights /* [host] */,
+                                             float *lrs /* [host] */);
+
 #ifdef __cplusplus
 }
 #endif
