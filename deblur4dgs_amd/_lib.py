@@ -4,7 +4,8 @@ Appending an entry point, a struct or a constant means editing the header and no
 STRUCT_NAMES).  The type rules and the [host] / [device] marks are in `_ctype`; DESIGN.md section 23 has them as a table.
 Prototypes under D4GS_API are PROTOTYPES / EXPORTS; the scene-initialisation block under D4GS_INIT_API is INIT_PROTOTYPES, the
 evaluation-time block (test-time pose refinement) under D4GS_EVAL_API is EVAL_PROTOTYPES, the data-preparation block (observations
-from raw arrays) under D4GS_DATA_API is DATA_PROTOTYPES, the warm-up block (the track fit) under D4GS_FIT_API is FIT_PROTOTYPES.
+from raw arrays) under D4GS_DATA_API is DATA_PROTOTYPES, the warm-up block (the track fit) under D4GS_FIT_API is FIT_PROTOTYPES, the
+per-step block (batch assembly from a device-resident clip) under D4GS_FEED_API is FEED_PROTOTYPES.
 
 The product path has NO fallback: if the HIP library is missing this module raises at first use, and every
 entry point raises RuntimeError on a non-zero return code with `d4gs_last_error()`.
@@ -53,7 +54,7 @@ def _ctype(base, stars, mark, structs, text):
     raise ValueError(f"d4gs.h: cannot bind the type of `{text}`")
 
 
-def parse(text, init=None, *, eval=None, data=None, fit=None):
+def parse(text, init=None, *, eval=None, data=None, fit=None, feed=None):
     """-> (constants, structs, prototypes) of the header `text`: {name without D4GS_: int}, {Python name: ctypes.Structure},
     {entry point: (restype, argtypes)}.  Strict: whatever is left of the header once every enum, struct and prototype has been
     taken out, and every declaration that does not parse completely, raises ValueError with the offending text.
@@ -61,7 +62,7 @@ def parse(text, init=None, *, eval=None, data=None, fit=None):
     by the same rules, counted in the same way, and land in the dict `init` when one is given; so do those under D4GS_EVAL_API
     (test-time pose refinement) and the dict `eval`, and those under D4GS_DATA_API (observations from raw
     arrays) and the dict `data`, and those under D4GS_FIT_API (the track fit) and the dict
-    `fit`."""
+    `fit`, and those under D4GS_FEED_API (batch assembly) and the dict `feed`."""
     def comment(m):  # an inline comment (code before it on its line) leaves its mark as a token; every other comment is blank
         inline = text[text.rfind("\n", 0, m.start()) + 1:m.start()].strip()
         found = re.search(r"\[(host|device)\]", m.group()) if inline else None
@@ -74,9 +75,10 @@ def parse(text, init=None, *, eval=None, data=None, fit=None):
     n_eval = max(len(re.findall(r"\bD4GS_EVAL_API\b", code)) - 1, 0)
     n_data = max(len(re.findall(r"\bD4GS_DATA_API\b", code)) - 1, 0)
     n_fit = max(len(re.findall(r"\bD4GS_FIT_API\b", code)) - 1, 0)
+    n_feed = max(len(re.findall(r"\bD4GS_FEED_API\b", code)) - 1, 0)
     code = re.sub(r"^[ \t]*#.*$", "", code, flags=re.M)
     structs, by_c_name, prototypes, init, eval = {}, {}, {}, {} if init is None else init, {} if eval is None else eval
-    data, fit = {} if data is None else data, {} if fit is None else fit
+    data, fit, feed = {} if data is None else data, {} if fit is None else fit, {} if feed is None else feed
 
     def enum(m):
         for item in filter(None, (x.strip() for x in m.group(1).split(","))):
@@ -123,7 +125,9 @@ def parse(text, init=None, *, eval=None, data=None, fit=None):
     code = re.sub(r"\bD4GS_EVAL_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, eval), code)
     code = re.sub(r"\bD4GS_DATA_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, data), code)
     code = re.sub(r"\bD4GS_FIT_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, fit), code)
-    for block, table, n in (("INIT", init, n_init), ("EVAL", eval, n_eval), ("DATA", data, n_data), ("FIT", fit, n_fit)):
+    code = re.sub(r"\bD4GS_FEED_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, feed), code)
+    for block, table, n in (("INIT", init, n_init), ("EVAL", eval, n_eval), ("DATA", data, n_data), ("FIT", fit, n_fit),
+                            ("FEED", feed, n_feed)):
         if len(table) != n:
             raise ValueError(f"d4gs.h: {len(table)} of {n} D4GS_{block}_API prototypes parsed; not understood: `{' '.join(code.split())}`")
     if code.split() != ["extern", '"C"', "{", "}"] or len(prototypes) != n_api or len(structs) != n_structs:
@@ -136,8 +140,10 @@ INIT_PROTOTYPES = {}  # the D4GS_INIT_API block: scene_init.py's entry points, b
 EVAL_PROTOTYPES = {}  # the D4GS_EVAL_API block: pose_refine.py's
 DATA_PROTOTYPES = {}  # the D4GS_DATA_API block: observations.py's
 FIT_PROTOTYPES = {}   # the D4GS_FIT_API block: the track fit of losses.py / scene_init.py
+FEED_PROTOTYPES = {}  # the D4GS_FEED_API block: feed.py's
 with open(HEADER) as _f:
-    CONSTANTS, STRUCTS, PROTOTYPES = parse(_f.read(), INIT_PROTOTYPES, eval=EVAL_PROTOTYPES, data=DATA_PROTOTYPES, fit=FIT_PROTOTYPES)
+    CONSTANTS, STRUCTS, PROTOTYPES = parse(_f.read(), INIT_PROTOTYPES, eval=EVAL_PROTOTYPES, data=DATA_PROTOTYPES, fit=FIT_PROTOTYPES,
+                                           feed=FEED_PROTOTYPES)
 # the package's names: VERSION, TILE, GEOM_STRIDE, ADAM_CHUNK, RAW_PARAMS ... ANTIALIASED, DEPTH_*, ROWS_*; Dims ... AdamRec
 globals().update(CONSTANTS)
 globals().update(STRUCTS)
@@ -153,7 +159,7 @@ _lib = None
 
 def bind(cdll: C.CDLL) -> C.CDLL:
     """Give every entry point of the header its restype and argtypes on a loaded library."""
-    later = {**INIT_PROTOTYPES, **EVAL_PROTOTYPES, **DATA_PROTOTYPES, **FIT_PROTOTYPES}
+    later = {**INIT_PROTOTYPES, **EVAL_PROTOTYPES, **DATA_PROTOTYPES, **FIT_PROTOTYPES, **FEED_PROTOTYPES}
     for name, (restype, argtypes) in {**PROTOTYPES, **later}.items():
         if (name in APPENDED or name in later) and os.environ.get("D4GS_LIB_PATH") and not hasattr(cdll, name):
             continue

@@ -21,7 +21,9 @@
 // bin by an integer atomic, the colour).  Background points: k_bkgd, one lane per pixel, and k_bkgd_compact, one block per frame.
 #include <cmath>
 
+#include "args.h"
 #include "common.h"
+#include "sampling.h"
 
 namespace {
 
@@ -220,20 +222,6 @@ __device__ __forceinline__ void unproject(const Cam &c, float x, float y, float 
   for (int i = 0; i < 3; i++) w[i] = c.c2w[4 * i] * cx + c.c2w[4 * i + 1] * cy + c.c2w[4 * i + 2] * cz + c.c2w[4 * i + 3];
 }
 
-// bilinear, coordinates clamped to the image (grid_sample's align_corners=True, padding_mode="border"); C interleaved channels
-template <int C>
-__device__ __forceinline__ void bilinear_border(const float *__restrict__ im, int H, int W, float x, float y, float (&o)[C]) {
-  x = fminf(fmaxf(x, 0.f), (float)(W - 1));  // (a NaN becomes 0)
-  y = fminf(fmaxf(y, 0.f), (float)(H - 1));
-  const float fx0 = floorf(x), fy0 = floorf(y), ax = x - fx0, ay = y - fy0;
-  const int ix0 = (int)fx0, iy0 = (int)fy0, ix1 = min(ix0 + 1, W - 1), iy1 = min(iy0 + 1, H - 1);  // (weight 0 where clamped)
-  const float w00 = (1.f - ax) * (1.f - ay), w01 = ax * (1.f - ay), w10 = (1.f - ax) * ay, w11 = ax * ay;
-#pragma unroll
-  for (int c = 0; c < C; c++)
-    o[c] = w00 * im[((size_t)iy0 * W + ix0) * C + c] + w01 * im[((size_t)iy0 * W + ix1) * C + c] + w10 * im[((size_t)iy1 * W + ix0) * C + c] +
-           w11 * im[((size_t)iy1 * W + ix1) * C + c];
-}
-
 // every bilinear corner of (x, y) with a non-zero weight lies in the image and has mask == 1.  Stated in pixel coordinates: the
 // corner floor(x) always weighs, floor(x) + 1 weighs iff x is no integer (x - floor(x) is exact), and the same in y.
 __device__ __forceinline__ bool corners_in_mask(const float *__restrict__ m, int H, int W, float x, float y) {
@@ -348,28 +336,6 @@ __global__ void __launch_bounds__(BK_NT) k_bkgd_compact(const uint8_t *__restric
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-struct Ptr {
-  const void *p;
-  const char *name;
-  unsigned align;
-  bool required;
-};
-
-template <int N>
-bool pointers_ok(const char *who, const Ptr (&ptrs)[N]) {
-  for (const auto &q : ptrs) {
-    if (!q.p && q.required) {
-      d4gs_set_error("%s: %s is NULL", who, q.name);
-      return false;
-    }
-    if ((uintptr_t)q.p % q.align) {
-      d4gs_set_error("%s: %s = %p is misaligned (%u-byte alignment needed)", who, q.name, q.p, q.align);
-      return false;
-    }
-  }
-  return true;
-}
-
 inline int64_t up16(int64_t n) { return (n + 15) & ~(int64_t)15; }
 
 struct MedianPlan {

@@ -313,6 +313,35 @@ def track_losses(tracks_3d, query_tracks_2d, target_Ks, target_tracks_2d, target
                                 f32c(torch.cat([d.reshape(-1) for d in depths])), f32c(torch.cat(Ks).reshape(-1, 9)), q)
 
 
+_TABLE_DTYPES = (("pix", torch.int32), ("rows", torch.int32), ("vis", torch.uint8), ("weights", torch.float32), ("tgt_2d", torch.float32),
+                 ("tgt_depth", torch.float32), ("Ks", torch.float32))
+
+
+def track_losses_from_tables(tracks_3d, tables, quantile: float = 0.98):
+    """`track_losses` for a caller that already holds the element tables - `feed.DeviceClip.batch(...)["track_tables"]` - so that no
+    torch op shapes them per step.  tracks_3d [1,H,W,N,3]; tables: a dict of contiguous device tensors over n elements (n, p), n = N P:
+    pix int32 [n] (the query's pixel y W + x, -1: none), rows int32 [n] (the target n), vis uint8 [n], weights fp32 [n] (already
+    summed over the trailing axis), tgt_2d fp32 [n,2], tgt_depth fp32 [n], Ks fp32 [N,9].  An element with vis = 0 or pix = -1 (a
+    padding row, a query outside the image) takes no part.  Same values, gradient and deviations as `track_losses`."""
+    q = _check_quantile(quantile, upper_open=True)
+    if not torch.is_tensor(tracks_3d) or tracks_3d.dim() != 5 or tracks_3d.shape[-1] != 3 or tracks_3d.shape[0] != 1:
+        raise ValueError("tracks_3d must be a [1,H,W,N,3] tensor")
+    need_gpu(tracks_3d, _WHO)
+    N = tracks_3d.shape[3]
+    if tracks_3d.numel() == 0:
+        raise ValueError(f"tracks_3d {tuple(tracks_3d.shape)} is empty")
+    n = tables["pix"].numel()
+    for name, dtype in _TABLE_DTYPES:
+        x = tables[name]
+        need_gpu(x, _WHO)
+        want = {"tgt_2d": (n, 2), "Ks": (N, 9)}.get(name, (n,))
+        if x.dtype != dtype or tuple(x.shape) != want or not x.is_contiguous():
+            raise ValueError(f"tables[{name!r}] must be a contiguous {dtype} tensor {want}, got {x.dtype} {tuple(x.shape)}")
+    if n == 0:
+        raise ValueError("no query tracks")
+    return _TrackLossesFn.apply(tracks_3d, *(tables[name] for name, _ in _TABLE_DTYPES), q)
+
+
 class _MotionRegsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, motion_coefs, rots, transls, scales, ts, w2cs, weight_rot, weight_transl):

@@ -1009,6 +1009,57 @@ D4GS_FIT_API int d4gs_track_fit_schedule_cpu(int32_t *iter /* [host] */, int32_t
                                              double lr0_transls, double lr0_coefs, double lr0_means, float *weights /* [host] */,
                                              float *lrs /* [host] */);
 
+/* Feed (appended; D4GS_VERSION unchanged): one training batch per step from a clip that lives in device memory - what
+ * StereoLowDataset.__getitem__ (flow3d/data/stereo_low_dataset.py:574-666), train_collate_fn and the trainer's shaping of the track
+ * supervision (trainer.py:549-565, 646-659) do on the host, written into buffers of fixed address so that a captured step reads new
+ * data on every replay.  The block is declared under a macro of its own, like the four before it: D4GS_FEED_API is the binding's
+ * FEED_PROTOTYPES; exported, parsed by the same strict rules and bound by the same call.  csrc/feed.hip; DESIGN.md section 28.  Every
+ * pointer is DEVICE memory unless marked, tensors are contiguous fp32 unless stated, every launch is on `stream`, nothing is read on the
+ * host, no atomics, and every result is bitwise reproducible.  D4GS_EINVAL with a message that names the argument, by host arithmetic
+ * alone and before any HIP call: a NULL required pointer, a misaligned pointer, a size < 1 or beyond its limit.
+ *
+ * d4gs_feed_draw: one wave.  step = *counter (int64); targets [n] int32 = n DISTINCT frames of [start, end), start + Floyd's sampling
+ * over R = end - start: pick k = 0 .. n-1 is t = (r_k (R - n + k + 1)) >> 32, or R - n + k if an earlier pick equals t, with r_k the
+ * 32-bit word k of a counter-based integer hash (splitmix64's finaliser) of (seed, step); then *counter = step + 1.  Every subset is
+ * equally likely up to the multiply-shift's bias (< 2^-32 R).  1 <= n <= min(R, 64), 0 <= start < end.  It is no stream of numpy's.
+ * d4gs_feed_draw_cpu: the same inline functions on HOST pointers, one thread, no stream: the exact twin.  Never a fallback.
+ *
+ * d4gs_feed_batch: ONE launch.  The clip: imgs [F,H,W,3], depths, masks, valid_masks [F,H,W], Ks [F,3,3], w2cs [F,4,4], time_ids [F]
+ * int64, tracks [n_rows,4] (16-byte aligned; rows x, y, occlusion logit, expected-distance logit), offsets [F + 1] int64: the rows of
+ * query frame q are offsets[q] .. offsets[q+1], P_q = (offsets[q+1] - offsets[q]) / F of them per target frame, target-frame-major
+ * (row offsets[q] + t P_q + p; 64-bit).  The selection is read from device memory: index [1] int32 = q, targets [N] int32 (N <= 64).
+ * P is the row stride of every per-query output: lanes p >= P_q are PADDING (coordinates, depth, image sample, confidence, weight 0,
+ * flags 0, pix -1, query (-1, -1)); n_queries [1] int32 = P_q.  With t = targets[n], tt = time_ids[t] and row = the track row (q, t, p):
+ *   ts [1] int64 = time_ids[q]; w2c [16], K [9] of frame q; img [H,W,3], valid_mask, mask, depth [H,W] = frame q's planes (all four or
+ *   none: NULL skips the copy; 16-byte words where source and destination share their offset in a 16-byte line, dwords otherwise)
+ *   query_tracks_2d [P,2] = x, y of row (q, q, p)            target_ts [N] int64 = tt
+ *   target_w2cs [N,16] = w2cs[tt], target_Ks [N,9] = Ks[tt]  (at the TIME id, as the reference indexes them)
+ *   target_tracks_2d [N,P,2] = row.xy   (8-byte aligned, as query_tracks_2d)
+ *   vis = 1 - sigmoid(row.z), conf = 1 - sigmoid(row.w); target_visibles = vis conf > 0.5, target_invisibles = (1 - vis) conf > 0.5
+ *   (uint8), target_confidences = conf where either holds, else 0                                              (utils.py:53-66)
+ *   target_track_depths [N,P], target_track_imgs [N,3,P]: depths[t], imgs[t] sampled bilinearly at row.xy, the coordinates clamped
+ *   to the image before any address is formed (grid_sample's align_corners=True, padding_mode="border"; d4gs_lift_tracks' rule)
+ * and the element tables of d4gs_track_losses_fwd, element (n, p) at n P + p: rows = n; pix = int(y) W + int(x) of the query
+ * (truncated), or -1 outside the image; vis (uint8) = target_visibles and pix >= 0; weights = target_confidences
+ * sum_n' exp(-2 |ts - target_ts[n']| / num_frames), 0 where pix = -1.  target_tracks_2d, target_track_depths and target_Ks are those
+ * tables' tgt_2d, tgt_depth and Ks as they are.
+ * status [1] int32: the launch ORs in 1 (index outside 0 .. F-1), 2 (a target outside 0 .. F-1), 4 (a target's time id outside
+ * 0 .. F-1), 8 (offsets of the query frame negative, decreasing, beyond n_rows or no multiple of F).  With any of them NOTHING is
+ * addressed through the offending value: the whole batch is written as padding (P_q = 0; planes, matrices and time ids 0).
+ * F H W 3 and N P 3 <= 2^31 - 1. */
+#define D4GS_FEED_API __attribute__((visibility("default")))
+D4GS_FEED_API int d4gs_feed_draw(int64_t *counter, uint64_t seed, int32_t start, int32_t end, int32_t n, int32_t *targets, void *stream);
+D4GS_FEED_API int d4gs_feed_draw_cpu(int64_t *counter /* [host] */, uint64_t seed, int32_t start, int32_t end, int32_t n,
+                                     int32_t *targets /* [host] */);
+D4GS_FEED_API int d4gs_feed_batch(const float *imgs, const float *depths, const float *masks, const float *valid_masks, const float *Ks,
+                                  const float *w2cs, const int64_t *time_ids, const float *tracks, const int64_t *offsets, int64_t n_rows,
+                                  const int32_t *index, const int32_t *targets, int32_t F, int32_t H, int32_t W, int32_t N, int32_t P,
+                                  int32_t num_frames, int64_t *ts, float *w2c, float *K, float *img, float *valid_mask, float *mask,
+                                  float *depth, float *query_tracks_2d, int64_t *target_ts, float *target_w2cs, float *target_Ks,
+                                  float *target_tracks_2d, uint8_t *target_visibles, uint8_t *target_invisibles,
+                                  float *target_confidences, float *target_track_depths, float *target_track_imgs, int32_t *pix,
+                                  int32_t *rows, uint8_t *vis, float *weights, int32_t *n_queries, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
