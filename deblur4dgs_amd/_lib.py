@@ -5,7 +5,8 @@ STRUCT_NAMES).  The type rules and the [host] / [device] marks are in `_ctype`; 
 Prototypes under D4GS_API are PROTOTYPES / EXPORTS; the scene-initialisation block under D4GS_INIT_API is INIT_PROTOTYPES, the
 evaluation-time block (test-time pose refinement) under D4GS_EVAL_API is EVAL_PROTOTYPES, the data-preparation block (observations
 from raw arrays) under D4GS_DATA_API is DATA_PROTOTYPES, the warm-up block (the track fit) under D4GS_FIT_API is FIT_PROTOTYPES, the
-per-step block (batch assembly from a device-resident clip) under D4GS_FEED_API is FEED_PROTOTYPES.
+per-step block (batch assembly from a device-resident clip) under D4GS_FEED_API is FEED_PROTOTYPES, the LPIPS block (the metric's
+passes around its convolutions) under D4GS_LPIPS_API is LPIPS_PROTOTYPES.
 
 The product path has NO fallback: if the HIP library is missing this module raises at first use, and every
 entry point raises RuntimeError on a non-zero return code with `d4gs_last_error()`.
@@ -54,7 +55,7 @@ def _ctype(base, stars, mark, structs, text):
     raise ValueError(f"d4gs.h: cannot bind the type of `{text}`")
 
 
-def parse(text, init=None, *, eval=None, data=None, fit=None, feed=None):
+def parse(text, init=None, *, eval=None, data=None, fit=None, feed=None, lpips=None):
     """-> (constants, structs, prototypes) of the header `text`: {name without D4GS_: int}, {Python name: ctypes.Structure},
     {entry point: (restype, argtypes)}.  Strict: whatever is left of the header once every enum, struct and prototype has been
     taken out, and every declaration that does not parse completely, raises ValueError with the offending text.
@@ -62,7 +63,8 @@ def parse(text, init=None, *, eval=None, data=None, fit=None, feed=None):
     by the same rules, counted in the same way, and land in the dict `init` when one is given; so do those under D4GS_EVAL_API
     (test-time pose refinement) and the dict `eval`, and those under D4GS_DATA_API (observations from raw
     arrays) and the dict `data`, and those under D4GS_FIT_API (the track fit) and the dict
-    `fit`, and those under D4GS_FEED_API (batch assembly) and the dict `feed`."""
+    `fit`, and those under D4GS_FEED_API (batch assembly) and the dict `feed`, and those under D4GS_LPIPS_API
+    (the LPIPS passes) and the dict `lpips`."""
     def comment(m):  # an inline comment (code before it on its line) leaves its mark as a token; every other comment is blank
         inline = text[text.rfind("\n", 0, m.start()) + 1:m.start()].strip()
         found = re.search(r"\[(host|device)\]", m.group()) if inline else None
@@ -76,9 +78,11 @@ def parse(text, init=None, *, eval=None, data=None, fit=None, feed=None):
     n_data = max(len(re.findall(r"\bD4GS_DATA_API\b", code)) - 1, 0)
     n_fit = max(len(re.findall(r"\bD4GS_FIT_API\b", code)) - 1, 0)
     n_feed = max(len(re.findall(r"\bD4GS_FEED_API\b", code)) - 1, 0)
+    n_lpips = max(len(re.findall(r"\bD4GS_LPIPS_API\b", code)) - 1, 0)
     code = re.sub(r"^[ \t]*#.*$", "", code, flags=re.M)
     structs, by_c_name, prototypes, init, eval = {}, {}, {}, {} if init is None else init, {} if eval is None else eval
     data, fit, feed = {} if data is None else data, {} if fit is None else fit, {} if feed is None else feed
+    lpips = {} if lpips is None else lpips
 
     def enum(m):
         for item in filter(None, (x.strip() for x in m.group(1).split(","))):
@@ -126,8 +130,9 @@ def parse(text, init=None, *, eval=None, data=None, fit=None, feed=None):
     code = re.sub(r"\bD4GS_DATA_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, data), code)
     code = re.sub(r"\bD4GS_FIT_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, fit), code)
     code = re.sub(r"\bD4GS_FEED_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, feed), code)
+    code = re.sub(r"\bD4GS_LPIPS_API\b([^;()]*?)\b(\w+)\s*\(([^;()]*)\)\s*;", lambda m: prototype(m, lpips), code)
     for block, table, n in (("INIT", init, n_init), ("EVAL", eval, n_eval), ("DATA", data, n_data), ("FIT", fit, n_fit),
-                            ("FEED", feed, n_feed)):
+                            ("FEED", feed, n_feed), ("LPIPS", lpips, n_lpips)):
         if len(table) != n:
             raise ValueError(f"d4gs.h: {len(table)} of {n} D4GS_{block}_API prototypes parsed; not understood: `{' '.join(code.split())}`")
     if code.split() != ["extern", '"C"', "{", "}"] or len(prototypes) != n_api or len(structs) != n_structs:
@@ -141,9 +146,10 @@ EVAL_PROTOTYPES = {}  # the D4GS_EVAL_API block: pose_refine.py's
 DATA_PROTOTYPES = {}  # the D4GS_DATA_API block: observations.py's
 FIT_PROTOTYPES = {}   # the D4GS_FIT_API block: the track fit of losses.py / scene_init.py
 FEED_PROTOTYPES = {}  # the D4GS_FEED_API block: feed.py's
+LPIPS_PROTOTYPES = {}  # the D4GS_LPIPS_API block: lpips.py's
 with open(HEADER) as _f:
     CONSTANTS, STRUCTS, PROTOTYPES = parse(_f.read(), INIT_PROTOTYPES, eval=EVAL_PROTOTYPES, data=DATA_PROTOTYPES, fit=FIT_PROTOTYPES,
-                                           feed=FEED_PROTOTYPES)
+                                           feed=FEED_PROTOTYPES, lpips=LPIPS_PROTOTYPES)
 # the package's names: VERSION, TILE, GEOM_STRIDE, ADAM_CHUNK, RAW_PARAMS ... ANTIALIASED, DEPTH_*, ROWS_*; Dims ... AdamRec
 globals().update(CONSTANTS)
 globals().update(STRUCTS)
@@ -159,7 +165,7 @@ _lib = None
 
 def bind(cdll: C.CDLL) -> C.CDLL:
     """Give every entry point of the header its restype and argtypes on a loaded library."""
-    later = {**INIT_PROTOTYPES, **EVAL_PROTOTYPES, **DATA_PROTOTYPES, **FIT_PROTOTYPES, **FEED_PROTOTYPES}
+    later = {**INIT_PROTOTYPES, **EVAL_PROTOTYPES, **DATA_PROTOTYPES, **FIT_PROTOTYPES, **FEED_PROTOTYPES, **LPIPS_PROTOTYPES}
     for name, (restype, argtypes) in {**PROTOTYPES, **later}.items():
         if (name in APPENDED or name in later) and os.environ.get("D4GS_LIB_PATH") and not hasattr(cdll, name):
             continue

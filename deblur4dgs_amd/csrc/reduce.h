@@ -1,4 +1,4 @@
-// reduce.h -- the one fixed-order sum of the loss and metric kernels (photometric, metrics, warp, trimmed, motion_regs, sh): device
+// reduce.h -- the one fixed-order sum of the loss and metric kernels (photometric, metrics, warp, trimmed, motion_regs, sh, lpips): device
 // code only, and nothing on the frame's hot path includes it.  Every float sum that these kernels promise bit for
 // bit, on every run and graph replay, is associated in this order and no other (tests/test_gpu_ordered_sum.py restates it in NumPy
 // from this comment and compares the bits):

@@ -10,8 +10,9 @@ map, for M masks of B images at once.  `ValidationMetrics` evaluates the validat
 M = 3 in one launch and returns the reference's `val/*` keys.
 
 The masked SSIM is the reference's own (count-normalised partial convolutions), not the pytorch_msssim one of
-`losses.photometric_loss`.  Images are channel-last [B,H,W,3] as the rasterizer returns them.  `mLPIPS` is not provided: its AlexNet
-backbone weights are not part of this project; importing the name raises an ImportError that says so.
+`losses.photometric_loss`.  Images are channel-last [B,H,W,3] as the rasterizer returns them.  `mLPIPS` lives in
+`deblur4dgs_amd.lpips`, because it is built around a network whose AlexNet weights the user supplies; importing the name from here
+raises an ImportError that says so.  `ValidationMetrics(lpips=net)` adds the three LPIPS keys.
 """
 from __future__ import annotations
 
@@ -28,7 +29,8 @@ __all__ = ["masked_image_metrics", "compute_psnr", "mPSNR", "mSSIM", "PCK", "Val
 def __getattr__(name):
     if name == "mLPIPS":
         raise ImportError("deblur4dgs_amd.metrics has no mLPIPS: the metric needs the pretrained AlexNet LPIPS weights, which this project "
-                          "does not ship; score LPIPS with the reference's flow3d.metrics.mLPIPS where torchmetrics is installed")
+                          "does not ship; use deblur4dgs_amd.lpips.mLPIPS(LPIPS(trunk, lins)) with torchvision's AlexNet weights and the "
+                          "LPIPS v0.1 alex.pth")
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -161,18 +163,27 @@ class PCK(_Metric):
 
 
 class ValidationMetrics:
-    """The six image numbers of the reference's Validator (flow3d/validator.py:460-499), all masks of a frame in one launch.
+    """The image numbers of the reference's Validator (flow3d/validator.py:460-499) - six, or all nine with `lpips=` - all masks of
+    a frame in one launch.
     has_bg: main = valid, fg = fg * valid, bg = (1 - fg) * valid.  Without a background the reference scores only fg * valid as the
-    main mask and never updates the fg / bg metrics; their keys are nan here."""
+    main mask and never updates the fg / bg metrics; their keys are nan here.
+    lpips: a `deblur4dgs_amd.lpips.LPIPS` (on the images' device) makes it the reference's nine: `update` also scores the three
+    masks with one `masked_sums` call, and `compute()` adds val/lpips, val/fg_lpips and val/bg_lpips (LPIPS_KEYS)."""
     KEYS = ("val/psnr", "val/ssim", "val/fg_psnr", "val/fg_ssim", "val/bg_psnr", "val/bg_ssim")
+    LPIPS_KEYS = ("val/lpips", "val/fg_lpips", "val/bg_lpips")
 
-    def __init__(self, has_bg: bool = True):
+    def __init__(self, has_bg: bool = True, lpips=None):
         self.has_bg = bool(has_bg)
+        self.lpips_net = lpips
         self.reset()
 
     def reset(self):
         self.psnr = [mPSNR() for _ in range(3)]
         self.ssim = [mSSIM() for _ in range(3)]
+        if self.lpips_net is not None:
+            from .lpips import mLPIPS
+
+            self.lpips = [mLPIPS(self.lpips_net) for _ in range(3)]
 
     @torch.no_grad()
     def update(self, rendered_img, img, valid_mask, fg_mask):
@@ -184,6 +195,10 @@ class ValidationMetrics:
         for i in range(masks.shape[0]):
             self.psnr[i]._append(sse[i], msum[i])
             self.ssim[i].similarity.append(ssim[i])
+        if self.lpips_net is not None:
+            scores, total = self.lpips_net.masked_sums(rendered_img, img, masks)
+            for i in range(masks.shape[0]):
+                self.lpips[i]._append(scores[i], total[i])
 
     def compute(self) -> dict:
         out = {}
@@ -191,4 +206,7 @@ class ValidationMetrics:
             seen = len(self.psnr[i]) > 0
             out[f"val/{name}psnr"] = self.psnr[i].compute() if seen else torch.tensor(float("nan"))
             out[f"val/{name}ssim"] = self.ssim[i].compute() if seen else torch.tensor(float("nan"))
+        if self.lpips_net is not None:
+            for i, name in enumerate(("", "fg_", "bg_")):
+                out[f"val/{name}lpips"] = self.lpips[i].compute() if len(self.lpips[i]) > 0 else torch.tensor(float("nan"))
         return out

@@ -168,8 +168,9 @@ def validate_with_pose_refinement(model, frames, metrics=None, **refine_kw) -> d
     """The reference's validation loop (flow3d/validator.py:400-475) over `frames`: an iterable of dicts with `t`, `w2c` [4,4] or
     [1,4,4], `K`, `img` [H,W,3] or [1,H,W,3] and, optionally, `valid_mask` [H,W] (default: ones) and `fg_mask` [H,W] (default:
     zeros).  Each frame's pose is refined by `refine_pose(**refine_kw)`; the last iteration's render is scored by
-    `metrics.ValidationMetrics` under the main, foreground and background masks, as the reference feeds its metrics.  No LPIPS.
-    -> the reference's `val/*` keys (device scalars)."""
+    `metrics.ValidationMetrics` under the main, foreground and background masks, as the reference feeds its metrics.  Pass
+    `metrics=ValidationMetrics(has_bg=model.has_bg, lpips=LPIPS(trunk, lins))` for the three LPIPS keys as well (deblur4dgs_amd.lpips).
+    -> the reference's `val/*` keys (device scalars): six, or nine with `lpips=`."""
     from .metrics import ValidationMetrics
 
     metrics = ValidationMetrics(has_bg=model.has_bg) if metrics is None else metrics

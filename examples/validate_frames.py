@@ -4,13 +4,15 @@
 A few `mode="mid"` (sharp) views of the synthetic scene are held against the same views of a perturbed copy of it, which also
 supplies the foreground mask and, as the valid mask, the pixels it covers.  `ValidationMetrics` evaluates the main, foreground and
 background masks of a frame in one launch (deblur4dgs_amd.metrics, DESIGN.md section 19) and returns the reference's `val/*` keys;
-nothing is read on the host until the dict is printed.  LPIPS is not part of it (its network weights are not shipped).
+nothing is read on the host until the dict is printed.  With --lpips-trunk and --lpips-lins (torchvision's AlexNet weights and the
+LPIPS v0.1 alex.pth; the project ships neither) the three LPIPS keys are scored too: nine keys, as the reference reports.
 With --pose-opt every frame's camera pose is first refined against its image, as the reference's `validate_imgs_with_optimization`
 does (flow3d/validator.py:400-475, the path `run_testing.py` scores through; deblur4dgs_amd.pose_refine): the
 views are then rendered from a slightly wrong pose, and the refinement - one HIP graph replayed --pose-iters times - has to find
 the right one.
 
     python examples/validate_frames.py [--frames 1 3 5] [--width 512 --height 288] [--pose-opt [--pose-iters 500]]
+                                       [--lpips-trunk alexnet.pth --lpips-lins alex.pth]
 """
 from __future__ import annotations
 
@@ -28,13 +30,13 @@ from deblur4dgs_amd.pose_refine import validate_with_pose_refinement  # noqa: E4
 from train_dynamic_step import build  # noqa: E402  (the synthetic scene of the training example)
 
 
-def pose_opt(model, frames, w2c, K, W, H, iters):
+def pose_opt(model, frames, w2c, K, W, H, iters, lpips=None):
     """Score the model's own views from a pose that is off by a small rotation and a shift, before and after refining it."""
     dev = w2c.device
     wrong = w2c[0].clone()
     wrong[:3, :3] = (torch.eye(3, device=dev) + 0.01 * torch.tensor([[0.0, -0.5, -0.7], [0.5, 0.0, -0.5], [0.7, 0.5, 0.0]], device=dev)) @ wrong[:3, :3]
     wrong[:3, 3] += torch.tensor([0.02, -0.015, 0.03], device=dev)
-    batch, before = [], ValidationMetrics(has_bg=True)
+    batch, before = [], ValidationMetrics(has_bg=True, lpips=lpips)
     with torch.no_grad():
         for t in frames:
             gt = model.render(t, w2c, K, (W, H), return_mask=True, mode="mid")
@@ -43,18 +45,24 @@ def pose_opt(model, frames, w2c, K, W, H, iters):
             before.update(model.render(t, wrong[None], K, (W, H), mode="mid")["img"], f["img"], f["valid_mask"], f["fg_mask"])
             batch.append(f)
     print("unrefined:", {k: round(float(v), 5) for k, v in before.compute().items()})
-    out = {k: float(v) for k, v in validate_with_pose_refinement(model, batch, iters=iters).items()}
+    out = {k: float(v) for k, v in validate_with_pose_refinement(model, batch, ValidationMetrics(has_bg=True, lpips=lpips), iters=iters).items()}
     print("refined:  ", {k: round(v, 5) for k, v in out.items()})
     return out
 
 
-def main(frames=(1, 3, 5), W=512, H=288, n_fg=40_000, n_bg=100_000, dev="cuda:0", seed=0, pose_iters=0):
+def main(frames=(1, 3, 5), W=512, H=288, n_fg=40_000, n_bg=100_000, dev="cuda:0", seed=0, pose_iters=0, lpips_trunk=None,
+         lpips_lins=None):
     model, sc = build(n_fg=n_fg, n_bg=n_bg, W=W, H=H, dev=dev, seed=seed)
     w2c, K = sc["viewmat"][None].to(dev), sc["K"][None].to(dev)
+    lpips = None
+    if lpips_trunk and lpips_lins:  # a path or a state dict each
+        from deblur4dgs_amd.lpips import LPIPS
+
+        lpips = LPIPS(lpips_trunk, lpips_lins).to(dev)
     if pose_iters:
-        return pose_opt(model, frames, w2c, K, W, H, pose_iters)
+        return pose_opt(model, frames, w2c, K, W, H, pose_iters, lpips)
     target, _ = build(n_fg=n_fg, n_bg=n_bg, W=W, H=H, dev=dev, seed=seed + 1)
-    metrics, train_psnr = ValidationMetrics(has_bg=True), mPSNR()
+    metrics, train_psnr = ValidationMetrics(has_bg=True, lpips=lpips), mPSNR()
     with torch.no_grad():
         for t in frames:
             rendered = model.render(t, w2c, K, (W, H), mode="mid")["img"]
@@ -78,5 +86,10 @@ if __name__ == "__main__":
     ap.add_argument("--bg", type=int, default=100_000)
     ap.add_argument("--pose-opt", action="store_true", help="refine every frame's pose against its image before scoring it")
     ap.add_argument("--pose-iters", type=int, default=500, help="iterations of --pose-opt per frame (the reference's 500)")
+    ap.add_argument("--lpips-trunk", default=None, help="torchvision's AlexNet state dict; with --lpips-lins: nine keys")
+    ap.add_argument("--lpips-lins", default=None, help="the LPIPS v0.1 alex.pth (lin{0..4}.model.1.weight)")
     a = ap.parse_args()
-    main(tuple(a.frames), a.width, a.height, a.fg, a.bg, pose_iters=a.pose_iters if a.pose_opt else 0)
+    if bool(a.lpips_trunk) != bool(a.lpips_lins):
+        ap.error("--lpips-trunk and --lpips-lins come together")
+    main(tuple(a.frames), a.width, a.height, a.fg, a.bg, pose_iters=a.pose_iters if a.pose_opt else 0, lpips_trunk=a.lpips_trunk,
+         lpips_lins=a.lpips_lins)

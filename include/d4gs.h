@@ -1060,6 +1060,46 @@ D4GS_FEED_API int d4gs_feed_batch(const float *imgs, const float *depths, const 
                                   float *target_confidences, float *target_track_depths, float *target_track_imgs, int32_t *pix,
                                   int32_t *rows, uint8_t *vis, float *weights, int32_t *n_queries, int32_t *status, void *stream);
 
+/* LPIPS (appended; D4GS_VERSION unchanged): everything of the validator's ninth metric that is not a convolution - the reference's
+ * PNetLin(pnet_type='alex', version='0.1') (models/networks_basic.py) as flow3d/metrics.py:250-279 and run_compute_metrics.py use it.
+ * The AlexNet trunk's five convolutions run in torch (deblur4dgs_amd/lpips.py); these entry points are what surrounds them.  The block
+ * is declared under a macro of its own, like the five before it: D4GS_LPIPS_API is the binding's LPIPS_PROTOTYPES; exported, parsed by
+ * the same strict rules and bound by the same call.  csrc/lpips.hip; DESIGN.md section 29.  Every pointer is DEVICE memory unless
+ * marked, tensors are contiguous fp32 unless stated, every launch is on `stream`, nothing is read on the host, no atomics, every result
+ * is bitwise reproducible, and nothing has a backward.  D4GS_EINVAL with a message that names the argument, by host arithmetic alone and
+ * before any HIP call: a NULL required pointer, a misaligned pointer, a size < 1, H or W < 31 (the trunk's smallest image), C > 4096, or
+ * a size beyond the grid.  masks == NULL stands for one mask of ones (M must be 1).
+ *
+ * d4gs_lpips_prepare: ONE launch.  pred, target [B,H,W,3] channel-last, masks [M,B,H,W] or NULL -> out [2,M,B,3,H,W] (pred first), the
+ * trunk's input: x = image * mask (with masks), x = x * 2 - 1 (normalize != 0), then the scaling layer (x - shift) / scale with shift
+ * (-.030, -.088, -.188) and scale (.458, .448, .450) - a division; each step rounded to fp32 in this order, as torch evaluates it.
+ *
+ * d4gs_lpips_layer: ONE launch per layer.  f0, f1 [n,C,h,w] (NCHW), weights [C] -> out [n,h,w]:
+ *   d = sum_c weights_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2,  |f| = sqrt(sum_c f_c^2) over the pixel's column,
+ * in the direct form (identical inputs give exactly 0.0; an all-zero column normalises to zero), accumulated in double and rounded once.
+ * 1 <= C <= 4096.  From C = 128 on a block holds 16 pixels x 16 channel slices, below that 64 x 4: the choice depends on C alone, so a
+ * pixel's value does not depend on n.  n h w <= 2^31 - 1.
+ *
+ * d4gs_lpips_score: two launches.  layers [5] (a HOST array of device pointers): the layer maps [M B, h_k, w_k]; sizes [10] (HOST):
+ * h_0, w_0, ... h_4, w_4.  Every map is upsampled to H x W as nn.Upsample(scale_factor=(1.*H/h, 1.*W/w), mode='bilinear',
+ * align_corners=False) does (source = (dst + 0.5) / scale_factor - 0.5, clamped at 0; in double), the five are added in layer order, and
+ * the sum is rounded to fp32: score_map [M,B,H,W], written when not NULL.  out [M B, 2] doubles = sum score * mask, sum mask per (m, b),
+ * from the fp32 scores, by block partials and one ordered total: partials is [d4gs_lpips_score_blocks(M,B,H,W), 2] doubles of scratch,
+ * 8-byte aligned.  The result of an (m, b) does not depend on M.  d4gs_lpips_score_blocks is host arithmetic alone and returns 0 for
+ * sizes the entry point refuses (M B <= 65535).
+ *
+ * d4gs_lpips_mean: ONE launch.  layers, sizes as above with maps [n, h_k, w_k] -> out [n] doubles: the mean over h_k x w_k of every
+ * layer map (an ordered total in double), added in layer order - the reference's spatial=False form. */
+#define D4GS_LPIPS_API __attribute__((visibility("default")))
+D4GS_LPIPS_API int d4gs_lpips_prepare(const float *pred, const float *target, const float *masks, int32_t M, int32_t B, int32_t H,
+                                      int32_t W, int32_t normalize, float *out, void *stream);
+D4GS_LPIPS_API int d4gs_lpips_layer(const float *f0, const float *f1, const float *weights, int32_t n, int32_t C, int32_t h, int32_t w,
+                                    float *out, void *stream);
+D4GS_LPIPS_API int64_t d4gs_lpips_score_blocks(int32_t M, int32_t B, int32_t H, int32_t W);
+D4GS_LPIPS_API int d4gs_lpips_score(const float *const *layers, const int32_t *sizes /* [host] */, const float *masks, int32_t M,
+                                    int32_t B, int32_t H, int32_t W, float *score_map, double *partials, double *out, void *stream);
+D4GS_LPIPS_API int d4gs_lpips_mean(const float *const *layers, const int32_t *sizes /* [host] */, int32_t n, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
