@@ -95,6 +95,14 @@ __device__ __forceinline__ int d4gs_byte_x16(uint32_t w) {
   if constexpr (B == 3) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "v"(4u), "v"(w));
   return r;
 }
+// Keeps every dword of a staged float4 record live, so that its LDS read stays ONE ds_read_b128.  The narrow step uses three dwords of
+// the conic record (w is the block filter's threshold) and, at D = 3, three of the colour record; left alone the compiler narrows
+// those reads to ds_read_b96 - which the LDS services in eight 8-lane groups, 8 cycles, where a ds_read_b128 takes four 16-lane
+// groups, 4 cycles: the step's reads cost 4 + 8 + 8 = 20 LDS cycles per wave instead of 12, on the pipe the four SIMDs of a CU share.
+// Measured (profiles/ab_fwd_row_bcast.txt): cfg2's forward 228 -> 210 us.  No instruction, no register (the b128 destination is four
+// consecutive registers either way: the allocation did not change in any instantiation).
+__device__ __forceinline__ void d4gs_read_whole(const float4 &r) { asm volatile("" ::"v"(r.w)); }
+
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // D = 0 (with DEPTH): the depth-only render modes "D" / "ED".  A batch stages the geometry record and the box only - no colour row,
 // no colour accumulators - and the one channel composites the record's depth (g0.w); the narrow kernels' loop and null record.
@@ -302,6 +310,7 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
     auto step = [&](const unsigned long long actm, const int j16 /* 16 x the staged splat's slot: the byte offset of its records */) {
       const float4 g0 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sg0) + j16);
       const float4 g1 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sg1) + j16);
+      if constexpr (DV <= 1) d4gs_read_whole(g1);  // (the 16-channel kernel shares this step and stays as it is)
       const float dx = g0.x - pxf, dy = g0.y - pyf;
       const float sigma = splat_sigma2(g1, dx, dy);  // sigma * log2(e)
       const float alpha = fminf(0.999f, g0.z * __builtin_amdgcn_exp2f(-sigma));
@@ -326,6 +335,7 @@ __device__ __forceinline__ void raster_fwd_r_body(const RasterFwdArgs &a) {
 #pragma unroll
         for (int v = 0; v < DV; v++) {
           const float4 c4 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(scol) + j16 * DV + 16 * v);
+          if constexpr (D == 3) d4gs_read_whole(c4);  // (three of its four dwords used: D = 1, 2 read 4 and 8 bytes, cheaper still)
           if (v * 4 < D) acc[v * 4] = __builtin_fmaf(c4.x, vis, acc[v * 4]);
           if (v * 4 + 1 < D) acc[v * 4 + 1] = __builtin_fmaf(c4.y, vis, acc[v * 4 + 1]);
           if (v * 4 + 2 < D) acc[v * 4 + 2] = __builtin_fmaf(c4.z, vis, acc[v * 4 + 2]);
