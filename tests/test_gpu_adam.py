@@ -1,5 +1,10 @@
 """Multi-tensor Adam on the device (csrc/adam.hip through deblur4dgs_amd.optim.AdamGroup): numerics against the fp64 truth,
-run-to-run and group-versus-handle bit equality, capture in a HIP graph, the control steps, and the example's --hip-adam."""
+run-to-run and group-versus-handle bit equality, capture in a HIP graph, the control steps, and the example's --hip-adam.
+
+The table of tests/adam_ref.py has 8 records and one record of several chunks (800 000 elements, n % 4 = 0).  The sizes past that:
+130 records (three launches of the 64-pointer gradient patch, the NULL pointers first in the second and third), and records of
+2 049, 4 099 and 6 146 elements (2, 3 and 4 chunks of 2 048 with an n % 4 tail of 1, 3 and 2 in the last chunk), each on the
+16-byte and on the dword path."""
 import importlib.util
 import os
 
@@ -95,6 +100,91 @@ def test_group_step_equals_stepping_each_handle_and_dword_path_equals_vector_pat
             for k in ("step", "exp_avg", "exp_avg_sq"):
                 assert torch.equal(ha[i].state[pa[i]][k], hs[i].state[params[i]][k]), (i, k)
     assert float(ha[R.SKIPPED].state[pa[R.SKIPPED]]["step"]) == 6 - len([s for s in R.SKIP_STEPS if s < 6])
+
+
+ADAM_PATCH = 64  # adam.hip: constexpr int ADAM_PATCH = 64, the gradient pointers of one k_adam_set_grads launch
+MANY = 130
+MANY_SIZES = [(1, 3, 5, 64, 2049, 4099, 6146)[i % 7] for i in range(MANY)]
+MANY_WITHOUT = (64, 128)  # no gradient after the first step: the first pointer of the second and of the third patch is NULL
+
+
+def _many_gradient(step, i):
+    g = torch.Generator().manual_seed(9000 + 131 * step + i)
+    return (torch.randn(MANY_SIZES[i], generator=g) + 0.3) * (0.1 if i % 2 else 3e-3)
+
+
+def _many(device):
+    """130 tensors, every third 4 bytes off a 16-byte line (the dword path), lr and eps distinct over neighbours"""
+    from deblur4dgs_amd.optim import AdamGroup
+
+    g = torch.Generator().manual_seed(21)
+    params, group = [], AdamGroup()
+    for i, n in enumerate(MANY_SIZES):
+        off = 1 if i % 3 == 0 else 0
+        buf = torch.zeros(n + 4, device=device)
+        p = buf[off:off + n].detach()
+        p.copy_(torch.randn(n, generator=g))
+        assert device == "cpu" or p.data_ptr() % 16 == 4 * off
+        params.append(p.requires_grad_())
+    return params, group, [group.adam(p, 1e-3 * (1 + i % 5), eps=(1e-8, 1e-6, 1e-10)[i % 3]) for i, p in enumerate(params)]
+
+
+def test_a_group_of_130_tensors_in_three_pointer_patches_with_every_chunk_tail():
+    """130 records: d4gs_adam_set_grads patches their gradient pointers in launches of 64, 64 and 2, and k_adam finds each block's
+    record among 130; the sizes 2 049, 4 099 and 6 146 are records of 2, 3 and 4 chunks whose last chunk ends in an n % 4 tail of
+    1, 3 and 2 elements, on the 16-byte path and, every third tensor, on the dword path.  Six steps, the first eager with every
+    gradient (it creates the state), the other five replayed from ONE captured `group.step()` - the only path on which the pointers
+    are patched by the kernel (an eager step uploads the table) - with no sync() in between, so the replays see the gradient
+    pointers the patch launches wrote and no others.  Bitwise equal to the same steps run eagerly in one launch, to stepping each
+    handle alone, and to the CPU twin on copies; tensors 64 and 128 get no gradient after the first step and stay untouched."""
+    from deblur4dgs_amd import _lib as L
+    from deblur4dgs_amd.optim import adam_step_cpu
+
+    assert -(-MANY // ADAM_PATCH) == 3 and all(i % ADAM_PATCH == 0 for i in MANY_WITHOUT)
+    assert {n % 4 for n in MANY_SIZES if n > L.ADAM_CHUNK} == {1, 2, 3} and {L.lib().d4gs_adam_blocks(n) for n in MANY_SIZES} == {1, 2, 3, 4}
+    steps = 6
+    grad = lambda s, i: None if (s > 0 and i in MANY_WITHOUT) else _many_gradient(s, i)
+    (pg, gg, hg), (pe, ge, he), (ph, gh, hh), (pc, gc, hc) = _many(DEV), _many(DEV), _many(DEV), _many("cpu")
+    # eager in one launch; each handle alone; the CPU twin
+    for s in range(steps):
+        for i in range(MANY):
+            g = grad(s, i)
+            for params, dev in ((pe, DEV), (ph, DEV), (pc, "cpu")):
+                params[i].grad = None if g is None else g.to(dev)
+        ge.step()
+        for h in hh:
+            h.step()
+        adam_step_cpu(gc)
+    # graph: step 0 eagerly, then one capture whose gradients are new tensors, replayed for steps 1 .. 5
+    first = [grad(0, i).to(DEV) for i in range(MANY)]  # kept alive: the table's pointers of before the patch stay readable
+    for p, g in zip(pg, first):
+        p.grad = g
+    gg.step()
+    static = [None if i in MANY_WITHOUT else torch.zeros(n, device=DEV) for i, n in enumerate(MANY_SIZES)]
+    for p, g in zip(pg, static):
+        p.grad = g
+    untouched = {i: (pg[i].detach().clone(), {k: v.clone() for k, v in hg[i].state[pg[i]].items()}) for i in MANY_WITHOUT}
+    torch.cuda.synchronize()
+    generation = gg.generation
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        gg.step()
+    for s in range(1, steps):
+        for i in range(MANY):
+            if static[i] is not None:
+                static[i].copy_(grad(s, i))
+        graph.replay()
+    torch.cuda.synchronize()
+    assert gg.generation == generation
+    for i in range(MANY):
+        for name, params, hs in (("one eager launch", pe, he), ("each handle alone", ph, hh), ("CPU twin", pc, hc)):
+            assert torch.equal(pg[i].detach().cpu(), params[i].detach().cpu()), (name, i, MANY_SIZES[i])
+            for k in ("step", "exp_avg", "exp_avg_sq"):
+                assert torch.equal(hg[i].state[pg[i]][k].cpu(), hs[i].state[params[i]][k].cpu()), (name, i, MANY_SIZES[i], k)
+        assert float(hg[i].state[pg[i]]["step"]) == (1.0 if i in MANY_WITHOUT else float(steps))
+    for i, (p0, st0) in untouched.items():
+        assert torch.equal(pg[i].detach(), p0) and all(torch.equal(hg[i].state[pg[i]][k], v) for k, v in st0.items()), i
+    assert not torch.equal(pg[4].detach()[-1:].cpu(), _many("cpu")[0][4].detach()[-1:])  # the tail element of a 2 049 record moved
 
 
 NAMES = ("means", "quats", "scales", "opacities", "colors", "motion_coefs", "rots", "transls")

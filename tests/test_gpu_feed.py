@@ -6,7 +6,10 @@ Inputs are fp32 and both sides see the same numbers.  The bounds:
   planes, Ks, w2cs, the 2-D tracks              bitwise the clip's own data: they are copied, never computed
   depth and image samples, confidences, weights within 1e-4 max|ref| of the fp64 fixture (the project's standing bound)
 The fixture's sizes: P_q = 1, 63, 64, 65 (around one wave) and 257 (one past a block of 256 lanes), N = 1 and 4; 24 x 32 frames start
-on 16-byte lines, 13 x 17 frames (663 floats) do not, and test_planes_on_every_copy_path walks every head, body and tail of the copy."""
+on 16-byte lines, 13 x 17 frames (663 floats) do not, and test_planes_on_every_copy_path walks every head, body and tail of the copy.
+Past the fixture: N = 16, 17, 28, 29 and 64 targets of a 66-frame clip with permuted time ids (the 256 lanes that write the target
+cameras take a second turn from N = 17 for the 4 x 4 matrices and from N = 29 for the 3 x 3), and draws of n = 63 and 64 frames, the
+last lanes of the one wave that draws."""
 import dataclasses
 import functools
 import os
@@ -199,7 +202,66 @@ def test_planes_on_every_copy_path():
                 assert (store[k][:shift] == -7).all() and (store[k][shift + n:] == -7).all(), (shift, q, k)
 
 
+# ------------------------------------------------------------------------------------------------- many targets: the strides
+
+FB = 256  # feed.hip: constexpr int FB = 256, the lanes by which feed_small strides over N 16 and N 9 values
+
+
+@functools.lru_cache(maxsize=None)
+def permuted_clip():
+    ids = torch.randperm(66, generator=torch.Generator().manual_seed(66))
+    assert int((ids != torch.arange(66)).sum()) > 60
+    return synthetic_clip(66, 5, 6, 3, seed=66, time_ids=ids.tolist()), ids.numpy()
+
+
+@pytest.mark.parametrize("N", (16, 17, 28, 29, 64))
+def test_target_cameras_of_many_targets_are_the_clip_rows_at_the_time_ids(N):
+    """feed_small writes target_w2cs with `i < N * 16` and target_Ks with `i < N * 9`, strided by 256 lanes: N = 16 and 28 are the last
+    sizes of one turn, 17 and 29 the first of two, 64 (the most a batch takes) has four and three.  The time ids are a permutation,
+    so a row taken at the frame and not at its time id, or at the wrong n, shows."""
+    assert (N * 16 > FB) == (N >= 17) and (N * 9 > FB) == (N >= 29) and N <= feed.MAX_TARGETS == 64
+    clip, ids = permuted_clip()
+    targets = torch.randperm(66, generator=torch.Generator().manual_seed(N))[:N].tolist()
+    q = N % 7
+    tt = ids[targets]
+    assert (tt != np.array(targets)).any()
+    w2cs, Ks = clip.w2cs.cpu().numpy(), clip.Ks.cpu().numpy()
+    t = flat(clip.batch(q, targets))
+    out = clip.buffers(N)
+    for f in dataclasses.fields(out):
+        x = getattr(out, f.name)
+        x.fill_(1) if x.dtype in (torch.uint8, torch.int32, torch.int64) else x.fill_(float("nan"))
+    out.status.zero_()
+    o = flat(clip.batch(q, targets, out=out))
+    for b in (t, o):
+        assert tuple(b["target_w2cs"].shape) == (N, 4, 4) and tuple(b["target_Ks"].shape) == (N, 3, 3)
+        assert same(b["target_w2cs"], w2cs[tt]) and same(b["target_Ks"], Ks[tt]) and same(b["target_ts"], tt)
+        assert same(b["tables/Ks"], Ks[tt].reshape(N, 9)) and int(b["ts"]) == int(ids[q]) and int(b["status"]) == 0
+    for k, v in o.items():
+        if v.is_floating_point():
+            assert not torch.isnan(v).any(), k  # every element of the buffers was written
+    clip.check(out), clip.check()
+
+
 # ---------------------------------------------------------------------------------------------------------------- the draw
+
+@pytest.mark.parametrize("n", (63, 64))
+def test_draw_of_a_whole_wave_equals_its_cpu_twin(n):
+    """k_feed_draw is one wave whose lane k keeps pick k: n = 63 and 64 (the most) use lanes 62 and 63.  From a range of exactly n
+    frames every draw is a permutation of the range; from n + 1 frames the picks are distinct and one frame is left out."""
+    assert n <= feed.MAX_TARGETS == 64  # feed.hip: FEED_MAX_TARGETS = 64, "one wave holds a draw"
+    for extra in (0, 1):
+        start, end = 1, 1 + n + extra
+        clip = synthetic_clip(66, 5, 6, 3, seed=n, start=start, end=end, n=n)
+        got = [clip.draw(31 + n).cpu().tolist() for _ in range(20)]
+        assert int(clip.counter) == 20
+        assert got == [feed.draw_cpu(31 + n, step, start, end, n) for step in range(20)]
+        assert all(len(t) == n and len(set(t)) == n and all(start <= x < end for x in t) for t in got)
+        if extra == 0:  # (Floyd's picks give a set: pick k is a new frame or frame k, so the whole range comes out in order)
+            assert all(sorted(t) == list(range(start, end)) for t in got)
+        else:  # the frame left out moves: 20 uniform picks among n + 1 frames hit about 17 different ones, a stuck draw one
+            assert len({sum(range(start, end)) - sum(t) for t in got}) > 10
+
 
 def test_draw_equals_its_cpu_twin_for_50_steps():
     clip, _ = fixture_clip("24x32")

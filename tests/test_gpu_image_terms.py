@@ -5,12 +5,17 @@ tests/test_image_terms_ref.py pins to torch's CPU ops.
 Inputs are fp32 and the statement sees the same numbers in fp64, so the two sides differ in arithmetic only.  Bounds are those of
 tests/test_gpu_trimmed_losses.py: the value at rtol 2e-6, the gradient within 1e-5 of its maximum.  No sign flip is allowed for:
 every random sharp-keep case first asserts, from the fp64 statement alone, that every non-zero |pbar mbar - tbar mbar| is at least
-1e-5 (the device forms it in double from exact window sums: its error is ~1e-16), and the tie case is exact in fp32."""
+1e-5 (the device forms it in double from exact window sums: its error is ~1e-16), and the tie case is exact in fp32.
+
+The coverage loss runs at n = 1, 255, 256, 257 (around one block), 5 740 (23 blocks) and 1 049 610 = 3 x 593 x 590, which is past
+the cap of 4 096 blocks x 256: 1 034 elements are summed in a second turn of the stride and 4 096 partials, 16 per thread, are
+totalled."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from deblur4dgs_amd import _lib as L
 from deblur4dgs_amd.losses import coverage_loss, dilate_mask, photometric_loss, sharp_keep_loss
 from tests import image_terms_ref as R
 
@@ -156,7 +161,9 @@ def test_mask_and_target_get_no_gradient():
 
 # ---------------------------------------------------------------------------------------------------------------- coverage
 
-MSE_SHAPES = {1: (1, 1, 1, 1), 255: (1, 15, 17, 1), 256: (1, 16, 16, 1), 257: (1, 1, 257, 1), 2 * 41 * 70: (2, 41, 70, 1)}
+MSE_SHAPES = {1: (1, 1, 1, 1), 255: (1, 15, 17, 1), 256: (1, 16, 16, 1), 257: (1, 1, 257, 1), 2 * 41 * 70: (2, 41, 70, 1),
+              3 * 593 * 590: (3, 593, 590, 1)}  # the last: past the block cap, 1 034 elements in a second turn
+MSE_MAX_BLOCKS = 4096  # image_terms.hip: constexpr int MSE_MAX_BLOCKS = 4096, blocks of 256
 
 
 def mse_on_gpu(acc, target):
@@ -171,6 +178,8 @@ def test_coverage_matches_the_statement(n):
     g = torch.Generator().manual_seed(n)
     acc = torch.rand(MSE_SHAPES[n], generator=g)
     assert acc.numel() == n
+    if n > 2 * 41 * 70:  # k_mse_fwd strides and k_image_terms_finish totals 4096 partials, 16 per thread
+        assert L.lib().d4gs_mse_blocks(n) == MSE_MAX_BLOCKS and n > MSE_MAX_BLOCKS * 256
     target = (torch.rand(MSE_SHAPES[n], generator=g) < 0.6).float()
     same = torch.rand(MSE_SHAPES[n], generator=g) < (0.25 if n > 1 else 0.0)
     hit = torch.where(same, torch.ones_like(acc), acc)  # acc == 1 on a quarter: opaque pixels under the all-ones target
@@ -183,6 +192,26 @@ def test_coverage_matches_the_statement(n):
     assert torch.all(got[1][same] == 0.0) and torch.all(got[1][~same] != 0.0)
     got3 = mse_on_gpu(hit[..., 0], target)  # acc without the trailing axis
     assert torch.equal(got3[0], got[0]) and torch.equal(got3[1], got[1][..., 0])
+
+
+def test_coverage_of_one_element_in_the_strided_tail():
+    """acc == target but for one element that only the second turn of k_mse_fwd's stride reaches: the loss is d^2 / n and the
+    gradient 2 d / n there and 0.0 everywhere else, both exact up to the one rounding of the quotient."""
+    shape = MSE_SHAPES[3 * 593 * 590]
+    n = 3 * 593 * 590
+    assert L.lib().d4gs_mse_blocks(n) == MSE_MAX_BLOCKS and n > MSE_MAX_BLOCKS * 256
+    at = MSE_MAX_BLOCKS * 256 + 777  # thread 9 of block 3, second turn
+    assert MSE_MAX_BLOCKS * 256 <= at < n
+    for target in (None, (torch.rand(shape, generator=torch.Generator().manual_seed(8)) < 0.6).float()):
+        acc = torch.ones(shape) if target is None else target.clone()
+        acc.view(-1)[at] -= 0.5  # 0.5 or -0.5: exact
+        loss, grad = mse_on_gpu(acc, target)
+        check((loss, grad), R.mse(acc.numpy(), None if target is None else target.numpy()), f"coverage one-hot target {target is not None}")
+        np.testing.assert_allclose(float(loss), 0.25 / n, rtol=2e-6, atol=0)
+        want = torch.zeros(n)
+        want[at] = -0.5
+        assert torch.equal(grad.view(-1) != 0, want != 0)
+        np.testing.assert_allclose(float(grad.view(-1)[at]), UP * 2 * -0.5 / n, rtol=2e-6, atol=0)
 
 
 # ------------------------------------------------------------------------------------------- reproducibility, capture, errors

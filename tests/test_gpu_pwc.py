@@ -6,7 +6,13 @@ Inputs are quantised to fp32 first and the restatement gets those same values in
 Cost volume: per element C 2^-23 mean_c(|a| |b|) - the recursive-summation bound for any order, with or without FMA - computed in
 fp64 from the inputs; backward 81 2^-23 mean_k(|v| |x|) / C likewise.  Warp and aligned L1: the photometric test's tolerances (value
 rtol 2e-6, gradients 1e-5 of their maximum); no mask flip is allowed for - every case first asserts, in fp64, that no sample's
-coverage lies within 1e-3 of the 0.999 threshold and that pred != target wherever the mask is 1."""
+coverage lies within 1e-3 of the 0.999 threshold and that pred != target wherever the mask is 1.
+
+Sizes: the cost volume and the warp at 2x2, 5x8, 7x13 and 20x33 (SPATIAL).  Past the launch caps, where the grid stops growing and
+every lane strides: the aligned L1 at 129 x 255 (32 895 px per pair against 128 blocks x 256 lanes: 127 lanes take a second pixel,
+and the partials lie 128 per pair), the backward warp at 3 x 593 x 590 (1 049 610 px against 4 096 blocks x 256: the last 1 034 px,
+all in batch 2, come in a second turn whose batch index is taken from the strided pixel index; its gradient of 2 planes per image
+is zeroed by a strided k_zero_f32)."""
 import math
 import os
 import re
@@ -17,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+from deblur4dgs_amd import _lib as L
 from deblur4dgs_amd import pwcnet as P
 from tests import pwc_ref as R
 
@@ -205,6 +212,97 @@ def test_aligned_l1_known_answers():
     eq[:, :, ::2] = target[:, :, ::2]  # sign(0) = 0
     g, = torch.autograd.grad(P.aligned_l1(eq.to(DEV).requires_grad_(), torch.zeros(3, 2, H, W, device=DEV), t).sum(), [t])
     assert not g[:, :, ::2].any() and g[:, :, 1::2].all()
+
+
+# ---- past the launch caps: the grid stops growing and every lane strides ---------------------------------------------------------------
+WB = 256                # warp.hip: constexpr int WB = REDUCE_NT (reduce.h: REDUCE_NT = 256)
+WARP_MAX_BLOCKS = 4096  # warp.hip: constexpr int WARP_MAX_BLOCKS = 4096
+AL1_CAPPED = (129, 255)       # 32 895 px per pair > 128 x 256: lanes 0..126 of block 0 take a second pixel
+WARP_CAPPED = (3, 2, 593, 590)  # 1 049 610 px > 4096 x 256: the last 1 034 take a second turn, all of them in batch 2
+
+
+def settled_flow(B, H, W, g, amp=4.0):
+    """Random flows of a few pixels.  Among so many samples some land within 1e-3 of the 0.999 coverage threshold at the border;
+    those are moved by a hundredth of a pixel, in fp64 on the CPU, until none is left (assert_conditions checks the result)."""
+    flow = amp * (torch.rand(B, 2, H, W, generator=g) - 0.5)
+    for _ in range(8):
+        cover = R.coverage(flow.double())  # exactly inside: 1 up to fp64 rounding, which the margin allows for
+        close = ((cover > 0.997) & (cover < 1 - 1e-8))[:, None].expand(B, 2, H, W)
+        if not bool(close.any()):
+            break
+        flow = torch.where(close, flow + 0.01, flow)
+    return flow
+
+
+def capped_l1_case():
+    H, W = AL1_CAPPED
+    assert L.lib().d4gs_aligned_l1_blocks(H, W) == 128 and H * W > 128 * WB  # the cap is reached and a second turn exists
+    g = torch.Generator().manual_seed(129255)
+    pred, target = torch.rand(2, 3, H, W, generator=g), torch.rand(2, 3, H, W, generator=g)
+    return pred, target, settled_flow(2, H, W, g), torch.rand(2, 1, H, W, generator=g)
+
+
+@pytest.mark.parametrize("with_mask", [True, False])
+def test_aligned_l1_past_the_block_cap_matches_restatement(with_mask):
+    """129 x 255: k_al1_fwd and k_al1_bwd run 128 blocks per pair and stride; the partials are laid out 128 per pair."""
+    pred, target, flow, mask = capped_l1_case()
+    assert_conditions(pred, target, flow)
+    check_l1(pred, target, flow, mask if with_mask else None, f"129x255 mask={with_mask}")
+
+
+def test_aligned_l1_past_the_block_cap_known_answer():
+    """pred == target but for one value per pair, at a pixel that only a second turn reaches (index >= 128 x 256), under a zero flow:
+    the loss is that |d| / (3 H W), the gradient sits on that value alone and v_target = -v_pred."""
+    H, W = AL1_CAPPED
+    assert L.lib().d4gs_aligned_l1_blocks(H, W) == 128 and H * W > 128 * WB
+    target = torch.randint(0, 16, (2, 3, H, W), generator=torch.Generator().manual_seed(4)).float() / 64  # a grid: d is exact
+    pred = target.clone()
+    spots = ((0, 1, 128, 200), (1, 2, H - 1, W - 1))  # (pair, channel, y, x)
+    for (p_, c, y, x), d in zip(spots, (0.5, -0.25)):
+        assert y * W + x >= 128 * WB
+        pred[p_, c, y, x] = target[p_, c, y, x] + d
+        assert float(pred[p_, c, y, x] - target[p_, c, y, x]) == d
+    p, t = pred.to(DEV).requires_grad_(), target.to(DEV).requires_grad_()
+    loss = P.aligned_l1(p, torch.zeros(2, 2, H, W, device=DEV), t)
+    np.testing.assert_allclose(loss.detach().cpu().numpy(), np.array([0.5, 0.25]) / (3 * H * W), rtol=2e-6, atol=0)
+    gp, gt = torch.autograd.grad(loss.sum(), [p, t])
+    want = torch.zeros(2, 3, H, W)
+    for (p_, c, y, x), d in zip(spots, (0.5, -0.25)):
+        want[p_, c, y, x] = math.copysign(float(np.float32(1.0 / (3.0 * H * W))), d)
+    assert torch.equal(gp.cpu(), want) and torch.equal(gt, -gp)
+
+
+def test_backwarp_past_the_block_cap():
+    """3 x 593 x 590: k_backwarp_fwd / _bwd run 4096 blocks and the lanes of the first five take a second pixel, whose batch
+    b = p / plane is 2; k_zero_f32 strides over the C = 2 planes of the gradient.  Values and mask against the restatement and the
+    backward against its autograd, at test_backwarp_matches_restatement's bounds; batch 2 bit for bit against a call on it alone."""
+    B, C, H, W = WARP_CAPPED
+    n_pix, first_turn = B * H * W, WARP_MAX_BLOCKS * WB
+    assert first_turn < n_pix <= first_turn + H * W and n_pix - first_turn == 1034 and first_turn > 2 * H * W  # the tail lies in batch 2
+    assert n_pix * C > first_turn  # and the zeroing strides too
+    g = torch.Generator().manual_seed(593590)
+    pred = torch.rand(B, C, H, W, generator=g)
+    flow = settled_flow(B, H, W, g, amp=6.0)
+    cover = R.coverage(flow.double())
+    assert bool(((cover - 0.999).abs() > 1e-3 - 1e-9).all()), float((cover - 0.999).abs().min())
+    want, want_mask = R.get_backwarp(pred.double(), flow.double())
+    tail = want_mask.reshape(-1)[first_turn:]
+    assert 0 < float(tail.mean()) < 1 and 0 < float(want_mask.mean()) < 1  # the second turn holds both kinds of sample
+    x = pred.to(DEV).requires_grad_()
+    got, mask = P.backwarp(x, flow.to(DEV))
+    assert torch.equal(mask.cpu().double(), want_mask) and not mask.requires_grad
+    np.testing.assert_allclose(got.detach().cpu().numpy(), want.numpy(), rtol=0, atol=2e-6 * float(want.abs().max()))
+    v = torch.randn(pred.shape, generator=torch.Generator().manual_seed(5))
+    x64 = pred.double().requires_grad_()
+    want_grad, = torch.autograd.grad((R.get_backwarp(x64, flow.double())[0] * v.double()).sum(), [x64])
+    got_grad, = torch.autograd.grad((got * v.to(DEV)).sum(), [x])
+    err = float((got_grad.cpu().double() - want_grad).abs().max())
+    print(f"backwarp {B}x{C}x{H}x{W}: max |grad| {float(want_grad.abs().max()):.3e}, max grad err {err:.3e}, "
+          f"bound {1e-5 * float(want_grad.abs().max()):.3e}")
+    np.testing.assert_allclose(got_grad.cpu().numpy(), want_grad.numpy(), rtol=0, atol=1e-5 * float(want_grad.abs().max()))
+    alone, alone_mask = P.backwarp(pred[2:3].to(DEV), flow[2:3].to(DEV))  # 349 870 px: below the cap, b = 0 throughout
+    assert H * W <= first_turn
+    assert torch.equal(got.detach()[2:3].view(torch.int32), alone.view(torch.int32)) and torch.equal(mask[2:3], alone_mask)
 
 
 # ---- the network ---------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,9 @@ Inputs are fp32 and every statement sees the same numbers in fp64, so the two si
              value); vel_dirs 1e-6 absolute (components <= 1, one rounding)
   kNN        1e-6 relative (three squares, two adds and a root in fp32: 2e-7), exact zeros, no index flip allowance
   k-means    labels equal to fp64 argmin outside points whose best two squared distances differ by < 1e-4 relative (fp32 sums of up
-             to 69 squares err by ~4e-6), at most 1 % such points; centres 1e-5 max|centre| (sums in double, one rounding)
+             to 69 squares err by ~4e-6), at most 1 % such points; centres 1e-5 max|centre| (sums in double, one rounding).
+             G = 777, 2 000 and 4 097 are 4, 8 and 17 blocks; G = 65 793 = 256 x 257 + 1 is past the cap of 256 blocks: the rows
+             are strided over (257 of them in a second turn) and every cluster's total is taken over exactly 256 partials
   Procrustes moments 1e-12 of the sum of the terms' magnitudes (double sums of <= 257 terms); bases 1e-4 max|ref|
 """
 import functools
@@ -186,7 +188,15 @@ def test_knn_matches_the_reference(name):
 
 
 # ----------------------------------------------------------------------------------------------------------------- k-means
-KM_CASES = ((777, 5, 3, 0.03), (2000, 12, 6, 0.05), (4097, 24, 20, 0.02))
+KM_CASES = ((777, 5, 3, 0.03), (2000, 12, 6, 0.05), (4097, 24, 20, 0.02), (65793, 12, 3, 0.02))
+KM_CAPPED = 256 * 257 + 1  # the last case: 256 blocks of 256 rows stride; block 0 and lane 0 of block 1 take a second row each
+
+
+def assert_kmeans_grid_is_capped(G):
+    """the row stride of k_kmeans_assign / k_kmeans_accum is taken and k_kmeans_finish totals 256 partials per cluster, one per thread"""
+    from deblur4dgs_amd import _lib as L
+
+    assert L.lib().d4gs_kmeans_blocks(G) == 256 and G > 65536
 
 
 @functools.lru_cache(maxsize=None)
@@ -215,6 +225,8 @@ def lloyd_f64(x, centres):
 @pytest.mark.parametrize("G,T,K,noise", KM_CASES)
 def test_kmeans_steps_follow_fp64_lloyd(G, T, K, noise):
     feats, first = kmeans_inputs(G, T, K, noise)
+    if G == KM_CAPPED:
+        assert_kmeans_grid_is_capped(G)
     x64 = feats.cpu().double().numpy()
     centres, labels = first.clone(), torch.full((G,), -1, dtype=torch.int32, device=DEV)
     worst_share, worst_centre = 0.0, 0.0
@@ -236,6 +248,8 @@ def test_kmeans_steps_follow_fp64_lloyd(G, T, K, noise):
         assert err <= 1e-5, it
     print(f"G={G} T={T} K={K}: largest excluded share {worst_share:.2e} (cap 1e-2), largest centre error {worst_centre:.2e} (bound 1e-5)")
     assert worst_share <= 1e-2
+    if G == KM_CAPPED:  # chosen on the CPU: the fp64 steps alone leave no row within the margin (the smallest is 7e-3), so every label is held
+        assert worst_share == 0.0
 
 
 @pytest.mark.parametrize("G,T,K,noise", KM_CASES)
@@ -266,6 +280,27 @@ def test_kmeans_ties_go_to_the_lower_index_and_an_empty_cluster_keeps_its_centre
     assert not bool((got == 2).any()) and bool((got[:5] == 0).all()) and bool((got[5:] == 1).all())
     assert torch.equal(bits(centres[2]), bits(twin)) and int(changed.item()) == 600
     assert torch.allclose(centres[1].cpu().double(), x[5:].cpu().double().mean(0), rtol=0, atol=1e-6)
+    # past the block cap: rows that only the stride reaches tie between centres 1 and 2, and cluster 3 has members among them alone
+    G = KM_CAPPED
+    assert_kmeans_grid_is_capped(G)
+    x64 = torch.randn(G, 7, generator=gen)
+    centres = torch.stack([twin + 9.0, twin, twin, twin - 9.0]).to(DEV)
+    x64[:5] += 9.0
+    lone = torch.tensor([65536, 65540, 65791, 65792])  # second-turn rows: lanes 0, 4 and 255 of block 0, lane 0 of block 1
+    x64[lone] -= 9.0
+    x, x64 = x64.to(DEV), x64.double()
+    labels = torch.full((G,), 2, dtype=torch.int32, device=DEV)
+    changed = S.kmeans_step(x, centres, labels, 1)
+    got = labels.cpu()
+    want = torch.ones(G, dtype=torch.int32)
+    want[:5], want[lone] = 0, 3
+    assert torch.equal(got, want) and int((got[65536:] == 1).sum()) == G - 65536 - len(lone)  # ties behind row 65 536: the lower index
+    assert torch.equal(bits(centres[2]), bits(twin)) and int(changed.item()) == G
+    rest = torch.ones(G, dtype=torch.bool)
+    rest[:5], rest[lone] = False, False
+    assert torch.allclose(centres[3].cpu().double(), x64[lone].mean(0), rtol=0, atol=1e-6)  # their mean, not "kept as empty"
+    assert torch.allclose(centres[1].cpu().double(), x64[rest].mean(0), rtol=0, atol=1e-6)
+    assert torch.allclose(centres[0].cpu().double(), x64[:5].mean(0), rtol=0, atol=1e-6)
 
 
 @pytest.mark.parametrize("G,T,K,noise", KM_CASES)
